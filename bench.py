@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — voxel-frames/s of the Neural Marionette hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): AIST++-shaped synthetic clips, 64^3 occupancy grid,
 T = 16, B = 4 clips per GPU, full NeuralMarionette.forward (keypoint detector incl. all 11
@@ -10,9 +10,18 @@ losses + HSVRNNBVH.encode), fp32, seeded random weights of the reference archite
 resident in HBM.  N > 1: independent clips per rank (weak scaling, no data-path collective);
 launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`.
 
-Rank 0 prints ONE JSON line with the throughput, the roofline of the dominant kernel
-(HIP-event timed inside the timed region, algorithmic FLOPs) and the CPU baseline (the
-oracle — a port of the reference on PyTorch-CPU ops — timed on the host cores, N = 1 only).
+Rank 0 prints ONE JSON line with the throughput (`value`, `ms_per_step`).  A plain run only sets up,
+warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.  --full adds
+what takes runs or work of its own: the roofline of the dominant kernel (HIP-event timed inside the
+timed region, algorithmic FLOPs), the secondary measurements (other precisions, the training steps,
+other configurations) and the CPU baseline (the oracle — a port of the reference on PyTorch-CPU
+ops — timed on the host cores, N = 1 only); --no-extras / --no-cpu-baseline trim a --full run.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned, one
+DIR/<name>.npy per tensor of the step's output dict (float32, float64 for float64 / integer
+tensors); a tensor of more than DUMP_CAP elements is written as a fixed, seeded sample of DUMP_CAP
+of its flattened elements (indices ascending).  Inputs and weights are seeded, so the same
+arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -32,10 +41,14 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); default: WORLD_SIZE under a torch.distributed launcher, else 1")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (exact-fp32 forward, training step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the secondary measurements and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; large tensors as a seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (exact-fp32 forward, training step)")
     ap.add_argument("--workload", choices=["forward", "train"], default="forward",
                     help="forward (default, BASELINE configs[1]): full NeuralMarionette.forward; train (configs[2] shape, fp32): one "
                          "detector-mode training step = forward + backward + gradient all-reduce + Adam")
@@ -48,8 +61,11 @@ def parse_args(argv=None):
                          "Forces --no-extras --no-cpu-baseline; not a scaling number")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="run only the multi-rank plumbing of this file (rendezvous, barrier, all-reduce of ones, MAX-reduce of the elapsed "
-                         "time) and print it as one JSON line; backend gloo when no GPU is visible (tests/test_sharding_cpu.py)")
-    return ap.parse_args(argv)
+                         "time) and print it as one JSON line; backend gloo when fewer GPUs than ranks are visible (tests/test_sharding_cpu.py)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def launch_ranks(args, argv) -> int:
@@ -475,9 +491,10 @@ def other_configs(dev, timed):
 
 
 def dist_selftest(world, rank, local):
-    """The multi-rank plumbing of main() without the GPU work: rendezvous, barrier, all-reduce of ones, MAX-reduce of a time."""
+    """The multi-rank plumbing of main() without the GPU work: rendezvous, barrier, all-reduce of ones, MAX-reduce of a time.
+    RCCL when every rank has a device of its own, else gloo on the host (e.g. two ranks on a one-GPU machine)."""
     import torch.distributed as dist
-    on_gpu = torch.cuda.is_available()
+    on_gpu = torch.cuda.is_available() and torch.cuda.device_count() >= world
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29511")
     dev = torch.device("cuda", local) if on_gpu else torch.device("cpu")
@@ -498,6 +515,34 @@ def dist_selftest(world, rank, local):
                                                device_count=torch.cuda.device_count()))), flush=True)
     dist.barrier()
     dist.destroy_process_group()
+
+
+DUMP_CAP = 1 << 20                      # elements per dumped array; larger tensors are written as a seeded sample of this many
+DUMP_BUDGET = 64 * 2 ** 20              # bytes of all dumped arrays together
+
+
+def dump_outputs(res, dirname):
+    """--dump-outputs: every tensor of the step's output dict as `dirname/<name>.npy`, float32 (float64 for float64 and integer
+    tensors, which it holds exactly); above DUMP_CAP elements, the elements at DUMP_CAP flat indices drawn without replacement by a
+    generator seeded with 0 (ascending order).  Returns the names written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    written, total = [], 0
+    for name, t in res.items():
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        t = t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_BUDGET >> 20} MB at {name!r}")
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        written.append(name)
+    return written
 
 
 def main():
@@ -566,24 +611,30 @@ def main():
         step()
     eng = net._engine
     lib, h = eng.ctx.lib, eng.ctx.handle
-    _lib.check(lib.nm_prof_enable(h, 3), "prof_enable")      # conv launches of >= 20 GFLOP on the ctx stream, bracketed by HIP events
+    full = args.full
+    if full:
+        _lib.check(lib.nm_prof_enable(h, 3), "prof_enable")      # conv launches of >= 20 GFLOP on the ctx stream, bracketed by HIP events
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    res = step()                          # the last step's outputs (--dump-outputs); earlier ones are dropped as they were
     barrier()
     dt = time.perf_counter() - t0
-    _lib.check(lib.nm_prof_enable(h, 0), "prof_enable")
+    if full:
+        _lib.check(lib.nm_prof_enable(h, 0), "prof_enable")
     cdev = torch.device("cpu") if one_gpu else dev      # where the collectives' scalars live
     if dist_on:
         tt = torch.tensor([dt], device=cdev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    fam_main = prof_families(lib, h, _lib) if rank == 0 else {}        # timed region, launches on the ctx stream (clean durations)
+    dumped = dump_outputs(res, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
+    del res
+    fam_main = prof_families(lib, h, _lib) if (full and rank == 0) else {}        # timed region, launches on the ctx stream (clean durations)
     # the same families including the launches the library puts on its side stream (clip-mean net / VRNN beside the frame stack):
     # three more steps after the timed region, every conv launch on either stream bracketed by events (durations include contention)
     fam_all = {}
-    if rank == 0:
+    if full and rank == 0:
         _lib.check(lib.nm_prof_enable(h, 2), "prof_enable")
         for _ in range(3):
             step()
@@ -599,7 +650,7 @@ def main():
         ranks_seen = int(seen.item())
 
     extra = {}
-    if args.workload == "forward" and not args.no_extras:
+    if full and args.workload == "forward" and not args.no_extras:
         extra = extra_measurements(net, vox, eps, acts, dev, barrier, dist_on, world)
 
     if rank == 0:
@@ -646,13 +697,14 @@ def main():
                 roof["frac_of_split_ceiling"] = ach / (peak / 3.0)
                 roof["algorithmic_vs_fp32_mfma_peak"] = ach / FP32_MFMA_PEAK_TFLOPS
         cpu, parity = (None, {})
-        if world == 1 and not args.no_cpu_baseline and args.workload == "forward":
+        if full and world == 1 and not args.no_cpu_baseline and args.workload == "forward":
             cpu, parity = cpu_baseline(sd, opts, net, dev)
         line = dict(
             metric="voxel-frames/sec (64^3, T=16)", value=frames / dt, unit="voxel-frames/s",
             n_gpus=1 if one_gpu else world,
             **(dict(diagnostic=f"{world} processes (one nm_ctx each) sharing device 0: aggregate of all of them; NOT a scaling figure", ranks_on_one_gpu=world) if one_gpu else {}), steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
-            higher_is_better=True, scaling="weak", vs_baseline=None,
+            higher_is_better=True, scaling="weak", vs_baseline=None, full=full,
+            **(dict(dumped_outputs=dict(dir=args.dump_outputs, names=dumped, sample_cap=DUMP_CAP)) if dumped is not None else {}),
             dtype=("f32 (conv products as 3x f16-split MFMA with f32 accumulate, fp32-equivalent; everything else f32)"
                    if eng.conv_mode == 1 else ("f16 conv products (operands rounded to fp16, 1 MFMA per product), f32 accumulation and storage"
                                                if eng.conv_mode == 3 else ("bf16 storage of the training path (activations / activation gradients >= 32^3 voxels per frame), "

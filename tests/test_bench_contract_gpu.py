@@ -23,7 +23,7 @@ def _run(*args):
 
 
 def test_forward_line():
-    d = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline")
+    d = _run("--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline")
     assert d["metric"].startswith("voxel-frames/sec") and d["unit"] == "voxel-frames/s"
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
     assert d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None and d["data"] == "synthetic"
@@ -69,3 +69,28 @@ def test_four_processes_sharing_one_gpu_keep_the_aggregate_throughput():
     assert four["ranks_on_one_gpu"] == 4 and four["distributed"]["ranks_seen_by_allreduce"] == 4 and four["distributed"]["backend"] == "gloo"
     print("one process %.0f voxel-frames/s, four processes on the same GPU %.0f in aggregate (x%.2f)" % (one["value"], four["value"], four["value"] / one["value"]))
     assert four["value"] >= 0.9 * one["value"], (one["value"], four["value"])
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the headline only: the line keeps metric / value / unit / higher_is_better / dtype / ms_per_step
+    and carries no roofline or CPU baseline.  --dump-outputs writes the last timed step's outputs as <name>.npy, float32 / float64,
+    at most 64 MB in all, the large ones as a sample of bench.DUMP_CAP elements."""
+    import numpy as np
+    out = tmp_path / "dump"
+    d = _run("--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+    assert d["metric"].startswith("voxel-frames/sec") and d["unit"] == "voxel-frames/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["dtype"].startswith("f32 (conv products as 3x f16-split MFMA")
+    assert d["value"] > 0 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    names = d["dumped_outputs"]["names"]
+    cap = d["dumped_outputs"]["sample_cap"]
+    assert {"keypoints", "recon", "z_kypts", "h_kypts", "affinity", "recon_loss"} <= set(names)
+    total = 0
+    for nm in names:
+        a = np.load(out / f"{nm}.npy")
+        assert a.dtype in (np.float32, np.float64), (nm, a.dtype)
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    kp = np.load(out / "keypoints.npy")
+    assert kp.shape == (4, 16, 24, 4) and np.isfinite(kp).all()
+    assert np.load(out / "recon.npy").shape == (cap,)             # 4 x 16 x 64^3 voxels: a seeded sample

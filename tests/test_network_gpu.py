@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 from neural_marionette_amd import NeuralMarionette, HotPathOptions, synth
 from neural_marionette_amd.spec import DETECTOR_LOSS_KEYS
 from oracle import nm_oracle as O
@@ -57,7 +59,7 @@ def _err(a, b):
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return golden_npz.load(os.path.join(golden_dir, name))        # (the full-size fixtures are stored in parts)
 
 
 def _traj_conditioning(kp_ref, e_kp):

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_npz
+
 from neural_marionette_amd import synth
 from neural_marionette_amd.spec import HotPathOptions, DETECTOR_LOSS_KEYS
 from oracle import nm_oracle as O
@@ -16,7 +18,7 @@ TOL = 2e-5
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return golden_npz.load(os.path.join(golden_dir, name))        # (the full-size fixtures are stored in parts)
 
 
 def _close(a, b, tol=TOL, what=""):

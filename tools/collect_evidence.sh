@@ -86,7 +86,7 @@ python3 tools/time_encode_ab.py 2>&1 | grep -v amdgpu.ids > $E/${R}_encode_ab.tx
 rm -rf $E/fwd $E/train $E/trainb $E/c4 $E/c5 $E/tf $E/tw $E/pm $E/pmb
 # the default bench line last: its roofline.traffic reads this run's PMC summary and calibration (profiles/ on the box is a scratch copy)
 mkdir -p profiles; cp $E/${R}_pmc_traffic.json $E/${R}_fetch_calib.json profiles/
-python bench.py --steps 20 --warmup 5 > $E/bench_default.log 2> $E/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $E/bench_default.log 2> $E/bench_default.err
 tail -1 $E/bench_default.log > $E/${R}_bench.json.log
 # stamp the tree id into every summary
 python3 tools/tree_id.py --stamp "$TREE" $E/${R}_*.json $E/${R}_*.csv $E/${R}_*.txt $E/${R}_bench.json.log
