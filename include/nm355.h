@@ -156,6 +156,25 @@ int nm_ctx_set_gaussian_cat(nm_ctx* ctx, int32_t cat);
  * decode_from_dyna does), and the backward writes that parameter's gradient.  Call before nm_ctx_set_weights.  Not implemented together
  * with vol_fit_type 'gaussian' (NM_ERR_UNSUPPORTED). */
 int nm_ctx_set_learnable_sigma(nm_ctx* ctx, int32_t on);
+/* options.graph_loss_ver, keypoints_detach, using_local_const, using_time_const, using_sparsity_const and keypoints_graph
+ * (model/kypt_detector.py:20-30,54-68,112-143; utils/kypt_detector_utils.py:172-265).  ver: 1 (default) or 0 / 2 - the local, time and
+ * trajectory terms weighted by the keypoint intensity of the first index (ver 2 also symmetrises the influence, M + M^T); the intensity
+ * then receives a gradient.  flags: 0 = every term as the reference's defaults compute it, else an OR of
+ *   NM_GRAPH_LOCAL_OFF     local_const_loss is 0 and sends no gradient     (using_local_const = 0)
+ *   NM_GRAPH_TIME_OFF      time_const_loss is 0 and sends no gradient      (using_time_const = 0)
+ *   NM_GRAPH_SPARSITY_OFF  sparsity_const_loss is 0 and sends no gradient  (using_sparsity_const = 0)
+ *   NM_GRAPH_DETACH        the local, time and trajectory terms see the keypoints detached: their gradient reaches the affinity
+ *                          parameters only                                (keypoints_detach = 1)
+ *   NM_GRAPH_NONE          keypoints_graph 'none': no kypt_detector.affinity_params in the weights, every detector call runs with
+ *                          affinity_on = 0 whatever the caller passes, nm_get_affinity fails, the backward writes no affinity gradient.
+ * Call before nm_ctx_set_weights (a change of NM_GRAPH_NONE invalidates loaded weights: the table loses / gains a tensor).  Other
+ * versions or bits are NM_ERR_UNSUPPORTED. */
+#define NM_GRAPH_LOCAL_OFF    1
+#define NM_GRAPH_TIME_OFF     2
+#define NM_GRAPH_SPARSITY_OFF 4
+#define NM_GRAPH_DETACH       8
+#define NM_GRAPH_NONE         16
+int nm_ctx_set_graph_loss(nm_ctx* ctx, int32_t ver, int32_t flags);
 
 /* Input path on the device: episodic_normalization (zero translation) + voxelize of
  * utils/dataset_utils.py:9-31, evaluated operation by operation in fp64 so that the voxel indices

@@ -116,7 +116,13 @@ struct nm_ctx {
     int learn_sigma = 0;                   // options.fixed_sigma == 0 (kypt_detector.py:258-260): nm_ctx_set_learnable_sigma
     int gauss_cat = 0;                     // options.gaussian_cat_type (kypt_detector.py:396-401): 0 'none', 1 'max', 2 'sum' (nm_ctx_set_gaussian_cat)
     int affinity_ver = 3;                  // get_affinity version (kypt_detector.py:171-210): 3 = the shipped configurations; 0 / 1 / 2 by nm_ctx_set_affinity_ver
-    int64_t affinity_numel() const { return (int64_t)cfg.nneighbor * cfg.nkeypoints * (affinity_ver == 3 ? cfg.nkeypoints - 1 : cfg.nkeypoints); }
+    int graph_loss_ver = 1;                // options.graph_loss_ver (kypt_detector_utils.py:172-265): 1 = the shipped configurations; 0 / 2 by nm_ctx_set_graph_loss
+    int graph_flags = 0;                   // NM_GRAPH_* switches of include/nm355.h (0: every graph term on, keypoints attached, 'affinity_params')
+    bool graph_none() const { return (graph_flags & NM_GRAPH_NONE) != 0; }
+    int64_t affinity_numel() const {
+        if (graph_none()) return 0;        // keypoints_graph 'none' (kypt_detector.py:54-68 skipped): no affinity_params
+        return (int64_t)cfg.nneighbor * cfg.nkeypoints * (affinity_ver == 3 ? cfg.nkeypoints - 1 : cfg.nkeypoints);
+    }
     Arena ws;                              // activations / scratch, reset per call
     Arena ws2;                             // scratch of work issued on stream2 (VRNN beside the decoder)
     std::vector<void*> owned;              // weight allocations

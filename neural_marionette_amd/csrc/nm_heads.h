@@ -20,12 +20,14 @@ int nm_tail_blocks(int G);
 int nm_launch_decoder_tail(const TensorRef& x, const float* w14, const float* first_frames, int ff_stride_frames, int T,
                            const float* target, const float* keypoints, int K, int G, float* recon, float* part,
                            hipStream_t s);
+// graph_ver: options.graph_loss_ver (0 / 1 / 2)
 int nm_launch_clip_loss(const float* keypoints, const float* affinity, int B, int T, int K, int N, float sep_sigma,
-                        float* out, hipStream_t s);
+                        float* out, hipStream_t s, int graph_ver = 1);
 int nm_launch_loss_finalize(const float* tail_part, int tail_blocks, int B, int T, int K, int N, int G,
                             const float* heat_mean, const float* clip_part, const float* affinity, int chamfer,
                             int use_traj, float* frame_sums /* scratch [B*T][3] */, float* losses, hipStream_t s,
-                            const float* vol_override = nullptr /* [B*T][2]: vol_fit_type 'gaussian' */);
+                            const float* vol_override = nullptr /* [B*T][2]: vol_fit_type 'gaussian' */,
+                            int graph_flags = 0 /* NM_GRAPH_* of include/nm355.h: switched-off terms are written as 0 */);
 // vol_fit_type 'gaussian' (kypt_detector_utils.py:154-169): per frame (numerator, denominator) into vol [B*T][2]
 size_t nm_volfit_gauss_ws_floats(int F, int G);
 int nm_launch_volfit_gauss(const float* vox, const float* keypoints, int B, int T, int K, int G, float sigma, float* ws, float* vol, hipStream_t s);

@@ -13,6 +13,7 @@
 //   affinity_kernel     get_affinity ver 3                            (kypt_detector.py:191-199)
 #include "nm_common.h"
 #include "nm_heads.h"
+#include "../../include/nm355.h"      // NM_GRAPH_* switches
 
 namespace {
 
@@ -333,21 +334,33 @@ __global__ __launch_bounds__(256) void decoder_tail_kernel(TensorRef x, const fl
 
 // one block per clip b: partial sums of the keypoint-only losses
 //   out[b][0] separation_b   [1] sum_t local   [2] sum_t time   [3] sum vel term   [4] sum acc term
+// gver (options.graph_loss_ver, kypt_detector_utils.py:172-265): 1 = plain influence; 0 / 2 = the local, time and trajectory terms of pair
+// (k, l) weighted by the intensity of k (I[t][k] = keypoints[..., 3]; velocity terms by (I_t + I_t+1) / 2, acceleration terms by the mean of
+// two consecutive velocity weights); 2 also symmetrises the influence, M + M^T.
 __global__ __launch_bounds__(256) void clip_loss_kernel(const float* __restrict__ keypoints, const float* __restrict__ affinity,
-                                                        int T, int K, int N, float sep_sigma, float* __restrict__ out) {
+                                                        int T, int K, int N, float sep_sigma, int gver, float* __restrict__ out) {
     __shared__ float sh[256];
     extern __shared__ float dyn[];
     float* pos = dyn;                      // [T][K][3]
     float* mean = dyn + T * K * 3;         // [K][3]
     float* infl = mean + K * 3;            // [K][K]
+    float* inten = infl + K * K;           // [T][K]   (gver 0 / 2 only)
     const int b = blockIdx.x;
+    const bool wi = gver != 1;
     for (int i = threadIdx.x; i < T * K * 3; i += 256) {
         int d = i % 3, tk = i / 3;
         pos[i] = keypoints[((size_t)b * T * K + tk) * 4 + d];
     }
+    if (wi) for (int i = threadIdx.x; i < T * K; i += 256) inten[i] = keypoints[((size_t)b * T * K + i) * 4 + 3];
     if (affinity) for (int i = threadIdx.x; i < K * K; i += 256) {
         float m = -INFINITY;
         for (int n = 0; n < N; ++n) m = fmaxf(m, affinity[(size_t)n * K * K + i]);
+        if (gver == 2) {
+            const int it = (i % K) * K + i / K;
+            float mt = -INFINITY;
+            for (int n = 0; n < N; ++n) mt = fmaxf(mt, affinity[(size_t)n * K * K + it]);
+            m = m + mt;
+        }
         infl[i] = m;
     }
     __syncthreads();
@@ -384,8 +397,13 @@ __global__ __launch_bounds__(256) void clip_loss_kernel(const float* __restrict_
                 float sd = 0.f;
 #pragma unroll
                 for (int d = 0; d < 3; ++d) { float w = pos[(t * K + k) * 3 + d] - pos[(t * K + l) * 3 + d]; sd += w * w; }
-                tl += sd * in;
-                tt += fabsf(sd - dmean) * in;
+                if (wi) {
+                    tl += sd * in * inten[t * K + k];
+                    tt += fabsf(sd - dmean) * in * inten[t * K + k];
+                } else {
+                    tl += sd * in;
+                    tt += fabsf(sd - dmean) * in;
+                }
             }
             loc += tl; tim += tt;
             // trajectory: cosine of velocities / accelerations of k and l (eps 1e-6 on each norm)
@@ -401,7 +419,8 @@ __global__ __launch_bounds__(256) void clip_loss_kernel(const float* __restrict_
                 float cs = 0.f;
 #pragma unroll
                 for (int d = 0; d < 3; ++d) cs += (vk[d] / nk) * (vl[d] / nl);
-                vel += ((-cs + 1.0f) / 2.0f) * in;
+                if (wi) vel += ((-cs + 1.0f) / 2.0f) * in * ((inten[t * K + k] + inten[(t + 1) * K + k]) / 2.0f);
+                else vel += ((-cs + 1.0f) / 2.0f) * in;
                 if (t + 2 < T) {
                     float ak[3], al[3], mk = 0.f, ml = 0.f;
 #pragma unroll
@@ -415,7 +434,11 @@ __global__ __launch_bounds__(256) void clip_loss_kernel(const float* __restrict_
                     float ca = 0.f;
 #pragma unroll
                     for (int d = 0; d < 3; ++d) ca += (ak[d] / mk) * (al[d] / ml);
-                    acc += ((-ca + 1.0f) / 2.0f) * in;
+                    if (wi) {
+                        const float iv0 = (inten[t * K + k] + inten[(t + 1) * K + k]) / 2.0f;
+                        const float iv1 = (inten[(t + 1) * K + k] + inten[(t + 2) * K + k]) / 2.0f;
+                        acc += ((-ca + 1.0f) / 2.0f) * in * ((iv1 + iv0) / 2.0f);
+                    } else acc += ((-ca + 1.0f) / 2.0f) * in;
                 }
             }
         }
@@ -496,7 +519,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
                                                             int K, int N, int G, const float* __restrict__ heat_mean,
                                                             const float* __restrict__ clip_part, const float* __restrict__ affinity,
                                                             int chamfer, int use_traj, const float* __restrict__ vol_override,
-                                                            float* __restrict__ losses) {
+                                                            int gflags, float* __restrict__ losses) {
     __shared__ float sh[256];
     const int F = B * T;
     const float G3 = (float)G * (float)G * (float)G;
@@ -518,7 +541,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
     sep = block_sum256(sep, sh); loc = block_sum256(loc, sh); tim = block_sum256(tim, sh);
     vel = block_sum256(vel, sh); acc = block_sum256(acc, sh);
     float spc = 0.f;
-    if (affinity) {
+    if (affinity && !(gflags & NM_GRAPH_SPARSITY_OFF)) {
         for (int i = threadIdx.x; i < K * K; i += 256) {
             float s = 0.f;
             for (int n = 0; n < N; ++n)
@@ -535,9 +558,10 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
         losses[2] = 0.f;
         losses[3] = sep / (float)B;
         losses[4] = sp / (float)F;
-        losses[5] = affinity ? loc / KK / (float)F : 0.f;
-        losses[6] = affinity ? tim / KK / (float)F : 0.f;
-        losses[7] = affinity ? spc / KK : 0.f;
+        // (a switched-off term is the reference's zeros(1, 1): exactly 0, kypt_detector_utils.py:200,210,223)
+        losses[5] = (affinity && !(gflags & NM_GRAPH_LOCAL_OFF)) ? loc / KK / (float)F : 0.f;
+        losses[6] = (affinity && !(gflags & NM_GRAPH_TIME_OFF)) ? tim / KK / (float)F : 0.f;
+        losses[7] = (affinity && !(gflags & NM_GRAPH_SPARSITY_OFF)) ? spc / KK : 0.f;
         losses[8] = 0.f;
         losses[9] = (affinity && use_traj) ? (vel / (float)(B * (T - 1)) + acc / (float)(B * (T - 2))) / KK : 0.f;
         losses[10] = 0.f;
@@ -732,18 +756,20 @@ int nm_launch_decoder_tail(const TensorRef& x, const float* w14, const float* fi
 }
 
 int nm_launch_clip_loss(const float* keypoints, const float* affinity, int B, int T, int K, int N, float sep_sigma,
-                        float* out, hipStream_t s) {
-    size_t lds = ((size_t)T * K * 3 + K * 3 + K * K) * sizeof(float);
-    hipLaunchKernelGGL(clip_loss_kernel, dim3(B), dim3(256), lds, s, keypoints, affinity, T, K, N, sep_sigma, out);
+                        float* out, hipStream_t s, int graph_ver) {
+    if (graph_ver < 0 || graph_ver > 2) { nm_set_error("clip_loss: graph_loss_ver %d", graph_ver); return NM_ERR_ARG; }
+    size_t lds = ((size_t)T * K * 3 + K * 3 + K * K + (graph_ver != 1 ? (size_t)T * K : 0)) * sizeof(float);
+    if (lds > 64 * 1024) { nm_set_error("clip_loss: T*K too large (%d x %d)", T, K); return NM_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(clip_loss_kernel, dim3(B), dim3(256), lds, s, keypoints, affinity, T, K, N, sep_sigma, graph_ver, out);
     return nm_check_hip(hipGetLastError(), "clip_loss launch");
 }
 
 int nm_launch_loss_finalize(const float* tail_part, int tail_blocks, int B, int T, int K, int N, int G,
                             const float* heat_mean, const float* clip_part, const float* affinity, int chamfer,
-                            int use_traj, float* frame_sums, float* losses, hipStream_t s, const float* vol_override) {
+                            int use_traj, float* frame_sums, float* losses, hipStream_t s, const float* vol_override, int graph_flags) {
     hipLaunchKernelGGL(tail_sums_kernel, dim3(B * T), dim3(256), 0, s, tail_part, tail_blocks, frame_sums);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, frame_sums, B, T, K, N, G, heat_mean,
-                       clip_part, affinity, chamfer, use_traj, vol_override, losses);
+                       clip_part, affinity, chamfer, use_traj, vol_override, graph_flags, losses);
     return nm_check_hip(hipGetLastError(), "loss_finalize launch");
 }
 

@@ -4,6 +4,7 @@
 //   0 recon  1 vol_fit  2 kypt_const  3 separation  4 sparsity  5 local  6 time  7 sparsity_const  8 intensity  9 traj  10 graph_vol
 // All reductions are block-ordered sums into scratch followed by a fixed-order reduce: run-to-run identical.
 #include "nm_heads_bwd.h"
+#include "../../include/nm355.h"      // NM_GRAPH_* switches
 
 namespace {
 
@@ -443,11 +444,16 @@ __global__ __launch_bounds__(256) void sum_t_kernel(const float* __restrict__ in
 
 // ---- keypoint-only losses of one clip (kypt_detector_utils.py:105-133,172-265) ------------------------------------------------------
 // one block per clip.  dkp[b][t][k][0..2] += gradient;  dinfl[b][k][l] = d loss / d influence[k][l] contribution of this clip
+// gver (graph_loss_ver) 0 / 2: the local, time and trajectory terms carry the intensity weights of clip_loss_kernel (nm_heads.hip) and
+// dkp[b][t][k][3] receives their intensity gradient; 2: the influence is M + M^T (dinfl is d loss / d (M + M^T): affinity_bwd_kernel
+// symmetrises it).  gflags (NM_GRAPH_*): switched-off terms send nothing; NM_GRAPH_DETACH keeps dinfl but sends nothing from the local,
+// time and trajectory terms into the keypoints.
 __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restrict__ keypoints, const float* __restrict__ affinity,
                                                             const float* __restrict__ dloss, int B, int T, int K, int N, float sep_sigma,
-                                                            int use_traj, float* __restrict__ dkp, float* __restrict__ dinfl) {
+                                                            int use_traj, int gver, int gflags, float* __restrict__ dkp,
+                                                            float* __restrict__ dinfl) {
     extern __shared__ float dyn[];
-    const int TK3 = T * K * 3, KK = K * K;
+    const int TK3 = T * K * 3, KK = K * K, TK = T * K;
     float* pos = dyn;                 // [T][K][3]
     float* gp = pos + TK3;            // [T][K][3]
     float* gv = gp + TK3;             // [T][K][3]   velocity gradients (t < T-1)
@@ -456,17 +462,36 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
     float* infl = mean + K * 3;       // [K][K]
     float* ekl = infl + KK;           // [K][K]  exp(-D_kl / s)
     float* dm = ekl + KK;             // [K][K]  mean_t d_tkl
-    float* sbar = dm + KK;            // [K][K]  mean_t sign(d_tkl - dm_kl)
+    float* sbar = dm + KK;            // [K][K]  mean_t sign(d_tkl - dm_kl)   (gver 0 / 2: mean_t sign(d_tkl - dm_kl) I_tk)
+    float* inten = sbar + KK;         // [T][K]  gver 0 / 2 only: I_tk, then d/dI of the local + time terms, sum_l cos-term * infl per step
+    float* gil = inten + TK;          // [T][K]
+    float* vsum = gil + TK;           // [T][K]  sum_l vel_cos_tkl infl_kl   (t < T-1)
+    float* asum = vsum + TK;          // [T][K]  sum_l acc_cos_tkl infl_kl   (t < T-2)
     const int b = blockIdx.x;
-    const float g_sep = dloss[3], g_loc = affinity ? dloss[5] : 0.f, g_time = affinity ? dloss[6] : 0.f;
+    const bool wi = gver != 1;
+    const bool attached = !(gflags & NM_GRAPH_DETACH);
+    const float g_sep = dloss[3];
+    const float g_loc = (affinity && !(gflags & NM_GRAPH_LOCAL_OFF)) ? dloss[5] : 0.f;
+    const float g_time = (affinity && !(gflags & NM_GRAPH_TIME_OFF)) ? dloss[6] : 0.f;
     const float g_traj = (affinity && use_traj) ? dloss[9] : 0.f;
     for (int i = threadIdx.x; i < TK3; i += 256) {
         pos[i] = keypoints[((size_t)b * T * K + i / 3) * 4 + i % 3];
         gp[i] = 0.f; gv[i] = 0.f; ga[i] = 0.f;
     }
+    if (wi) for (int i = threadIdx.x; i < TK; i += 256) {
+        inten[i] = keypoints[((size_t)b * T * K + i) * 4 + 3];
+        gil[i] = 0.f; vsum[i] = 0.f; asum[i] = 0.f;
+    }
     for (int i = threadIdx.x; i < KK; i += 256) {
         float m = 0.f;
-        if (affinity) { m = -INFINITY; for (int n = 0; n < N; ++n) m = fmaxf(m, affinity[(size_t)n * KK + i]); }
+        if (affinity) {
+            m = -INFINITY; for (int n = 0; n < N; ++n) m = fmaxf(m, affinity[(size_t)n * KK + i]);
+            if (gver == 2) {
+                const int it = (i % K) * K + i / K;
+                float mt = -INFINITY; for (int n = 0; n < N; ++n) mt = fmaxf(mt, affinity[(size_t)n * KK + it]);
+                m = m + mt;
+            }
+        }
         infl[i] = m;
     }
     __syncthreads();
@@ -499,12 +524,20 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
         const float dmean = dsum / (float)T;
         dm[pr] = dmean;
         float ss = 0.f, tabs = 0.f, velc = 0.f, accc = 0.f;
+        if (wi) dsum = 0.f;               // (gver 0 / 2: intensity-weighted sums of d and |d - mean_t d|)
         for (int t = 0; t < T; ++t) {
             float sd = 0.f;
             for (int d = 0; d < 3; ++d) { const float w = pos[(t * K + k) * 3 + d] - pos[(t * K + l) * 3 + d]; sd += w * w; }
             const float df = sd - dmean;
-            ss += df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
-            tabs += fabsf(df);
+            if (wi) {
+                const float it = inten[t * K + k];
+                ss += (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * it;
+                tabs += fabsf(df) * it;
+                dsum += sd * it;
+            } else {
+                ss += df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
+                tabs += fabsf(df);
+            }
         }
         sbar[pr] = ss / (float)T;
         if (g_traj != 0.f) {
@@ -518,7 +551,8 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                 nk = fmaxf(sqrtf(nk), 1e-6f); nl = fmaxf(sqrtf(nl), 1e-6f);
                 float cs = 0.f;
                 for (int d = 0; d < 3; ++d) cs += (vk[d] / nk) * (vl[d] / nl);
-                velc += (-cs + 1.0f) / 2.0f;
+                if (wi) velc += ((-cs + 1.0f) / 2.0f) * ((inten[t * K + k] + inten[(t + 1) * K + k]) / 2.0f);
+                else velc += (-cs + 1.0f) / 2.0f;
                 if (t + 2 < T) {
                     float ak[3], al[3], mk = 0.f, ml = 0.f;
                     for (int d = 0; d < 3; ++d) {
@@ -530,7 +564,8 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                     mk = fmaxf(sqrtf(mk), 1e-6f); ml = fmaxf(sqrtf(ml), 1e-6f);
                     float ca = 0.f;
                     for (int d = 0; d < 3; ++d) ca += (ak[d] / mk) * (al[d] / ml);
-                    accc += (-ca + 1.0f) / 2.0f;
+                    if (wi) accc += ((-ca + 1.0f) / 2.0f) * ((inten[t * K + k] + 2.0f * inten[(t + 1) * K + k] + inten[(t + 2) * K + k]) / 4.0f);
+                    else accc += (-ca + 1.0f) / 2.0f;
                 }
             }
         }
@@ -551,14 +586,24 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
             // local + time: q_tkl + q_tlk with q = dL/dd_tkl
             const float dfk = sd - dm[k * K + l];
             const float sg = dfk > 0.f ? 1.f : (dfk < 0.f ? -1.f : 0.f);
-            const float q = (c_loc + c_time * (sg - sbar[k * K + l])) * infl[k * K + l] + (c_loc + c_time * (sg - sbar[l * K + k])) * infl[l * K + k];
+            float q;
+            if (wi) {
+                // d/dI_tk of the local + time terms; pair (k, l) weighs by I_tk, pair (l, k) by I_tl
+                gil[t * K + k] += (c_loc * sd + c_time * fabsf(dfk)) * infl[k * K + l];
+                const float itk = inten[t * K + k], itl = inten[t * K + l];
+                q = (c_loc * itk + c_time * (sg * itk - sbar[k * K + l])) * infl[k * K + l] +
+                    (c_loc * itl + c_time * (sg * itl - sbar[l * K + k])) * infl[l * K + k];
+            } else {
+                q = (c_loc + c_time * (sg - sbar[k * K + l])) * infl[k * K + l] + (c_loc + c_time * (sg - sbar[l * K + k])) * infl[l * K + k];
+            }
+            if (!attached) q = 0.f;
             for (int d = 0; d < 3; ++d) {
                 const float u = w[d] - (mean[k * 3 + d] - mean[l * 3 + d]);
                 gr[d] += cs * u + q * 2.0f * w[d];
             }
         }
         for (int d = 0; d < 3; ++d) gp[(t * K + k) * 3 + d] = gr[d];
-        if (g_traj != 0.f && t + 1 < T) {
+        if (g_traj != 0.f && attached && t + 1 < T) {
             float vk[3], nk2 = 0.f;
             for (int d = 0; d < 3; ++d) { vk[d] = pos[((t + 1) * K + k) * 3 + d] - pos[(t * K + k) * 3 + d]; nk2 += vk[d] * vk[d]; }
             const float nkr = sqrtf(nk2), nk = fmaxf(nkr, 1e-6f);
@@ -573,15 +618,20 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
             const float mkr = sqrtf(mk2), mk = fmaxf(mkr, 1e-6f);
             const bool clamp_a = mkr < 1e-6f;
             float gaa[3] = {0.f, 0.f, 0.f};
+            float vs = 0.f, as = 0.f;
             for (int l = 0; l < K; ++l) {
-                const float wi = infl[k * K + l] + infl[l * K + k];
+                // (gver 0 / 2: pair (k, l) weighs by k's step intensity, pair (l, k) by l's)
+                const float wv = wi ? infl[k * K + l] * ((inten[t * K + k] + inten[(t + 1) * K + k]) / 2.0f) +
+                                      infl[l * K + k] * ((inten[t * K + l] + inten[(t + 1) * K + l]) / 2.0f)
+                                    : infl[k * K + l] + infl[l * K + k];
                 float vl[3], nl = 0.f;
                 for (int d = 0; d < 3; ++d) { vl[d] = pos[((t + 1) * K + l) * 3 + d] - pos[(t * K + l) * 3 + d]; nl += vl[d] * vl[d]; }
                 nl = fmaxf(sqrtf(nl), 1e-6f);
                 float cs = 0.f;
                 for (int d = 0; d < 3; ++d) cs += (vk[d] / nk) * (vl[d] / nl);
+                if (wi) vs += ((-cs + 1.0f) / 2.0f) * infl[k * K + l];
                 // d cos / d v_k = (vhat_l - cos * vhat_k) / |v_k|   (norm clamped at eps: the clamp has no gradient)
-                const float ck = -0.5f * c_vel * wi;
+                const float ck = -0.5f * c_vel * wv;
                 for (int d = 0; d < 3; ++d) {
                     const float dc = clamp_k ? (vl[d] / nl) / nk : ((vl[d] / nl) - cs * (vk[d] / nk)) / nk;
                     gvv[d] += l == k ? 0.f : ck * dc;      // (the influence has a zero diagonal)
@@ -595,7 +645,11 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                     ml = fmaxf(sqrtf(ml), 1e-6f);
                     float ca = 0.f;
                     for (int d = 0; d < 3; ++d) ca += (ak[d] / mk) * (al[d] / ml);
-                    const float cka = -0.5f * c_acc * wi;
+                    const float wa = wi ? infl[k * K + l] * ((inten[t * K + k] + 2.0f * inten[(t + 1) * K + k] + inten[(t + 2) * K + k]) / 4.0f) +
+                                          infl[l * K + k] * ((inten[t * K + l] + 2.0f * inten[(t + 1) * K + l] + inten[(t + 2) * K + l]) / 4.0f)
+                                        : infl[k * K + l] + infl[l * K + k];
+                    if (wi) as += ((-ca + 1.0f) / 2.0f) * infl[k * K + l];
+                    const float cka = -0.5f * c_acc * wa;
                     for (int d = 0; d < 3; ++d) {
                         const float dc = clamp_a ? (al[d] / ml) / mk : ((al[d] / ml) - ca * (ak[d] / mk)) / mk;
                         gaa[d] += l == k ? 0.f : cka * dc;
@@ -603,9 +657,21 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                 }
             }
             for (int d = 0; d < 3; ++d) { gv[(t * K + k) * 3 + d] = gvv[d]; ga[(t * K + k) * 3 + d] = has_a ? gaa[d] : 0.f; }
+            if (wi) { vsum[t * K + k] = vs; asum[t * K + k] = has_a ? as : 0.f; }
         }
     }
     __syncthreads();
+    if (wi && attached) for (int i = threadIdx.x; i < TK; i += 256) {
+        // intensity gradient: local + time, then the velocity weights (I_t + I_t+1) / 2 and the acceleration weights (I_t + 2 I_t+1 + I_t+2) / 4
+        const int t = i / K;
+        float s = gil[i];
+        if (t + 1 < T) s += 0.5f * c_vel * vsum[i];
+        if (t >= 1) s += 0.5f * c_vel * vsum[i - K];
+        if (t + 2 < T) s += 0.25f * c_acc * asum[i];
+        if (t >= 1 && t + 1 < T) s += 0.5f * c_acc * asum[i - K];
+        if (t >= 2) s += 0.25f * c_acc * asum[i - 2 * K];
+        dkp[((size_t)b * T * K + i) * 4 + 3] += s;
+    }
     for (int i = threadIdx.x; i < TK3; i += 256) {
         const int t = i / (K * 3), r = i % (K * 3);
         float s = gp[i];
@@ -621,15 +687,18 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
 
 // single block: d affinity (through the influence = max over neighbours and the neighbour-sparsity loss) -> d affinity_params
 // (softmax over K-1 logits with the zero diagonal re-inserted, kypt_detector.py:191-199)
+// gver 2 (graph_loss_ver): dinfl is the gradient of the symmetrised influence M + M^T, so M receives dinfl + dinfl^T;
+// gflags & NM_GRAPH_SPARSITY_OFF: no sparsity-const term
 __global__ __launch_bounds__(256) void affinity_bwd_kernel(const float* __restrict__ params, const float* __restrict__ affinity,
                                                            const float* __restrict__ dinfl, const float* __restrict__ dloss, int B, int N,
-                                                           int K, int ver, float* __restrict__ dparams) {
+                                                           int K, int ver, int gver, int gflags, float* __restrict__ dparams) {
     extern __shared__ float dA[];       // [N][K][K]
     const int KK = K * K;
-    const float g_spc = dloss[7];
+    const float g_spc = (gflags & NM_GRAPH_SPARSITY_OFF) ? 0.f : dloss[7];
     for (int i = threadIdx.x; i < KK; i += 256) {
         float di = 0.f;
         for (int b = 0; b < B; ++b) di += dinfl[(size_t)b * KK + i];
+        if (gver == 2) { const int it = (i % K) * K + i / K; for (int b = 0; b < B; ++b) di += dinfl[(size_t)b * KK + it]; }
         int am = 0; float mx = -INFINITY;
         for (int n = 0; n < N; ++n) { const float a = affinity[(size_t)n * KK + i]; if (a > mx) { mx = a; am = n; } }
         for (int n = 0; n < N; ++n) {
@@ -781,8 +850,9 @@ int nm_launch_heat_bwd(const float* head, const float* clip_head, const float* p
 size_t nm_heat_bwd_ws_floats(int F, int K, int g) { return (size_t)F * K * 4 + (size_t)F * g * 3 + 64; }
 
 int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const float* dloss, int B, int T, int K, int N, float sep_sigma,
-                            int use_traj, float* dkp, float* dinfl, hipStream_t s) {
-    const size_t lds = ((size_t)4 * T * K * 3 + K * 3 + 4 * K * K) * sizeof(float);
+                            int use_traj, float* dkp, float* dinfl, hipStream_t s, int graph_ver, int graph_flags) {
+    if (graph_ver < 0 || graph_ver > 2) { nm_set_error("clip_loss_bwd: graph_loss_ver %d", graph_ver); return NM_ERR_ARG; }
+    const size_t lds = ((size_t)4 * T * K * 3 + K * 3 + 4 * K * K + (graph_ver != 1 ? (size_t)4 * T * K : 0)) * sizeof(float);
     if (lds > 150 * 1024) { nm_set_error("clip_loss_bwd: T*K too large (%d x %d)", T, K); return NM_ERR_UNSUPPORTED; }
     static NmDeviceOnce attr_set;
     if (!attr_set.done()) {
@@ -791,14 +861,14 @@ int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const
         }
         attr_set.mark();
     }
-    hipLaunchKernelGGL(clip_loss_bwd_kernel, dim3(B), dim3(256), lds, s, keypoints, affinity, dloss, B, T, K, N, sep_sigma, use_traj, dkp,
-                       affinity ? dinfl : nullptr);
+    hipLaunchKernelGGL(clip_loss_bwd_kernel, dim3(B), dim3(256), lds, s, keypoints, affinity, dloss, B, T, K, N, sep_sigma, use_traj,
+                       graph_ver, graph_flags, dkp, affinity ? dinfl : nullptr);
     return nm_check_hip(hipGetLastError(), "clip_loss_bwd launch");
 }
 
 int nm_launch_affinity_bwd(const float* params, const float* affinity, const float* dinfl, const float* dloss, int B, int N, int K,
-                           float* dparams, hipStream_t s, int ver) {
+                           float* dparams, hipStream_t s, int ver, int graph_ver, int graph_flags) {
     hipLaunchKernelGGL(affinity_bwd_kernel, dim3(1), dim3(256), (size_t)N * K * K * sizeof(float), s, params, affinity, dinfl, dloss, B, N, K,
-                       ver, dparams);
+                       ver, graph_ver, graph_flags, dparams);
     return nm_check_hip(hipGetLastError(), "affinity_bwd launch");
 }

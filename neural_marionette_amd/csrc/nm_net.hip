@@ -622,6 +622,7 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
     Net n(c);
     n.keep = tape != nullptr;
     const DetectorW& d = c->det;
+    if (c->graph_none()) affinity_on = 0;       // keypoints_graph 'none': no affinity, every graph term is zero (kypt_detector.py:114-119)
     const int K = c->cfg.nkeypoints, G = c->cfg.grid_size, g = G / 4, F = B * T, N = c->cfg.nneighbor;
     const size_t g3 = (size_t)g * g * g, G3 = (size_t)G * G * G;
     const int Kc = d.head.Cout;                 // head / clip_head channels per voxel: K rounded up to 8 (padded channels are zeros)
@@ -719,10 +720,10 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
     float* vol_fs = nullptr; float* vol_ws = nullptr;               // vol_fit_type 'gaussian' (cfg.vol_fit_chamfer == 2): its own per-frame sums
     if (recon && losses && c->cfg.vol_fit_chamfer == 2) { vol_fs = n.alloc((size_t)F * 2); vol_ws = n.alloc(nm_volfit_gauss_ws_floats(F, G)); }
     if (n.live() && recon && losses) {
-        n.run(nm_launch_clip_loss(keypoints, aff, B, T, K, N, c->cfg.sep_sigma, clip_part, n.s));
+        n.run(nm_launch_clip_loss(keypoints, aff, B, T, K, N, c->cfg.sep_sigma, clip_part, n.s, c->graph_loss_ver));
         if (vol_fs) n.run(nm_launch_volfit_gauss(vox_in, keypoints, B, T, K, G, c->cfg.gaussian_sigma, vol_ws, vol_fs, n.s));
         n.run(nm_launch_loss_finalize(tail_part, tb, B, T, K, N, G, heat_mean, clip_part, aff, c->cfg.vol_fit_chamfer,
-                                      c->cfg.use_graph_traj, frame_sums, losses, n.s, vol_fs));
+                                      c->cfg.use_graph_traj, frame_sums, losses, n.s, vol_fs, c->graph_flags));
     }
     return n.rc;
 }
@@ -1166,16 +1167,17 @@ int backward_graph(nm_ctx* c, const TrainTape& t, const float* dloss, const std:
         const size_t m = b.ws.mark();
         float* cws = b.alloc((size_t)F * nm_chamfer_bwd_blocks(G) * K * 3);
         float* gvws = c->cfg.vol_fit_chamfer == 2 ? b.alloc(nm_volfit_gauss_bwd_ws_floats(B, T, G)) : nullptr;
-        float* gaff = b.grad("kypt_detector.affinity_params", c->affinity_numel());
+        float* gaff = c->graph_none() ? nullptr : b.grad("kypt_detector.affinity_params", c->affinity_numel());
         if (b.live()) {
             if (c->cfg.vol_fit_chamfer == 1)
                 b.run(nm_launch_chamfer_bwd(t.vox, t.keypoints, t.tail_part, nm_tail_blocks(G), dloss, F, K, G, cws, dkp, b.s));
             else if (c->cfg.vol_fit_chamfer == 2)
                 b.run(nm_launch_volfit_gauss_bwd(t.vox, t.keypoints, dloss, B, T, K, G, c->cfg.gaussian_sigma, gvws, dkp, b.s));
             b.run(nm_launch_clip_loss_bwd(t.keypoints, t.affinity_on ? t.aff : nullptr, dloss, B, T, K, N, c->cfg.sep_sigma, c->cfg.use_graph_traj,
-                                          dkp, dinfl, b.s));
-            if (t.affinity_on) b.run(nm_launch_affinity_bwd(d.affinity_params, t.aff, dinfl, dloss, B, N, K, gaff, b.s, c->affinity_ver));
-            else b.run(nm_check_hip(hipMemsetAsync(gaff, 0, (size_t)c->affinity_numel() * sizeof(float), b.s), "backward: memset"));
+                                          dkp, dinfl, b.s, c->graph_loss_ver, c->graph_flags));
+            if (t.affinity_on) b.run(nm_launch_affinity_bwd(d.affinity_params, t.aff, dinfl, dloss, B, N, K, gaff, b.s, c->affinity_ver,
+                                                            c->graph_loss_ver, c->graph_flags));
+            else if (gaff) b.run(nm_check_hip(hipMemsetAsync(gaff, 0, (size_t)c->affinity_numel() * sizeof(float), b.s), "backward: memset"));
         }
         b.ws.release(m);
     }
@@ -1336,7 +1338,7 @@ int nm_net_set_weights(nm_ctx* c, const std::map<std::string, std::pair<const fl
     DetectorW& d = c->det;
     const std::string v = "kypt_detector.vox_to_kypt", k2v = "kypt_detector.kypt_to_vox";
     const std::string dec = k2v + ".decode_voxel_from_combined_representation";
-    d.affinity_params = L.copy("kypt_detector.affinity_params", c->affinity_numel());
+    d.affinity_params = c->graph_none() ? nullptr : L.copy("kypt_detector.affinity_params", c->affinity_numel());
     d.sigma_param = c->learn_sigma ? L.copy("kypt_detector.vox_to_kypt.sigmas", K) : nullptr;
     d.zeros = nm_ctx_weight_alloc(c, 512);
     if (d.zeros) (void)hipMemsetAsync(d.zeros, 0, 512 * sizeof(float), c->stream);
@@ -1588,6 +1590,7 @@ int nm_get_affinity(nm_ctx* c, float* affinity) try { NmScope nm_scope_(c);
     int rc = check_ready(c, "get_affinity");
     if (rc) return rc;
     if (!affinity) { nm_set_error("get_affinity: null output"); return NM_ERR_ARG; }
+    if (c->graph_none()) { nm_set_error("get_affinity: keypoints_graph 'none' has no affinity"); return NM_ERR_STATE; }
     return nm_launch_affinity(c->det.affinity_params, c->cfg.nneighbor, c->cfg.nkeypoints, affinity, c->stream, c->affinity_ver);
 } catch (...) { return nm_abi_catch("nm_get_affinity"); }
 
@@ -1611,5 +1614,16 @@ int nm_ctx_set_affinity_ver(nm_ctx* c, int32_t ver) try { NmScope nm_scope_(c);
     if (ver != c->affinity_ver) { c->affinity_ver = ver; c->has_weights = false; }      // the parameter's shape changes: weights must be set again
     return NM_OK;
 } catch (...) { return nm_abi_catch("nm_ctx_set_affinity_ver"); }
+
+int nm_ctx_set_graph_loss(nm_ctx* c, int32_t ver, int32_t flags) try { NmScope nm_scope_(c);
+    if (!c) { nm_set_error("ctx_set_graph_loss: null context"); return NM_ERR_ARG; }
+    if (ver < 0 || ver > 2) { nm_set_error("ctx_set_graph_loss: graph_loss_ver %d (0, 1 or 2)", ver); return NM_ERR_UNSUPPORTED; }
+    const int32_t known = NM_GRAPH_LOCAL_OFF | NM_GRAPH_TIME_OFF | NM_GRAPH_SPARSITY_OFF | NM_GRAPH_DETACH | NM_GRAPH_NONE;
+    if (flags & ~known) { nm_set_error("ctx_set_graph_loss: unknown flag bits 0x%x", (unsigned)(flags & ~known)); return NM_ERR_UNSUPPORTED; }
+    if ((flags & NM_GRAPH_NONE) != (c->graph_flags & NM_GRAPH_NONE)) c->has_weights = false;     // the weight table loses / gains affinity_params
+    c->graph_loss_ver = ver;
+    c->graph_flags = flags;
+    return NM_OK;
+} catch (...) { return nm_abi_catch("nm_ctx_set_graph_loss"); }
 
 }  // extern "C"

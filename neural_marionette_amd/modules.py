@@ -98,6 +98,9 @@ class Engine:
                 _lib.check(self.ctx.lib.nm_ctx_set_gaussian_cat(self.ctx.handle, {"max": 1, "sum": 2}[o.gaussian_cat_type]), "set_gaussian_cat")
             if o.affinity_ver != 3:                        # (N, K, K) affinity parameters: before the first nm_ctx_set_weights
                 _lib.check(self.ctx.lib.nm_ctx_set_affinity_ver(self.ctx.handle, int(o.affinity_ver)), "set_affinity_ver")
+            flags = o.graph_loss_flags()
+            if o.graph_loss_ver != 1 or flags:             # kypt_detector.py:112-143 ('none': before the first nm_ctx_set_weights)
+                _lib.check(self.ctx.lib.nm_ctx_set_graph_loss(self.ctx.handle, int(o.graph_loss_ver), flags), "set_graph_loss")
             self._stamp = None
             self._named = None
         _lib.check(self.ctx.lib.nm_ctx_set_training(self.ctx.handle, int(self.training_packs)), "set_training")
@@ -259,7 +262,9 @@ class KyptDetector(nn.Module):
         self.kypt_to_vox = holders.KyptToVoxNet(grid_size=o.grid_size, nkeypoints=o.nkeypoints, input_dim=o.input_dim,
                                                 gaussian_cat_type=o.gaussian_cat_type)
         K, N = o.nkeypoints, o.nneighbor
-        if o.affinity_ver < 3:                                 # kypt_detector.py:57-58,65-66
+        if o.keypoints_graph == "none":                        # kypt_detector.py:54: no affinity parameters, no draws from the RNG
+            pass
+        elif o.affinity_ver < 3:                               # kypt_detector.py:57-58,65-66
             self.affinity_params = nn.Parameter(torch.randn(N, K, K) if o.graph_random_init else torch.zeros(N, K, K))
         else:
             self.affinity_params = nn.Parameter(torch.randn(N, K, K - 1) if o.graph_random_init else torch.ones(N, K, K - 1))
@@ -269,7 +274,9 @@ class KyptDetector(nn.Module):
         return self._engine
 
     def anneal(self, nepoch):
-        """kypt_detector.py:71-78."""
+        """kypt_detector.py:71-78 (nothing under keypoints_graph 'none')."""
+        if self.keypoints_graph == "none":
+            return
         if self.affinity_anneal > nepoch:
             self.affinity_params.requires_grad = False
         elif not self.affinity_start:
@@ -328,6 +335,8 @@ class KyptDetector(nn.Module):
 
     def get_affinity(self):
         """kypt_detector.py:171-211 (ver 3) -> (N,K,K,1)."""
+        if self.keypoints_graph == "none":
+            raise _lib.NmError("KyptDetector.get_affinity: keypoints_graph 'none' has no affinity")
         eng = self._eng()
         ctx = eng.ready()
         aff = torch.empty(self.nneighbor, self.nkeypoints, self.nkeypoints, 1, device=ctx.device)
@@ -345,6 +354,14 @@ class KyptDetector(nn.Module):
         kp, ff, fr = _f32(keypoints, dev), _f32(first_feature, dev), _f32(first_frame, dev)
         eng.call_conv("nm_decode_from_keypoints", _lib.ptr(kp), _lib.ptr(ff), _lib.ptr(fr), B, Tg, _lib.ptr(gen))
         return dict(gen=gen)
+
+
+def _need_graph(o: HotPathOptions, what: str) -> None:
+    """The learner builds its skeleton from the detector's affinity (neural_marionette.py:53 calls affinity.detach()): under
+    keypoints_graph 'none' there is none, and the reference cannot run this path either."""
+    if o.keypoints_graph == "none":
+        raise _lib.NmError(f"{what}: keypoints_graph 'none' has no affinity, and the learner needs one to build its skeleton "
+                           "(the reference fails here as well, neural_marionette.py:53); only the detector runs under 'none'")
 
 
 # ==========================================================================================
@@ -486,6 +503,7 @@ class HSVRNNBVH(nn.Module):
     # -- public surface -----------------------------------------------------------------------
     def encode(self, keypoints, affinity, SAMPLE_NUM=10, eps=None):
         """hsvrnn_bvh.py:67-156.  ``eps`` (T,S,B,Z) injects the standard-normal draws."""
+        _need_graph(self._o, "HSVRNNBVH.encode")
         eng = self._eng()
         ctx = eng.ready()
         dev = ctx.device
@@ -514,6 +532,7 @@ class HSVRNNBVH(nn.Module):
 
     def generate(self, keypoints_cond, affinity=None, Ttot=10, Tcond=3, SAMPLE_NUM=10, eps_post=None, eps_prior=None):
         """hsvrnn_bvh.py:158-234."""
+        _need_graph(self._o, "HSVRNNBVH.generate")
         eng = self._eng()
         ctx = eng.ready()
         dev = ctx.device
@@ -679,6 +698,7 @@ class NeuralMarionette(nn.Module):
         eps_post (Tcond,sample_num,Z) / eps_prior (Tgen,sample_num,Z) inject the noise.
         Returns keypoints_cond (1,Tcond,K,4) [the detected keypoints, as the script records], keypoints_gen
         (1,Tgen,sample_num,K,4) and voxels (sample_num,Tcond+Tgen,1,G,G,G) binarised at 0.5."""
+        _need_graph(self._engine.opts, "NeuralMarionette.sample_generation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
         det = self.kypt_detector(cond_voxel[None])
@@ -712,6 +732,7 @@ class NeuralMarionette(nn.Module):
         otherwise); eps_b (T,sample_num,Z): the second (prior, 'for choosing') draw at key frames.
         ``force_picks`` (list of (i1, i2) per key frame) replaces the two nearest-row selections (teacher forcing in tests).
         Returns keypoints (1,T,K,4), voxels (T,1,G,G,G) binarised at 0.5, and the selected row per key frame."""
+        _need_graph(self._engine.opts, "NeuralMarionette.sample_interpolation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
         det = self.kypt_detector(target_voxel[None])
@@ -765,6 +786,8 @@ class NeuralMarionette(nn.Module):
         log: Dict[str, torch.Tensor] = dict()
         keypoints = affinity = None
         d, det_m = self.dyna_module, self.kypt_detector
+        if module_actives["learner"]:
+            _need_graph(self._engine.opts, "NeuralMarionette.forward (learner)")
         if module_actives["learner"] and d.A is not None and det_m.affinity_start and not \
                 (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())):
             return self._forward_fused(vox_seq, eps)
@@ -816,6 +839,8 @@ class NeuralMarionette(nn.Module):
 
     def generate(self, vox_seq, module_actives=None, eps_post=None, eps_prior=None):
         """neural_marionette.py:58-103 ('dl' transition)."""
+        if module_actives["learner"]:
+            _need_graph(self._engine.opts, "NeuralMarionette.generate")
         B, T = vox_seq.shape[:2]
         assert self.Tcond < T
         log = dict()

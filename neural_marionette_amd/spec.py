@@ -22,6 +22,10 @@ HG_WIDTHS = (32, 48, 72)  # vox_modules.py:83-87
 VRNN_MLP_HIDDEN = 128   # hsvrnn_bvh.py:31,37,43,51
 
 
+# NM_GRAPH_* bits of nm_ctx_set_graph_loss (include/nm355.h)
+GRAPH_LOCAL_OFF, GRAPH_TIME_OFF, GRAPH_SPARSITY_OFF, GRAPH_DETACH, GRAPH_NONE = 1, 2, 4, 8, 16
+
+
 @dataclass
 class HotPathOptions:
     """The subset of the reference's argparse Namespace the hot path reads
@@ -69,6 +73,16 @@ class HotPathOptions:
         base = cls()
         return cls(**{k: get(k, v) for k, v in asdict(base).items()})
 
+    def graph_loss_flags(self) -> int:
+        """The NM_GRAPH_* word of nm_ctx_set_graph_loss (include/nm355.h) for these options (kypt_detector.py:20-30,112-143)."""
+        f = 0
+        if not self.using_local_const: f |= GRAPH_LOCAL_OFF
+        if not self.using_time_const: f |= GRAPH_TIME_OFF
+        if not self.using_sparsity_const: f |= GRAPH_SPARSITY_OFF
+        if self.keypoints_detach: f |= GRAPH_DETACH
+        if self.keypoints_graph == "none": f |= GRAPH_NONE
+        return f
+
     def check_fast_path(self) -> None:
         """The HIP path implements the pretrained-AIST configuration family
         (SURVEY §5 'Config / flags'); anything else is rejected loudly instead of
@@ -77,10 +91,10 @@ class HotPathOptions:
         if self.input_dim != 3: bad.append("input_dim must be 3")
         if self.const_intensity != 3: bad.append("const_intensity must be 3")
         if self.affinity_ver not in (0, 1, 2, 3): bad.append("affinity_ver must be 0, 1, 2 or 3 (4 draws Gumbel noise: not implemented)")
-        if self.graph_loss_ver != 1: bad.append("graph_loss_ver must be 1")
+        if self.graph_loss_ver not in (0, 1, 2): bad.append("graph_loss_ver must be 0, 1 or 2")
         if self.gaussian_cat_type not in ("none", "max", "sum"): bad.append("gaussian_cat_type must be 'none', 'max' or 'sum'")
         if self.vol_fit_type not in ("chamfer", "none", "gaussian"): bad.append("vol_fit_type must be chamfer / none / gaussian")
-        if self.keypoints_graph != "affinity_params": bad.append("keypoints_graph must be 'affinity_params'")
+        if self.keypoints_graph not in ("affinity_params", "none"): bad.append("keypoints_graph must be 'affinity_params' or 'none'")
         if not self.fixed_sigma and self.vol_fit_type == "gaussian": bad.append("fixed_sigma = 0 with vol_fit_type 'gaussian' is not implemented")
         if self.transition_type != "dl": bad.append("transition_type must be 'dl'")
         if self.grid_size % 8 != 0 or self.grid_size < 32:
@@ -165,7 +179,8 @@ def param_spec(opts: HotPathOptions) -> List[Tuple[str, Shape]]:
     F = FEAT_DIM
     out: List[Tuple[str, Shape]] = []
     d = "kypt_detector"
-    out.append((d + ".affinity_params", (opts.nneighbor, K, K if opts.affinity_ver < 3 else K - 1)))      # kypt_detector.py:57-68
+    if opts.keypoints_graph != "none":                     # kypt_detector.py:54-68 ('none': no affinity parameters)
+        out.append((d + ".affinity_params", (opts.nneighbor, K, K if opts.affinity_ver < 3 else K - 1)))      # kypt_detector.py:57-68
     v = d + ".vox_to_kypt"
     if not opts.fixed_sigma:
         out.append((v + ".sigmas", (K,)))                  # kypt_detector.py:258-260: created before the sub-modules
