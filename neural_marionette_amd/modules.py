@@ -496,6 +496,10 @@ class HSVRNNBVH(nn.Module):
 
     def _eps(self, n, shape, dev, eps):
         if eps is not None:
+            # the library reads n * prod(shape) floats: a smaller tensor (e.g. S samples of noise for SAMPLE_NUM > S) is an
+            # out-of-bounds read on the device, so the shape is checked here
+            if tuple(eps.shape) != (n, *shape):
+                raise ValueError(f"eps must be {(n, *shape)}, got {tuple(eps.shape)}")
             return _f32(eps, dev)
         # the reference draws one rsample per step from the device generator (hsvrnn_bvh.py:107,216)
         return torch.stack([torch.randn(*shape, device=dev) for _ in range(n)], dim=0) if n else torch.empty(0, *shape, device=dev)
@@ -585,6 +589,9 @@ class HSVRNNBVH(nn.Module):
         hh = _f32(h, dev)
         B = int(hh.shape[0])
         off = _f32(offset.reshape(B, self.nkeypoints, 3), dev)
+        want = (B, self.nlatent_kypt) if keypoints_obs is None else (int(SAMPLE_NUM), B, self.nlatent_kypt)
+        if tuple(eps.shape) != want:
+            raise ValueError(f"eps must be {want}, got {tuple(eps.shape)}")
         e = _f32(eps, dev)
         obs = None if keypoints_obs is None else _f32(keypoints_obs.reshape(B, -1), dev)
         kp = torch.empty(B, self.nkeypoints * 4, device=dev)

@@ -1306,7 +1306,8 @@ def test_first_plain_call_never_returns_nan_where_fp32_would_not():
     net.check_finite()
 
 
-@pytest.mark.parametrize("B,S,K,T", [(1, 10, 24, 16), (4, 10, 24, 16), (3, 3, 24, 5), (2, 10, 12, 7), (2, 16, 22, 4), (4, 1, 28, 3)])
+@pytest.mark.parametrize("B,S,K,T", [(1, 10, 24, 16), (4, 10, 24, 16), (3, 3, 24, 5), (2, 10, 12, 7), (2, 16, 22, 4), (4, 1, 28, 3),
+                                     (9, 10, 24, 5), (6, 16, 24, 5), (16, 6, 24, 5)])      # (the chain's limits: S B <= 96, S <= 16, B <= 16)
 def test_persistent_encode_is_bit_identical_to_launch_per_phase_steps(B, S, K, T):
     """vrnn_post_chain_kernel (round 5; BASELINE north_star "GRU / prior / posterior MLPs fused into one kernel per timestep" - here
     all T posterior steps of a stand-alone HSVRNNBVH.encode are ONE persistent launch: worker, sample and statistics workgroups,
