@@ -4095,6 +4095,7 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
         // the fused-upsample layers on the coarse grid with composite weights (nm_up2c.hip): main + shell launch, timed together
         ProfRec rec;
         rec.flops = 2.0 * in.N * (double)g.OD * g.OH * g.OW * g.Cout * (double)(cin_real > 0 ? cin_real : in.C) * 27.0;
+        if (nm_up2y_active()) rec.flops *= 0.5;      // the products conv_up2y_kernel PERFORMS: 4 x 27 per coarse voxel instead of the fine conv's 8 x 27 (halo rows not counted)
         const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
         if (prof_rec) {
             rec.a = prof_event(); rec.b = prof_event(); rec.variant = 12;

@@ -5,7 +5,11 @@
 
 // true when the layer shape is taken by the composite-weight kernel (otherwise conv_f16s<.., UP2> of nm_conv.hip runs it)
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad);
+// true when the split-fp16 mode runs the main launch in the product-then-interpolate form along y (conv_up2y_kernel: 4 x 27 instead of
+// 8 x 27 products per coarse voxel); NM355_UP2Y=0 keeps conv_up2c[_x16]_kernel
+bool nm_up2y_active();
 // floats (4-byte units) of the packed composite weight sets of one layer: 8 parity sets of 27 coarse taps + 56 shell-correction sets
+// + the four (pz, px) sets of conv_up2y_kernel
 size_t nm_up2c_weight_floats(int Cin, int Co_pad);
 // OIDHW fp32 (Cout, Cin, 3, 3, 3) -> every composite set, split fp16, MFMA operand layout
 int nm_launch_up2c_compose(const float* w_oidhw, int Cout, int Cin, int Co_pad, void* packed, hipStream_t s);

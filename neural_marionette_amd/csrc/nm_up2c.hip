@@ -7,8 +7,11 @@
 //      p = 0:  t=-1 -> (.75, .25, 0)    t=0 -> (.25, .75, 0)    t=+1 -> (0, .75, .25)
 //      p = 1:  t=-1 -> (.25, .75, 0)    t=0 -> (0, .75, .25)    t=+1 -> (0, .25, .75)
 // so  out[2i+p] = sum_{d, c} C_p[d][c] * a[i+d][c]  with the composite weights  C_p[d] = sum_t Uz[pz][tz][dz] Uy[..] Ux[..] w[t]:
-// eight 3x3x3 convolutions of the ACTIVATED COARSE tensor, one per parity class, the same MAC count as the fine convolution and
-// no interpolation arithmetic at all.  The coarse halo tile of a brick is 8x smaller than the fine one: all 64 input channels of
+// eight 3x3x3 convolutions of the ACTIVATED COARSE tensor, one per parity class, and no interpolation arithmetic at all.  That is
+// the fine convolution's MAC count, 8 x 27 products per coarse voxel - of which the result needs 27: the channel contraction commutes
+// with the interpolation, so the products can be taken once per coarse voxel and RAW tap and interpolated afterwards.  The split-fp16
+// mode does that along y (conv_up2y_kernel below: 4 x 27 per coarse voxel + one halo cell per side of a brick); the composite
+// kernels remain for the one-product modes and as the A/B arm NM355_UP2Y=0.  The coarse halo tile of a brick is 8x smaller than the fine one: all 64 input channels of
 // a (2+2) x (8+2) x (8+2) coarse tile sit in LDS at once (split fp16 hi/lo, 104 KB), staged once per brick, and the 864 k-steps of
 // the brick's eight parity classes run from it without a barrier.
 //
@@ -55,6 +58,7 @@ struct Up2cParams {
     const float* in; const float* in_scale; const float* in_shift; float in_slope;
     int N, ID, IH, IW, Cin;
     const half8* wc;             // composite sets (see set_offset)
+    const half8* wy;             // the four (pz, px) sets of conv_up2y_kernel (behind the composite sets)
     const float* bias; float* out; float* part;
     int Cout, Co_pad;
     int nbz, nby, nbx;           // bricks per frame
@@ -170,6 +174,38 @@ __global__ void up2c_compose_kernel(const float* __restrict__ w, int Cout, int C
         const _Float16 lo = (_Float16)((vf - (float)hi) * UP2C_SPLIT_SCALE);
         // position inside the set: [chunk][tap], taps in the order they were decoded (gt)
         const size_t base = (((size_t)set_tap_offset(e) * C16) + (size_t)cb * axes_taps(S) + gt) * 4 * Co_pad * 8;
+        packed[base + ((size_t)hh * Co_pad + co) * 8 + j] = hi;
+        packed[base + ((size_t)(2 + hh) * Co_pad + co) * 8 + j] = lo;
+    }
+}
+
+// The four sets of conv_up2y_kernel, behind the TOTAL_TAPS composite ones: class (pz, px), composite along z and x only, the RAW
+// taps along y.  Same layout as a composite set with the 27 'taps' u = (dz * 3 + dx) * 3 + ty.
+constexpr int YSETS = 4;
+__global__ void up2y_compose_kernel(const float* __restrict__ w, int Cout, int Cin, int Co_pad, _Float16* __restrict__ packed) {
+    const int C16 = Cin >> 4;
+    const size_t per_tap = (size_t)C16 * 2 * Co_pad * 8;
+    const size_t total = (size_t)YSETS * 27 * per_tap;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int j = i & 7; size_t r = i >> 3;
+        const int co = r % Co_pad; r /= Co_pad;
+        const int hh = r & 1; r >>= 1;
+        const int cb = r % C16; const int gu = (int)(r / C16);
+        const int cls = gu / 27, u = gu % 27, ty = u % 3, dx = (u / 3) % 3, dz = u / 9;
+        const int pz = cls >> 1, px = cls & 1;
+        const int ci = cb * 16 + hh * 8 + j;
+        double v = 0.0;
+        if (co < Cout && ci < Cin) {
+            const float* wk = w + ((size_t)co * Cin + ci) * 27;
+            for (int tz = 0; tz < 3; ++tz) for (int tx = 0; tx < 3; ++tx) {
+                const double c = ucoef(pz, tz, dz) * ucoef(px, tx, dx);
+                if (c != 0.0) v += c * (double)wk[(tz * 3 + ty) * 3 + tx];
+            }
+        }
+        const float vf = (float)v;
+        const _Float16 hi = (_Float16)vf;
+        const _Float16 lo = (_Float16)((vf - (float)hi) * UP2C_SPLIT_SCALE);
+        const size_t base = (((size_t)(TOTAL_TAPS + cls * 27) * C16) + (size_t)cb * 27 + u) * 4 * Co_pad * 8;
         packed[base + ((size_t)hh * Co_pad + co) * 8 + j] = hi;
         packed[base + ((size_t)(2 + hh) * Co_pad + co) * 8 + j] = lo;
     }
@@ -656,6 +692,238 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
     }
 }
 
+// ---- the product-then-interpolate form along y ------------------------------------------------------------------------------
+// Trilinear upsampling acts per channel and the conv's channel contraction is linear, so along any one axis the two commute:
+//      out[2i + p] = sum_d sum_t U[p][t][d] P_t[i + d],     P_t[r] = sum_c W_t[c] a[r][c]   (t the fine tap, r a COARSE cell)
+// with U the table at the top of this file.  The composite form spends 2 (parities) x 3 (coarse offsets) products per coarse cell
+// and axis; this form spends 3 (the raw taps) on the cells of the brick plus one halo cell per side and pays for it with fp32
+// interpolation of the products (weights 1/4, 3/4: exact).  conv_up2y_kernel applies it along y and keeps composite weights along z
+// and x: per (pz, px) class 3 x 9 x (BY + 2) products replace 2 x 27 x BY - 10/16 of the MFMAs, the same bricks, the same LDS
+// image (staging code shared verbatim with conv_up2c_x16_kernel), the same A-operand reads per brick for FEWER B operands.
+//
+// Mapping: wave = (pz, px, column block of 16 output channels); a row tile of v_mfma_f32_16x16x32_f16 is ONE coarse y of the halo
+// tile (row r -> x = r & 7, z = r >> 3), so the 10 tiles x 3 taps of a lane's accumulators are the SAME (z, x, channel) at the ten
+// coarse y's: the interpolation along y is twelve in-lane FMAs per cell and needs no LDS and no cross-lane traffic.  A k-step is one
+// coarse (dz, dx) tap of a 32-channel group: 20 A reads, 6 B loads, 90 MFMAs.
+// The halo tile is staged with clamped indices, so the halo products at the volume border are those of the clamped cell: the kernel
+// computes exactly what the composite kernel computes (zero padding ignored), and the shell kernels below correct it as before.
+// The GroupNorm partials of class (pz, px), parity py go to slot 8 brick + 4 pz + 2 px + py: the class's two waves fill its two
+// column blocks - every slot is written once, in a fixed order.
+constexpr int YT = HY;
+
+__global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
+    extern __shared__ f32x4 lds_raw[];
+    half8* tile = reinterpret_cast<half8*>(lds_raw);               // [buffer][chunk*4 + hl*2 + h][HVP] x 16 B, slot = hz*ZP + hy*HX + hx
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q = lane >> 4, r16 = lane & 15;
+    const int cls = wave >> 1, nbw = wave & 1, pz = cls >> 1, px = cls & 1;
+    const int C16 = p.Cin >> 4, NCG = p.Cin / CG, NH = p.Cout >> 5;
+    const size_t plane = (size_t)p.Co_pad;
+    const size_t kstride = 4 * plane;                             // half8 units between consecutive (tap, ty) units of a chunk
+    const half8* __restrict__ wset = p.wy + (size_t)cls * 27 * C16 * kstride;       // wave-uniform
+    const unsigned wlane = (unsigned)((q >> 1) * 27 * (int)kstride + (q & 1) * (int)plane + nbw * 16 + r16) * 16u;
+    const size_t kbytes = kstride * 16, lobytes = 2 * plane * 16;
+    const int OD = 2 * p.ID, OH = 2 * p.IH, OW = 2 * p.IW;
+    // A row of this lane in tile 0, tap 0: tile j adds j * HX, tap (dz, dx) adds dz * ZP + dx.  A lane group of a ds_read_b128 takes
+    // rows {0-3, 12-15} of one plane and {4-11} of the next (HVP = 1 mod 16 slots on): 15 distinct slots of 16
+    const int abase = ((q >> 1) * 4 + (q & 1)) * HVP + (r16 >> 3) * ZP + (r16 & 7);
+    const int s_oct = tid & 3;
+    const int s_plane = (s_oct >> 1) * 4 + (s_oct & 1);
+    constexpr int NV = HZ * HY * HX, SITEMS = (NV * 4 + 511) / 512;
+    const bool affine = p.in_scale != nullptr;
+
+    const int bricks = p.nbz * p.nby * p.nbx, total = p.N * bricks;
+    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int item0 = (int)blockIdx.x * per, item_end = min(total, item0 + per);
+    if (item0 >= item_end) return;
+    auto pos_of = [&](int item, int nh, int cg) {
+        StepPos s; s.n = item / bricks; s.br = item % bricks; s.nh = nh; s.cg = cg;
+        s.cx0 = (s.br % p.nbx) * BX; s.cy0 = ((s.br / p.nbx) % p.nby) * BY; s.cz0 = (s.br / (p.nbx * p.nby)) * BZ;
+        return s;
+    };
+    // staging: as in conv_up2c_x16_kernel (scale / shift of the tile being staged behind the two tile buffers)
+    float* aff = reinterpret_cast<float*>(tile + 2 * NPLANES * HVP);
+    f32x4 pr_a, pr_b;
+    pr_a = pr_b = f32x4{0.f, 0.f, 0.f, 0.f};
+    // (both values per lane, selected at the store: a per-lane POINTER select is loop-invariant, 64 bits wide and was spilled)
+    float aff_a = 0.f, aff_b = 0.f;
+    auto aff_load = [&](const StepPos& s) {
+        if (affine && tid < 64) { const size_t e = (size_t)s.n * p.Cin + s.cg * CG + (tid & 31); aff_a = p.in_scale[e]; aff_b = p.in_shift[e]; }
+    };
+    auto aff_store = [&]() { if (affine && tid < 64) aff[tid] = tid < 32 ? aff_a : aff_b; };
+    auto issue = [&](const StepPos& s, int k) {
+        int v;      // (opaque: see conv_up2c_kernel)
+        asm volatile("v_lshrrev_b32 %0, 2, %1\n\tv_add_u32 %0, %2, %0" : "=v"(v) : "v"(tid), "s"(128 * k));
+        if (v < NV) {
+            const int hx = v % HX, hy = (v / HX) % HY, hz = v / (HX * HY);
+            const int gz = min(max(s.cz0 - 1 + hz, 0), p.ID - 1), gy = min(max(s.cy0 - 1 + hy, 0), p.IH - 1), gx = min(max(s.cx0 - 1 + hx, 0), p.IW - 1);
+            ld8_raw<false>(p.in, ((((size_t)s.n * p.ID + gz) * p.IH + gy) * p.IW + gx) * p.Cin + s.cg * CG + s_oct * 8, pr_a, pr_b);
+        }
+    };
+    auto commit = [&](half8* buf, int k) {
+        int v;
+        asm volatile("v_lshrrev_b32 %0, 2, %1\n\tv_add_u32 %0, %2, %0" : "=v"(v) : "v"(tid), "s"(128 * k));
+        if (v < NV) {
+            const int hx = v % HX, hy = (v / HX) % HY, hz = v / (HX * HY);
+            half8 hi, lo;
+            f32x4 sca = {0.f, 0.f, 0.f, 0.f}, scb = sca, sha = sca, shb = sca;
+            if (affine) {
+                sca = *reinterpret_cast<const f32x4*>(aff + s_oct * 8); scb = *reinterpret_cast<const f32x4*>(aff + s_oct * 8 + 4);
+                sha = *reinterpret_cast<const f32x4*>(aff + 32 + s_oct * 8); shb = *reinterpret_cast<const f32x4*>(aff + 32 + s_oct * 8 + 4);
+            }
+            split8(act4(pr_a, sca, sha, affine, p.in_slope), act4(pr_b, scb, shb, affine, p.in_slope), hi, lo);
+            const int slot = hz * ZP + hy * HX + hx;
+            buf[s_plane * HVP + slot] = hi;
+            buf[(s_plane + 2) * HVP + slot] = lo;
+        }
+    };
+    auto ldw = [&](const char* base, size_t extra) { return *reinterpret_cast<const half8*>(base + extra + wlane); };
+
+    // first tile: staged in the open
+    StepPos cs = pos_of(item0, 0, 0);
+    aff_load(cs); aff_store();
+    lds_barrier();
+#pragma unroll
+    for (int k = 0; k < SITEMS; ++k) { issue(cs, k); commit(tile, k); }
+    lds_barrier();
+    int cur = 0, item = item0;
+    f32x4 acc[3][YT];
+    // One software-pipelined stream over the steps: the B operands of a k-step (three register sets by name, two live; 9 % 3 == 0
+    // keeps the set of a step's first k-step fixed) are requested one k-step ahead, an A tile is refilled with the tile NRING places
+    // further on right after its last MFMA.  Staging of the next step's tile: item i is loaded at k-step 2 i and written at 2 i + 1;
+    // barriers at k-step 1 (before the first write into the other buffer: every wave has left the previous step, which read it) and
+    // at k-step 8 (after the last write, before the first read of that buffer by the A refills of this k-step's last tiles).
+    constexpr int KS = 9, NRING = 2;
+    const char* wk = reinterpret_cast<const char*>(wset);              // (cs.nh = cs.cg = 0)
+    half8 bh[3][3], bl[3][3], ah[NRING], al[NRING];
+#pragma unroll
+    for (int ty = 0; ty < 3; ++ty) { bh[0][ty] = ldw(wk, ty * kbytes); bl[0][ty] = ldw(wk, ty * kbytes + lobytes); }
+#pragma unroll
+    for (int u = 0; u < NRING; ++u) { ah[u] = tile[abase + u * HX]; al[u] = tile[abase + u * HX + 2 * HVP]; }
+    for (;;) {
+        StepPos ns = cs; bool have_next = true;
+        if (cs.cg + 1 < NCG) ns.cg = cs.cg + 1;
+        else if (cs.nh + 1 < NH) { ns.nh = cs.nh + 1; ns.cg = 0; }
+        else if (item + 1 < item_end) ns = pos_of(item + 1, 0, 0);
+        else have_next = false;
+        if (cs.cg == 0) {
+#pragma unroll
+            for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+                for (int j = 0; j < YT; ++j) acc[ty][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const half8* tb = tile + cur * (NPLANES * HVP);
+        half8* nb_ = tile + (cur ^ 1) * (NPLANES * HVP);
+        const bool stage = have_next;
+        const char* wnext = reinterpret_cast<const char*>(wset + (size_t)ns.nh * 32 + (size_t)(ns.cg * (CG / 16)) * 27 * kstride);
+#pragma unroll
+        for (int t = 0; t < KS; ++t) {
+            const int s = t % 3, s1 = (t + 1) % 3;
+            if (stage) {
+                if (t == 0) aff_load(ns);
+                if (t == 1) aff_store();
+            }
+            if (have_next && (t == 1 || t == 8)) lds_barrier();
+            if (stage) {
+#pragma unroll
+                for (int i = 0; i < SITEMS; ++i) {
+                    if (t == 2 * i + 1) commit(nb_, i);
+                    if (t == 2 * i) issue(ns, i);
+                }
+            }
+            // B operands of the next k-step - requested BEHIND the staging code (see conv_up2c_x16_kernel)
+            {
+                const char* wsrc = (t + 1 < KS) ? wk + 3 * kbytes : wnext;
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty) { bh[s1][ty] = ldw(wsrc, ty * kbytes); bl[s1][ty] = ldw(wsrc, ty * kbytes + lobytes); }
+                wk += 3 * kbytes;
+            }
+            // ONE accumulator for the three products (see conv_up2c_x16_kernel)
+            half8 b2k[3];
+#pragma unroll
+            for (int ty = 0; ty < 3; ++ty) b2k[ty] = bh[s][ty] * (_Float16)UP2C_SPLIT_SCALE;
+            UP2C_SB();
+#pragma unroll
+            for (int j = 0; j < YT; ++j) {
+                const int rs = (YT * t + j) % NRING;
+                const int jn = (j + NRING) % YT, tn = t + (j + NRING) / YT;
+                const half8* xb = (tn == KS) ? nb_ : tb;
+                const int nof = (tn == KS) ? 0 : (tn / 3) * ZP + (tn % 3);
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty) acc[ty][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rs], b2k[ty], acc[ty][j], 0, 0, 0);
+                UP2C_SB();
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty) acc[ty][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rs], bl[s][ty], acc[ty][j], 0, 0, 0);
+                ah[rs] = xb[abase + jn * HX + nof];
+                UP2C_SB();
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty) acc[ty][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rs], bh[s][ty], acc[ty][j], 0, 0, 0);
+                al[rs] = xb[abase + jn * HX + nof + 2 * HVP];
+                UP2C_SB();
+            }
+        }
+        wk = wnext;
+        if (cs.cg == NCG - 1) {
+            // ---- epilogue of this 32-channel group: interpolation along y (fine y = 2 i + py of coarse cell i reads the tiles i, i + 1,
+            // i + 2 = cells i - 1, i, i + 1), bias, store, GroupNorm partials without the shell
+            const size_t sX = (size_t)p.Cout;
+            const bool border_brick = cs.cz0 == 0 || cs.cz0 + BZ == p.ID || cs.cy0 == 0 || cs.cy0 + BY == p.IH || cs.cx0 == 0 || cs.cx0 + BX == p.IW;
+            const int oz = 2 * (cs.cz0 + (q >> 1)) + pz;
+            const bool zshell = oz == 0 || oz == OD - 1;
+            const int co = cs.nh * 32 + nbw * 16 + r16;
+            const float bv = p.bias ? p.bias[co] : 0.f;
+            constexpr float C1 = 0.25f / UP2C_SPLIT_SCALE, C3 = 0.75f / UP2C_SPLIT_SCALE;
+#pragma unroll
+            for (int py = 0; py < 2; ++py) {
+                float s = 0.f, ss = 0.f;
+#pragma unroll
+                for (int i = 0; i < BY; ++i) {
+                    const int oy = 2 * (cs.cy0 + i) + py;
+                    float* base = p.out + ((((size_t)cs.n * OD + oz) * OH + oy) * OW + 2 * (cs.cx0 + 4 * (q & 1)) + px) * sX + co;
+                    const bool zy = zshell || oy == 0 || oy == OH - 1;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float v;
+                        if (py == 0) {
+                            v = C3 * acc[0][i][r];
+                            v = __builtin_fmaf(C1, acc[0][i + 1][r], v);
+                            v = __builtin_fmaf(C1, acc[1][i][r], v);
+                            v = __builtin_fmaf(C3, acc[1][i + 1][r], v);
+                            v = __builtin_fmaf(C3, acc[2][i + 1][r], v);
+                            v = __builtin_fmaf(C1, acc[2][i + 2][r], v);
+                        } else {
+                            v = C1 * acc[0][i][r];
+                            v = __builtin_fmaf(C3, acc[0][i + 1][r], v);
+                            v = __builtin_fmaf(C3, acc[1][i + 1][r], v);
+                            v = __builtin_fmaf(C1, acc[1][i + 2][r], v);
+                            v = __builtin_fmaf(C1, acc[2][i + 1][r], v);
+                            v = __builtin_fmaf(C3, acc[2][i + 2][r], v);
+                        }
+                        v += bv;
+                        base[(size_t)(2 * r) * sX] = v;
+                        float mv = v;
+                        if (border_brick) {
+                            const int ox = 2 * (cs.cx0 + 4 * (q & 1) + r) + px;
+                            if (zy || ox == 0 || ox == OW - 1) mv = 0.f;
+                        }
+                        s += mv; ss = __builtin_fmaf(mv, mv, ss);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (p.part) {
+                    s += __shfl_xor(s, 16); ss += __shfl_xor(ss, 16);
+                    s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+                    if (q == 0) { float* dst = p.part + (((size_t)cs.n * p.nblk + cs.br * 8 + cls * 2 + py) * p.Cout + co) * 2; dst[0] = s; dst[1] = ss; }
+                }
+            }
+        }
+        if (!have_next) break;
+        if (ns.cg == 0 && ns.nh == 0) ++item;
+        cs = ns; cur ^= 1;
+    }
+}
+
 // ---- shell kernels -----------------------------------------------------------------------------------------------------------
 // Ownership of the shell cells (per parity class): a cell on two or three faces belongs to an EDGE item, every other shell cell to
 // the FACE item of its face.  A face cell needs one correction set (S = its face's axis, 9 coarse taps); the cells of an edge need
@@ -882,16 +1150,19 @@ int g_cus = 0;
 
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad) {
     return nm_ls().up2c && ks == 3 && stride == 1 && pad == 1 && ID % BZ == 0 && IH % BY == 0 && IW % BX == 0 && Cin % CG == 0 && Cout % 32 == 0 &&
-           ((Cin == 64 && Cout == 32) || (nm_ls().up2c_all && Cin <= 128 && Cout <= 64));
+           ((Cin == 64 && Cout == 32) || ((nm_ls().up2c_all || (nm_ls().up2y >= 2 && !nm_conv_single())) && Cin <= 128 && Cout <= 64));      // (the one-product modes keep the wider layers on conv_f16s)
 }
 
+bool nm_up2y_active() { return nm_ls().up2y != 0 && nm_ls().conv_mode == 1 && nm_conv_single() == 0; }
+
 size_t nm_up2c_weight_floats(int Cin, int Co_pad) {
-    return (size_t)TOTAL_TAPS * (Cin >> 4) * 4 * Co_pad * 8 / 2;       // halves -> 4-byte units
+    return (size_t)(TOTAL_TAPS + YSETS * 27) * (Cin >> 4) * 4 * Co_pad * 8 / 2;       // halves -> 4-byte units
 }
 
 int nm_launch_up2c_compose(const float* w, int Cout, int Cin, int Co_pad, void* packed, hipStream_t s) {
     if (Cin % 16 || Co_pad % 32 || Cout > Co_pad) { nm_set_error("up2c_compose: bad channels Cin=%d Cout=%d/%d", Cin, Cout, Co_pad); return NM_ERR_ARG; }
     hipLaunchKernelGGL(up2c_compose_kernel, dim3(2048), dim3(256), 0, s, w, Cout, Cin, Co_pad, reinterpret_cast<_Float16*>(packed));
+    hipLaunchKernelGGL(up2y_compose_kernel, dim3(512), dim3(256), 0, s, w, Cout, Cin, Co_pad, reinterpret_cast<_Float16*>(packed));
     return nm_check_hip(hipGetLastError(), "up2c_compose launch");
 }
 
@@ -917,6 +1188,7 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_up2c)");
         attr_set.mark();
     }
@@ -934,7 +1206,7 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     Up2cParams p;
     p.in = in.p; p.in_scale = in.scale; p.in_shift = in.shift; p.in_slope = in.slope;
     p.N = in.N; p.ID = in.D; p.IH = in.H; p.IW = in.W; p.Cin = in.C;
-    p.wc = static_cast<const half8*>(packed); p.bias = bias; p.out = out; p.part = part;
+    p.wc = static_cast<const half8*>(packed); p.wy = p.wc + (size_t)TOTAL_TAPS * (in.C >> 4) * 4 * Co_pad; p.bias = bias; p.out = out; p.part = part;
     p.Cout = Cout; p.Co_pad = Co_pad;
     p.nbz = in.D / BZ; p.nby = in.H / BY; p.nbx = in.W / BX;
     p.nblk = nm_up2c_blocks_per_frame(in.D, in.H, in.W);
@@ -945,6 +1217,7 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     else if (io == 1) hipLaunchKernelGGL((conv_up2c_kernel<true, 1>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     // (the one-product modes keep the 32x32x16 kernel in fp32 storage too: their bfloat16-storage instantiations are bit-compared with
     //  it, tests/test_storage16_gpu.py; NM355_UP2C_X16=2 forces the 16x16x32 form there as well - A/B)
+    else if (!single && nm_ls().up2y) hipLaunchKernelGGL(conv_up2y_kernel, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (nm_ls().up2c_x16 >= 2 && single) hipLaunchKernelGGL(conv_up2c_x16_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (nm_ls().up2c_x16 && !single) hipLaunchKernelGGL(conv_up2c_x16_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (single) hipLaunchKernelGGL(conv_up2c_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
