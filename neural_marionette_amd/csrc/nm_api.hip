@@ -70,6 +70,8 @@ NmLaunchState::NmLaunchState()
       , p2_defer(env_int("NM355_P2_DEFER", 0))              // 1: conv_f16p2 with one accumulator per tile and the epilogue deferred into the next brick's first step (A/B: slower)
       , fast_decode(env_int("NM355_FAST_DECODE", 1))        // 0: the persistent convs decode a brick's position with integer divisions instead of host-made reciprocal multiplications (A/B)
       , up2y(env_int("NM355_UP2Y", 2))                      // 0: the fused-upsample layers keep the composite-weight kernel in all three axes (A/B); 1: conv_up2y_kernel (products on the coarse grid, interpolated along y) on the 64 -> 32 layer; 2: on the 128 -> 64 layer too
+      , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
+      , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
 { store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
   chain_wgpoll = env_int("NM355_CHAIN_WGPOLL", 1);      // 0: every wave of the cross-XCD rollout chain polls for itself (round 5; A/B)
   chain_xcd_nogo = env_int("NM355_CHAIN_XCD_NOGO", 0);  // test hook: the one-XCD chain never starts (its fallback must do the work)

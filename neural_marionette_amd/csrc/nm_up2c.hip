@@ -10,7 +10,8 @@
 // eight 3x3x3 convolutions of the ACTIVATED COARSE tensor, one per parity class, and no interpolation arithmetic at all.  That is
 // the fine convolution's MAC count, 8 x 27 products per coarse voxel - of which the result needs 27: the channel contraction commutes
 // with the interpolation, so the products can be taken once per coarse voxel and RAW tap and interpolated afterwards.  The split-fp16
-// mode does that along y (conv_up2y_kernel below: 4 x 27 per coarse voxel + one halo cell per side of a brick); the composite
+// mode does that along y (conv_up2y_kernel below: 4 x 27 per coarse voxel + one halo cell per side of a COLUMN of bricks along y:
+// a workgroup marches along y and carries the halo products from brick to brick); the composite
 // kernels remain for the one-product modes and as the A/B arm NM355_UP2Y=0.  The coarse halo tile of a brick is 8x smaller than the fine one: all 64 input channels of
 // a (2+2) x (8+2) x (8+2) coarse tile sit in LDS at once (split fp16 hi/lo, 104 KB), staged once per brick, and the 864 k-steps of
 // the brick's eight parity classes run from it without a barrier.
@@ -29,6 +30,9 @@
 // coarse tensor (axes in S: the single outward tap, which reads the voxel's own coarse cell with weight 1; the other axes: the
 // interior composite) - 9, 3 or 1 coarse taps.  conv_up2c_shell_kernel applies them to the shell (9 % of the voxels, 3 % of the
 // MACs) after the main kernel and owns the shell's GroupNorm partial sums; the main kernel leaves the shell out of its own.
+// Along an axis with RAW taps the padding needs no correction: the outward tap's products are simply left out of the interpolation.
+// conv_up2y_kernel does that along y, so with it as the main kernel the y faces are final after the main launch (and counted in
+// its partial sums): the shell keeps the z and x faces, and on the edges and corners every subset of border axes except {y}.
 #include "nm_up2c.h"
 
 namespace {
@@ -63,6 +67,8 @@ struct Up2cParams {
     int Cout, Co_pad;
     int nbz, nby, nbx;           // bricks per frame
     int nblk;                    // partial blocks per frame (bricks + shell items)
+    int march;                   // conv_up2y_kernel<true> is launched: workgroups take whole columns of bricks along y and carry the two halo row tiles
+    int ypad;                    // conv_up2y_kernel is the main kernel and zero-pads along y itself: the y faces are not the shell kernels'
     int diag;                    // NM355_UP2C_DIAG (timing experiments only): 1 (unused), 2 no staging, 4 no shell launch, 8 no MFMA loop, 16 weights from one address, 32 no barriers, 64 (with NM355_UP2C_X16=0) the 32x32x16 kernel with one accumulator
 };
 
@@ -705,12 +711,25 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
 // tile (row r -> x = r & 7, z = r >> 3), so the 10 tiles x 3 taps of a lane's accumulators are the SAME (z, x, channel) at the ten
 // coarse y's: the interpolation along y is twelve in-lane FMAs per cell and needs no LDS and no cross-lane traffic.  A k-step is one
 // coarse (dz, dx) tap of a 32-channel group: 20 A reads, 6 B loads, 90 MFMAs.
-// The halo tile is staged with clamped indices, so the halo products at the volume border are those of the clamped cell: the kernel
-// computes exactly what the composite kernel computes (zero padding ignored), and the shell kernels below correct it as before.
+// The halo tile is staged with clamped indices, so the halo products at the volume border are those of the clamped cell.  Along z
+// and x the kernel computes what the composite kernel computes (zero padding ignored) and the shell kernels below correct it as
+// before; along y the epilogue leaves the outward tap's terms out at oy = 0 and oy = OH - 1 (p.ypad; NM355_UP2Y_YPAD=0: the shell
+// kernels correct the y faces too), so a voxel on a y face and on no other is final here and part of this kernel's partial sums.
+//
+// Marching (p.march).  Tiles 8 and 9 of a brick are the cells, the operands and the MFMA sequence of tiles 0 and 1 of its successor
+// along y.  A workgroup therefore takes a contiguous range of whole COLUMNS (frame, brick z, brick x) and walks each along y: a
+// column's first brick runs all ten tiles, every further one copies acc[..][8..9] to acc[..][0..1] after its predecessor's
+// epilogue, stages the rows hy = 2 .. 9 only (320 of 400 cells) and runs tiles 2 .. 9 - (10 + 8 (nby - 1)) / (10 nby) of the MFMAs
+// and of the staging, bit for bit the same result.  With two output groups (128 -> 64) the column is marched once per group (step
+// order: column, output group, brick, channel group).  Where there are fewer columns than CUs (small extents) every brick is its own
+// item as before, and so where whole columns would give the busiest workgroup more row tiles than single bricks do (config 4's
+// 128 -> 64 layer: 288 columns on 256 CUs).  NM355_UP2Y_MARCH: 0 never, 2 always marches.
 // The GroupNorm partials of class (pz, px), parity py go to slot 8 brick + 4 pz + 2 px + py: the class's two waves fill its two
 // column blocks - every slot is written once, in a fixed order.
 constexpr int YT = HY;
+struct StepPosY : StepPos { int iy; };      // iy: the brick's place in its column (0: all ten row tiles; else tiles 0 and 1 are carried)
 
+template <bool MARCH>
 __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
     extern __shared__ f32x4 lds_raw[];
     half8* tile = reinterpret_cast<half8*>(lds_raw);               // [buffer][chunk*4 + hl*2 + h][HVP] x 16 B, slot = hz*ZP + hy*HX + hx
@@ -733,14 +752,31 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
     constexpr int NV = HZ * HY * HX, SITEMS = (NV * 4 + 511) / 512;
     const bool affine = p.in_scale != nullptr;
 
-    const int bricks = p.nbz * p.nby * p.nbx, total = p.N * bricks;
+    // an item is a column (frame, brick z, brick x) of L = nby bricks when marching, else one brick (x-fastest, L = 1)
+    const int bricks = p.nbz * p.nby * p.nbx, ncol = p.nbz * p.nbx, L = MARCH ? p.nby : 1;
+    const int per_frame = MARCH ? ncol : bricks, total = p.N * per_frame;
     const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
     const int item0 = (int)blockIdx.x * per, item_end = min(total, item0 + per);
     if (item0 >= item_end) return;
-    auto pos_of = [&](int item, int nh, int cg) {
-        StepPos s; s.n = item / bricks; s.br = item % bricks; s.nh = nh; s.cg = cg;
+    auto pos_of = [&](int item, int iy, int nh, int cg) {
+        StepPosY s; s.n = item / per_frame; s.nh = nh; s.cg = cg; s.iy = iy;
+        const int c = item % per_frame;
+        s.br = MARCH ? ((c / p.nbx) * p.nby + iy) * p.nbx + c % p.nbx : c;
         s.cx0 = (s.br % p.nbx) * BX; s.cy0 = ((s.br / p.nbx) % p.nby) * BY; s.cz0 = (s.br / (p.nbx * p.nby)) * BZ;
         return s;
+    };
+    // a carried brick (iy > 0) needs the rows hy = 2 .. 9 only: 320 cells in three items.  The cell of a staging thread follows from
+    // five per-step scalars (kept opaque: as selects of constants they were threaded into branches all through the staging code)
+    // cells, rows per z plane, 2^16 / (rows * HX) rounded up, first row, slot of cell v = v + hz * zs + y0 * HX
+    struct StageMap { int nv, rows, rcp, y0, zs; };
+    auto stage_map = [&](bool cr) {
+        StageMap m = {cr ? HZ * BY * HX : NV, cr ? BY : HY, cr ? 65536 / (BY * HX) + 1 : 65536 / (HY * HX) + 1, cr ? 2 : 0, cr ? ZP - BY * HX : ZP - HY * HX};
+        if constexpr (MARCH) asm volatile("" : "+s"(m.nv), "+s"(m.rows), "+s"(m.rcp), "+s"(m.y0), "+s"(m.zs));
+        return m;
+    };
+    auto cell_of = [&](int v, const StageMap& m, int& hz, int& hy, int& hx) {
+        if constexpr (MARCH) { const int vx = v / HX; hx = v - vx * HX; hz = (v * m.rcp) >> 16; hy = vx - hz * m.rows + m.y0; }      // (v < 512)
+        else { hx = v % HX; hy = (v / HX) % HY; hz = v / (HX * HY); }
     };
     // staging: as in conv_up2c_x16_kernel (scale / shift of the tile being staged behind the two tile buffers)
     float* aff = reinterpret_cast<float*>(tile + 2 * NPLANES * HVP);
@@ -748,24 +784,23 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
     pr_a = pr_b = f32x4{0.f, 0.f, 0.f, 0.f};
     // (both values per lane, selected at the store: a per-lane POINTER select is loop-invariant, 64 bits wide and was spilled)
     float aff_a = 0.f, aff_b = 0.f;
-    auto aff_load = [&](const StepPos& s) {
+    auto aff_load = [&](const StepPosY& s) {
         if (affine && tid < 64) { const size_t e = (size_t)s.n * p.Cin + s.cg * CG + (tid & 31); aff_a = p.in_scale[e]; aff_b = p.in_shift[e]; }
     };
     auto aff_store = [&]() { if (affine && tid < 64) aff[tid] = tid < 32 ? aff_a : aff_b; };
-    auto issue = [&](const StepPos& s, int k) {
+    auto issue = [&](const StepPosY& s, int k, const StageMap& m) {
         int v;      // (opaque: see conv_up2c_kernel)
         asm volatile("v_lshrrev_b32 %0, 2, %1\n\tv_add_u32 %0, %2, %0" : "=v"(v) : "v"(tid), "s"(128 * k));
-        if (v < NV) {
-            const int hx = v % HX, hy = (v / HX) % HY, hz = v / (HX * HY);
+        if (v < (MARCH ? m.nv : NV)) {
+            int hz, hy, hx; cell_of(v, m, hz, hy, hx);
             const int gz = min(max(s.cz0 - 1 + hz, 0), p.ID - 1), gy = min(max(s.cy0 - 1 + hy, 0), p.IH - 1), gx = min(max(s.cx0 - 1 + hx, 0), p.IW - 1);
             ld8_raw<false>(p.in, ((((size_t)s.n * p.ID + gz) * p.IH + gy) * p.IW + gx) * p.Cin + s.cg * CG + s_oct * 8, pr_a, pr_b);
         }
     };
-    auto commit = [&](half8* buf, int k) {
+    auto commit = [&](half8* buf, int k, const StageMap& m) {
         int v;
         asm volatile("v_lshrrev_b32 %0, 2, %1\n\tv_add_u32 %0, %2, %0" : "=v"(v) : "v"(tid), "s"(128 * k));
-        if (v < NV) {
-            const int hx = v % HX, hy = (v / HX) % HY, hz = v / (HX * HY);
+        if (v < (MARCH ? m.nv : NV)) {
             half8 hi, lo;
             f32x4 sca = {0.f, 0.f, 0.f, 0.f}, scb = sca, sha = sca, shb = sca;
             if (affine) {
@@ -773,19 +808,21 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
                 sha = *reinterpret_cast<const f32x4*>(aff + 32 + s_oct * 8); shb = *reinterpret_cast<const f32x4*>(aff + 32 + s_oct * 8 + 4);
             }
             split8(act4(pr_a, sca, sha, affine, p.in_slope), act4(pr_b, scb, shb, affine, p.in_slope), hi, lo);
-            const int slot = hz * ZP + hy * HX + hx;
+            int slot;
+            if constexpr (MARCH) slot = v + ((v * m.rcp) >> 16) * m.zs + m.y0 * HX;
+            else { int hz, hy, hx; cell_of(v, m, hz, hy, hx); slot = hz * ZP + hy * HX + hx; }
             buf[s_plane * HVP + slot] = hi;
             buf[(s_plane + 2) * HVP + slot] = lo;
         }
     };
     auto ldw = [&](const char* base, size_t extra) { return *reinterpret_cast<const half8*>(base + extra + wlane); };
 
-    // first tile: staged in the open
-    StepPos cs = pos_of(item0, 0, 0);
+    // first tile (a column's first brick, or any brick when not marching: all ten rows): staged in the open
+    StepPosY cs = pos_of(item0, 0, 0, 0);
     aff_load(cs); aff_store();
     lds_barrier();
 #pragma unroll
-    for (int k = 0; k < SITEMS; ++k) { issue(cs, k); commit(tile, k); }
+    for (int k = 0; k < SITEMS; ++k) { issue(cs, k, stage_map(false)); commit(tile, k, stage_map(false)); }
     lds_barrier();
     int cur = 0, item = item0;
     f32x4 acc[3][YT];
@@ -802,16 +839,24 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
 #pragma unroll
     for (int u = 0; u < NRING; ++u) { ah[u] = tile[abase + u * HX]; al[u] = tile[abase + u * HX + 2 * HVP]; }
     for (;;) {
-        StepPos ns = cs; bool have_next = true;
+        // step order: (item, output group, brick in the column, channel group) - the accumulators belong to one output group, so a
+        // column is marched once per group
+        StepPosY ns = cs; bool have_next = true;
         if (cs.cg + 1 < NCG) ns.cg = cs.cg + 1;
-        else if (cs.nh + 1 < NH) { ns.nh = cs.nh + 1; ns.cg = 0; }
-        else if (item + 1 < item_end) ns = pos_of(item + 1, 0, 0);
+        else if (MARCH && cs.iy + 1 < L) ns = pos_of(item, cs.iy + 1, cs.nh, 0);
+        else if (cs.nh + 1 < NH) ns = pos_of(item, 0, cs.nh + 1, 0);
+        else if (item + 1 < item_end) ns = pos_of(item + 1, 0, 0, 0);
         else have_next = false;
+        // a carried brick holds the products of its row tiles 0 and 1 already (its predecessor's tiles 8 and 9: the same cells, the
+        // same operands, the same MFMA chain) and runs the tiles 2 .. 9; the rows 0 and 1 of its LDS image are not staged and not read
+        const bool carried = MARCH && cs.iy > 0, ncarried = MARCH && have_next && ns.iy > 0;
+        const int coff = carried ? 2 * HX : 0, noff = ncarried ? 2 * HX : 0;       // first row tile of this / the next step
+        const StageMap nmap = stage_map(ncarried);
         if (cs.cg == 0) {
 #pragma unroll
             for (int ty = 0; ty < 3; ++ty)
 #pragma unroll
-                for (int j = 0; j < YT; ++j) acc[ty][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < YT; ++j) if (j >= 2 || !carried) acc[ty][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         const half8* tb = tile + cur * (NPLANES * HVP);
         half8* nb_ = tile + (cur ^ 1) * (NPLANES * HVP);
@@ -828,8 +873,8 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
             if (stage) {
 #pragma unroll
                 for (int i = 0; i < SITEMS; ++i) {
-                    if (t == 2 * i + 1) commit(nb_, i);
-                    if (t == 2 * i) issue(ns, i);
+                    if (t == 2 * i + 1) commit(nb_, i, nmap);
+                    if (t == 2 * i) issue(ns, i, nmap);
                 }
             }
             // B operands of the next k-step - requested BEHIND the staging code (see conv_up2c_x16_kernel)
@@ -846,10 +891,12 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
             UP2C_SB();
 #pragma unroll
             for (int j = 0; j < YT; ++j) {
+                if (j < 2 && carried) continue;                            // (wave-uniform)
                 const int rs = (YT * t + j) % NRING;
+                // the slot's next tile: two on, or the first (+ j - 8) tile of the next tap / of the next step's buffer
                 const int jn = (j + NRING) % YT, tn = t + (j + NRING) / YT;
                 const half8* xb = (tn == KS) ? nb_ : tb;
-                const int nof = (tn == KS) ? 0 : (tn / 3) * ZP + (tn % 3);
+                const int nof = ((tn == KS) ? 0 : (tn / 3) * ZP + (tn % 3)) + (tn == t ? 0 : (tn == KS ? noff : coff));
 #pragma unroll
                 for (int ty = 0; ty < 3; ++ty) acc[ty][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rs], b2k[ty], acc[ty][j], 0, 0, 0);
                 UP2C_SB();
@@ -881,11 +928,24 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
                 for (int i = 0; i < BY; ++i) {
                     const int oy = 2 * (cs.cy0 + i) + py;
                     float* base = p.out + ((((size_t)cs.n * OD + oz) * OH + oy) * OW + 2 * (cs.cx0 + 4 * (q & 1)) + px) * sX + co;
-                    const bool zy = zshell || oy == 0 || oy == OH - 1;
+                    // zero padding of the fine conv along y: the fine tap that leaves the volume is left out (the remaining terms are
+                    // torch's clamped interpolation: the halo tile is staged with clamped indices)
+                    const bool ytop = p.ypad && oy == 0, ybot = p.ypad && oy == OH - 1;
+                    const bool zy = zshell || (!p.ypad && (oy == 0 || oy == OH - 1));
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float v;
-                        if (py == 0) {
+                        if (py == 0 && i == 0 && ytop) {
+                            v = C1 * acc[1][i][r];
+                            v = __builtin_fmaf(C3, acc[1][i + 1][r], v);
+                            v = __builtin_fmaf(C3, acc[2][i + 1][r], v);
+                            v = __builtin_fmaf(C1, acc[2][i + 2][r], v);
+                        } else if (py == 1 && i == BY - 1 && ybot) {
+                            v = C1 * acc[0][i][r];
+                            v = __builtin_fmaf(C3, acc[0][i + 1][r], v);
+                            v = __builtin_fmaf(C3, acc[1][i + 1][r], v);
+                            v = __builtin_fmaf(C1, acc[1][i + 2][r], v);
+                        } else if (py == 0) {
                             v = C3 * acc[0][i][r];
                             v = __builtin_fmaf(C1, acc[0][i + 1][r], v);
                             v = __builtin_fmaf(C1, acc[1][i][r], v);
@@ -917,16 +977,21 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
                     if (q == 0) { float* dst = p.part + (((size_t)cs.n * p.nblk + cs.br * 8 + cls * 2 + py) * p.Cout + co) * 2; dst[0] = s; dst[1] = ss; }
                 }
             }
+            if (ncarried) {
+#pragma unroll
+                for (int ty = 0; ty < 3; ++ty) { acc[ty][0] = acc[ty][YT - 2]; acc[ty][1] = acc[ty][YT - 1]; }
+            }
         }
         if (!have_next) break;
-        if (ns.cg == 0 && ns.nh == 0) ++item;
+        if (ns.cg == 0 && ns.nh == 0 && ns.iy == 0) ++item;
         cs = ns; cur ^= 1;
     }
 }
 
 // ---- shell kernels -----------------------------------------------------------------------------------------------------------
 // Ownership of the shell cells (per parity class): a cell on two or three faces belongs to an EDGE item, every other shell cell to
-// the FACE item of its face.  A face cell needs one correction set (S = its face's axis, 9 coarse taps); the cells of an edge need
+// the FACE item of its face (with conv_up2y_kernel padding along y, p.ypad: the y-face items own nothing, write empty partial slots
+// and leave; the edge items skip the set S = {y}).  A face cell needs one correction set (S = its face's axis, 9 coarse taps); the cells of an edge need
 // three (two faces - their common taps), a corner seven.
 //
 // conv_up2c_face_kernel: one workgroup = one line of 32 cells on a face (along y on the x faces, along x on the y and z faces);
@@ -953,6 +1018,12 @@ __global__ __launch_bounds__(256, 4) void conv_up2c_face_kernel(Up2cParams p, in
     if (q < nX) { type = 0; tl = q % TY; f = (q / TY) % p.ID; side = q / (TY * p.ID); }
     else if (q < nX + nY) { q -= nX; type = 1; tl = q % TX; f = (q / TX) % p.ID; side = q / (TX * p.ID); }
     else { q -= nX + nY; type = 2; tl = q % TX; f = (q / TX) % p.IH; side = q / (TX * p.IH); }
+    if (p.ypad && type == 1) {
+        // the main kernel (conv_up2y_kernel) has padded along y itself and counted these voxels: nothing to add, empty partial slots
+        if (p.part && lane < 32)
+            for (int co = lane; co < p.Cout; co += 32) { float* dst = p.part + (((size_t)n * p.nblk + slot_part) * p.Cout + co) * 2; dst[0] = 0.f; dst[1] = 0.f; }
+        return;
+    }
     const int LA = type == 0 ? p.IH : p.IW;                            // cells along the line's axis
     const int AC = type == 2 ? p.IH : p.ID;                            // extent of the across axis
     const int fb = side ? (type == 0 ? p.IW : type == 1 ? p.IH : p.ID) - 1 : 0;      // the face's coarse index on its own axis
@@ -1081,6 +1152,7 @@ __global__ __launch_bounds__(256, 4) void conv_up2c_edge_kernel(Up2cParams p, in
         for (int S = 1; S < 8; ++S) {
             const bool rowon = owned && (bset & S) == S;
             if (__ballot(rowon) == 0ull) continue;                     // wave-uniform
+            if (p.ypad && S == 2) continue;                            // {y} alone: left out by the main kernel's epilogue already
             const int e = 8 + (S - 1) * 8 + par;
             const int ntaps = axes_taps(S);
             const half8* wq = p.wc + (size_t)set_tap_offset(e) * C16 * kstride + (size_t)h * plane + nh * 32 + l31;
@@ -1188,7 +1260,8 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_up2c)");
         attr_set.mark();
     }
@@ -1212,12 +1285,21 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     p.nblk = nm_up2c_blocks_per_frame(in.D, in.H, in.W);
     p.diag = nm_ls().up2c_diag;
     const int bricks = p.nbz * p.nby * p.nbx, total = p.N * bricks;
+    // conv_up2y_kernel: whole columns of bricks along y per workgroup where that leaves no CU without one (NM355_UP2Y_MARCH=2: always),
+    // zero padding along y in its epilogue (NM355_UP2Y_YPAD)
+    const bool y_main = io == 0 && !single && nm_ls().up2y;
+    const int columns = p.N * p.nbz * p.nbx;
+    // row tiles of the busiest workgroup: 10 per brick, or 10 + 8 (nby - 1) per column
+    const long long tiles_bricks = (long long)((total + g_cus - 1) / g_cus) * YT, tiles_columns = (long long)((columns + g_cus - 1) / g_cus) * (YT + (YT - 2) * (p.nby - 1));
+    p.march = y_main && p.nby > 1 && (nm_ls().up2y_march >= 2 || (nm_ls().up2y_march == 1 && columns >= g_cus && tiles_columns < tiles_bricks));
+    p.ypad = y_main && nm_ls().up2y_ypad != 0;
     if (io == 3) hipLaunchKernelGGL((conv_up2c_kernel<true, 3>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (io == 2) hipLaunchKernelGGL((conv_up2c_kernel<true, 2>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (io == 1) hipLaunchKernelGGL((conv_up2c_kernel<true, 1>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     // (the one-product modes keep the 32x32x16 kernel in fp32 storage too: their bfloat16-storage instantiations are bit-compared with
     //  it, tests/test_storage16_gpu.py; NM355_UP2C_X16=2 forces the 16x16x32 form there as well - A/B)
-    else if (!single && nm_ls().up2y) hipLaunchKernelGGL(conv_up2y_kernel, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
+    else if (y_main && p.march) hipLaunchKernelGGL(conv_up2y_kernel<true>, dim3((unsigned)min(columns, g_cus)), dim3(512), LDS_BYTES, s, p);
+    else if (y_main) hipLaunchKernelGGL(conv_up2y_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (nm_ls().up2c_x16 >= 2 && single) hipLaunchKernelGGL(conv_up2c_x16_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (nm_ls().up2c_x16 && !single) hipLaunchKernelGGL(conv_up2c_x16_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
     else if (single) hipLaunchKernelGGL(conv_up2c_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
