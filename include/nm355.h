@@ -293,6 +293,38 @@ int nm_vrnn_step(nm_ctx* ctx, int32_t posterior, const float* h_in, const float*
 int nm_rows_argmin_dist(nm_ctx* ctx, const float* rows, const float* target, int32_t target_row_stride,
                         int32_t B, int32_t D, int32_t* idx_out, float* dist_out);
 
+/* ---- motion retargeting (vis_retarget.py of the reference, the computation between its two detector calls and its first render) ----
+ * Bind a target point cloud to the skeleton once, then pose it for T frames.  All three calls use the tree of nm_vrnn_set_tree
+ * (parents, order, root = order[0]) and fail with NM_ERR_STATE when none is set, NM_ERR_ARG when K is not the context's nkeypoints or
+ * N < 1 / T < 1.  Point data is float64 like the reference's numpy points; `w`, `local` and `out` must be 16-byte aligned.  Results are
+ * bit-identical from run to run (no atomics).
+ *
+ * nm_retarget_bind - extract_skin_weights (vis_retarget.py:21-62) and the local coordinates of :268-270 in one pass over the points.
+ *   points (N,3) float64, keypoints (K,4) fp32, R_bind (K,3,3) fp32 or NULL (identity), force_child (N) int32 or NULL: imposes the
+ *   selection (values in [0,K): the caller checks; `margin` is still the free selection's).
+ *   child (N) int32 = the joint whose bone point is nearest (first minimum), parent (N) int32 = parents[child] of the ORIGINAL tree,
+ *   w (N,2) fp32 = weight of the child joint, weight of the parent joint, local (N,2,3) float64 = R_bind[j]^T (p - pos_j) for
+ *   j = child, parent, margin (N) float64 or NULL = second-smallest minus smallest bone distance, dense (N,K) fp32 or NULL = the
+ *   reference's matrix.  Operation by operation as the reference: invalid[k] = intensity_k < (float)threshold in fp32; bone point of
+ *   joint k in fp32 = the joint for the root, else (pos_k + pos_a) / 2 with a the nearest ancestor that is not invalid; distances in
+ *   float64, sqrt((dx dx + dy dy) + dz dz); invalid joints and the root take the distance VALUE 1e4; c = exp(hardness |p - pos_child|),
+ *   q = exp(hardness |p - pos_parent|), w_child = (float)(q / (c + q)), w_parent = (float)(c / (c + q)).  When the root is chosen
+ *   (every joint masked) parent == child: the reference's second assignment overwrites the first, so the dense row holds w_child alone
+ *   and w_parent is written as 0.
+ *   The ancestor walk STOPS AT THE ROOT even when the root is invalid, after at most K steps: the reference's loop (:41-42) does not
+ *   terminate in that case (parents[root] == root), so this is the library's own choice, not a reference behaviour.
+ * nm_retarget_fk - the re-posing loop of :275-300: R (T,K,3,3), root_pos (T,3), offset (K,3) [nm_vrnn_offsets] -> pos (T,K,3):
+ *   pos[root] = root_pos, pos[j] = R[j] offset[j] + pos[parents[j]] in `order`, fp32, then clipped to [-1, 1].
+ * nm_retarget_pose - the blend of :303-322 on the bind record: out (T,N,3) float64,
+ *   out[t,n] = w_child (R[t,child] local_child + pos[t,child]) + w_parent (R[t,parent] local_parent + pos[t,parent]); the parent term is
+ *   0 when parent == child. */
+int nm_retarget_bind(nm_ctx* ctx, const double* points, int64_t N, const float* keypoints, const float* R_bind, int32_t K, double hardness,
+                     double threshold, const int32_t* force_child, int32_t* child, int32_t* parent, float* w, double* local,
+                     double* margin, float* dense);
+int nm_retarget_fk(nm_ctx* ctx, const float* R, const float* root_pos, const float* offset, int32_t T, int32_t K, float* pos);
+int nm_retarget_pose(nm_ctx* ctx, const int32_t* child, const int32_t* parent, const float* w, const double* local, const float* R,
+                     const float* pos, int32_t T, int64_t N, int32_t K, double* out);
+
 /* Sub-module callables the reference's demo scripts reach into (hsvrnn_bvh.py:29-57):
  *  which: 0 extract_post_dist (H+K*4 -> 2Z), 1 extract_prior_dist (H -> 2Z),
  *         2 root_intensity_decoder (H+Z -> 3+K, tanh), 3 joint_matrix_decoder (H+Z -> 6K) */

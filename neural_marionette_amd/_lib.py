@@ -78,6 +78,9 @@ SIGNATURES = {
     "nm_vrnn_rollout": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _P, _P]),
     "nm_vrnn_step": (C.c_int, [C.c_void_p, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "nm_rows_argmin_dist": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
+    "nm_retarget_bind": (C.c_int, [C.c_void_p, _P, C.c_int64, _P, _P, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "nm_retarget_fk": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _P]),
+    "nm_retarget_pose": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, _P, _I, C.c_int64, _I, _P]),
     "nm_vrnn_mlp": (C.c_int, [C.c_void_p, _I, _P, _I, _P]),
     "nm_vrnn_gru": (C.c_int, [C.c_void_p, _P, _P, _I, _P]),
     "nm_vrnn_fk": (C.c_int, [C.c_void_p, _P, _P, _I, _P, _P]),

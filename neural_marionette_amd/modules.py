@@ -494,6 +494,30 @@ class HSVRNNBVH(nn.Module):
             self._eng().call("nm_vrnn_set_tree", par.ctypes.data_as(_lib.c_int32_p), order.ctypes.data_as(_lib.c_int32_p))
             object.__setattr__(self, "_tree_key", key)
 
+    def set_tree(self, parents, order, A=None) -> None:
+        """Install a skeleton directly instead of deriving it from an affinity in the first encode(): parents (K) with
+        parents[root] == root, order (K) = the joints in kinematic order, root first (what ``priority.indices`` holds); A (K,K) is kept
+        as given (default: the tree's adjacency).  The library checks that every joint's parent precedes it.  ``priority.values`` is
+        then only a placeholder (0 .. K-1 in kinematic order): the distances the reference's topk returns exist only for a tree derived
+        from an affinity, and nothing in the library reads them."""
+        ctx = self._eng().ready()
+        dev, K = ctx.device, self.nkeypoints
+        par = torch.as_tensor(np.asarray(parents).astype(np.int64))
+        ordr = torch.as_tensor(np.asarray(order).astype(np.int64))
+        if tuple(par.shape) != (K,) or tuple(ordr.shape) != (K,):
+            raise ValueError(f"parents and order must be ({K},), got {tuple(par.shape)} and {tuple(ordr.shape)}")
+        if A is None:
+            A = torch.zeros(K, K)
+            k = torch.arange(K)
+            A[k, par] = 1
+            A[par, k] = 1
+            A[k, k] = 0
+        self.A = torch.as_tensor(A).float().to(dev)
+        self.priority = Priority(values=torch.arange(K, dtype=torch.float64, device=dev), indices=ordr.to(dev))
+        self.parents = par.to(dev)
+        object.__setattr__(self, "_tree_key", None)
+        self._ensure_tree(None, ctx)
+
     def _eps(self, n, shape, dev, eps):
         if eps is not None:
             # the library reads n * prod(shape) floats: a smaller tensor (e.g. S samples of noise for SAMPLE_NUM > S) is an
@@ -631,6 +655,83 @@ class HSVRNNBVH(nn.Module):
         eng.call("nm_rows_argmin_dist", _lib.ptr(r), _lib.ptr(t), 0 if t.shape[0] == 1 else int(r.shape[1]),
                  int(r.shape[0]), int(r.shape[1]), _lib.ptr(idx), None)
         return int(idx.item())
+
+    # -- motion retargeting (vis_retarget.py of the reference; nm_retarget.hip) ---------------------------------------------
+    def skin_weights(self, points, keypoints, R_bind=None, hardness=8.0, threshold=0.2, force_child=None):
+        """extract_skin_weights (vis_retarget.py:21-62) and the local coordinates of :268-270, one pass over the points on the device.
+        points (N,3) [float64 arithmetic, as the reference's numpy points], keypoints (K,4), R_bind (K,3,3) or None (identity: the local
+        coordinates are plain offsets).  ``force_child`` (N) imposes the nearest-bone selection (``margin`` stays the free one).
+        Returns child (N) int32, parent (N) int32, w (N,2) [child joint, parent joint], local (N,2,3) float64, margin (N) float64
+        [second-smallest minus smallest bone distance] and dense (N,K) = what the reference's function returns.  Needs the tree."""
+        eng = self._eng()
+        ctx = eng.ready()
+        self._ensure_tree(None, ctx)
+        dev, K = ctx.device, self.nkeypoints
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise ValueError(f"points must be (N,3) with N >= 1, got {tuple(points.shape)}")
+        if tuple(keypoints.shape) != (K, 4):
+            raise ValueError(f"keypoints must be ({K},4), got {tuple(keypoints.shape)}")
+        if R_bind is not None and tuple(R_bind.shape) != (K, 3, 3):
+            raise ValueError(f"R_bind must be ({K},3,3), got {tuple(R_bind.shape)}")
+        N = int(points.shape[0])
+        force = None
+        if force_child is not None:
+            if tuple(force_child.shape) != (N,):
+                raise ValueError(f"force_child must be ({N},), got {tuple(force_child.shape)}")
+            force = force_child.detach().to(device=dev, dtype=torch.int32).contiguous()
+            if int(force.min()) < 0 or int(force.max()) >= K:
+                raise ValueError(f"force_child must hold joint indices in [0,{K})")
+        pts = points.detach().to(device=dev, dtype=torch.float64).contiguous()
+        kp = _f32(keypoints, dev)
+        rb = None if R_bind is None else _f32(R_bind, dev)
+        child = torch.empty(N, device=dev, dtype=torch.int32)
+        parent = torch.empty(N, device=dev, dtype=torch.int32)
+        w = torch.empty(N, 2, device=dev)
+        local = torch.empty(N, 2, 3, device=dev, dtype=torch.float64)
+        margin = torch.empty(N, device=dev, dtype=torch.float64)
+        dense = torch.empty(N, K, device=dev)
+        eng.call("nm_retarget_bind", _lib.ptr(pts), N, _lib.ptr(kp), _lib.ptr(rb), K, float(hardness), float(threshold), _lib.ptr(force),
+                 _lib.ptr(child), _lib.ptr(parent), _lib.ptr(w), _lib.ptr(local), _lib.ptr(margin), _lib.ptr(dense))
+        return dict(child=child, parent=parent, w=w, local=local, margin=margin, dense=dense)
+
+    def retarget_fk(self, R, root_pos, offset):
+        """The re-posing loop of vis_retarget.py:275-300: R (T,K,3,3), root_pos (T,3), offset (K,3[,1]) -> joint positions (T,K,3), forward
+        kinematics along the tree in fp32, clipped to [-1,1]."""
+        eng = self._eng()
+        ctx = eng.ready()
+        self._ensure_tree(None, ctx)
+        dev, K = ctx.device, self.nkeypoints
+        T = int(R.shape[0]) if R.dim() == 4 else -1
+        if T < 1 or tuple(R.shape) != (T, K, 3, 3):
+            raise ValueError(f"R must be (T,{K},3,3) with T >= 1, got {tuple(R.shape)}")
+        if tuple(root_pos.shape) != (T, 3):
+            raise ValueError(f"root_pos must be ({T},3), got {tuple(root_pos.shape)}")
+        if offset.numel() != K * 3 or offset.shape[0] != K:
+            raise ValueError(f"offset must be ({K},3) or ({K},3,1), got {tuple(offset.shape)}")
+        pos = torch.empty(T, K, 3, device=dev)
+        eng.call("nm_retarget_fk", _lib.ptr(_f32(R, dev)), _lib.ptr(_f32(root_pos, dev)), _lib.ptr(_f32(offset.reshape(K, 3), dev)), T, K, _lib.ptr(pos))
+        return pos
+
+    def retarget_pose(self, bind, R, pos):
+        """The blend of vis_retarget.py:303-322 on a bind record (the dict of skin_weights): R (T,K,3,3), pos (T,K,3) -> points (T,N,3)
+        float64, out[t,n] = w_child (R[t,child] local_child + pos[t,child]) + w_parent (R[t,parent] local_parent + pos[t,parent])."""
+        eng = self._eng()
+        ctx = eng.ready()
+        self._ensure_tree(None, ctx)
+        dev, K = ctx.device, self.nkeypoints
+        T = int(R.shape[0]) if R.dim() == 4 else -1
+        if T < 1 or tuple(R.shape) != (T, K, 3, 3) or tuple(pos.shape) != (T, K, 3):
+            raise ValueError(f"R must be (T,{K},3,3) and pos (T,{K},3) with T >= 1, got {tuple(R.shape)} and {tuple(pos.shape)}")
+        N = int(bind["child"].shape[0])
+        want = dict(child=((N,), torch.int32), parent=((N,), torch.int32), w=((N, 2), torch.float32), local=((N, 2, 3), torch.float64))
+        for k, (shape, dtype) in want.items():
+            if N < 1 or tuple(bind[k].shape) != shape or bind[k].dtype != dtype:
+                raise ValueError(f"bind['{k}'] must be {shape} {dtype}, got {tuple(bind[k].shape)} {bind[k].dtype}")
+        rec = {k: bind[k].detach().to(dev).contiguous() for k in want}
+        out = torch.empty(T, N, 3, device=dev, dtype=torch.float64)
+        eng.call("nm_retarget_pose", _lib.ptr(rec["child"]), _lib.ptr(rec["parent"]), _lib.ptr(rec["w"]), _lib.ptr(rec["local"]),
+                 _lib.ptr(_f32(R, dev)), _lib.ptr(_f32(pos, dev)), T, N, K, _lib.ptr(out))
+        return out
 
 
 # ==========================================================================================
@@ -776,6 +877,52 @@ class NeuralMarionette(nn.Module):
         sel[0, :, :, -1] = sel[0, 0, :, -1]
         vox = self.kypt_detector.decode_from_dyna(sel, det["first_feature"], target_voxel[None, 0].to(dev))["gen"][0]
         return dict(keypoints=sel, voxels=(vox >= 0.5).float(), voxels_raw=vox, picks=picks)
+
+    @torch.no_grad()
+    def sample_retarget(self, source_voxel, target_voxel, target_points, hardness=8.0, threshold=0.2, eps_source=None, eps_target=None,
+                        force_nearest=None):
+        """vis_retarget.py:236-322 (its 'ours' branch, the one the script takes): the motion of ``source_voxel`` (T,1,G,G,G) carried over to
+        the shape ``target_voxel`` (1,G,G,G) whose points ``target_points`` (N,3) are skinned to the skeleton.  Detector on the source
+        clip, every frame's intensity replaced by frame 0's, encode (best-of-10, noise eps_source (T,10,1,Z)) -> R; detector on the
+        target frame, its keypoints take the source's frame-0 intensities, encode (eps_target (1,10,1,Z)) -> R_bind; get_offset of the
+        target; bind (skin_weights); forward kinematics with the source's root trajectory; pose.  ``force_nearest`` (N) replaces the
+        nearest-bone selection (teacher forcing in tests).  Mesh loading and rendering are the caller's.
+        Returns source_keypoints (1,T,K,4), target_keypoints (1,1,K,4), R (T,K,3,3), R_bind (K,3,3), offset (1,K,3,1), keypoints
+        (1,T,K,4) [retargeted], skin_weights (N,K), nearest (N), nearest_margin (N) and points (T,N,3) float64."""
+        _need_graph(self._engine.opts, "NeuralMarionette.sample_retarget")
+        d = self.dyna_module
+        G, K, Z, S = self._engine.opts.grid_size, d.nkeypoints, d.nlatent_kypt, 10
+        if source_voxel.dim() != 5 or tuple(source_voxel.shape[1:]) != (1, G, G, G) or source_voxel.shape[0] < 1:
+            raise ValueError(f"source_voxel must be (T,1,{G},{G},{G}) with T >= 1, got {tuple(source_voxel.shape)}")
+        T = int(source_voxel.shape[0])
+        if tuple(target_voxel.shape) != (1, G, G, G):
+            raise ValueError(f"target_voxel must be (1,{G},{G},{G}), got {tuple(target_voxel.shape)}")
+        if target_points.dim() != 2 or target_points.shape[1] != 3 or target_points.shape[0] < 1:
+            raise ValueError(f"target_points must be (N,3) with N >= 1, got {tuple(target_points.shape)}")
+        N = int(target_points.shape[0])
+        for name, e, want in (("eps_source", eps_source, (T, S, 1, Z)), ("eps_target", eps_target, (1, S, 1, Z))):
+            if e is not None and tuple(e.shape) != want:
+                raise ValueError(f"{name} must be {want}, got {tuple(e.shape)}")
+        if force_nearest is not None and tuple(force_nearest.shape) != (N,):
+            raise ValueError(f"force_nearest must be ({N},), got {tuple(force_nearest.shape)}")
+        det = self.kypt_detector.detect(source_voxel[None])
+        if det["affinity"] is None:
+            raise _lib.NmError("NeuralMarionette.sample_retarget: the detector returns no affinity yet - call anneal() first (vis_retarget.py:237)")
+        src = det["keypoints"].clone()
+        src[..., 3] = src[:, :1, :, 3].clone()                        # every frame carries frame 0's intensities (vis_retarget.py:242)
+        R = d.encode(src, det["affinity"], SAMPLE_NUM=S, eps=eps_source)["R"][0]
+        tgt = self.kypt_detector.detect(target_voxel[None, None])["keypoints"]
+        tgt = tgt.clone()
+        tgt[..., 3] = src[:, :1, :, 3]                              # the target's joints take the source's frame-0 intensities (:260)
+        R_bind = d.encode(tgt, det["affinity"], SAMPLE_NUM=S, eps=eps_target)["R"][0, 0]
+        offset = d.get_offset(tgt)
+        bind = d.skin_weights(target_points, tgt[0, 0], R_bind, hardness=hardness, threshold=threshold, force_child=force_nearest)
+        root = int(d.priority.indices[0])
+        pos = d.retarget_fk(R, src[0, :, root, :3], offset[0])
+        new_kp = torch.cat([pos[None], src[..., 3:]], dim=-1)
+        points = d.retarget_pose(bind, R, pos)
+        return dict(source_keypoints=src, target_keypoints=tgt, R=R, R_bind=R_bind, offset=offset, keypoints=new_kp,
+                    skin_weights=bind["dense"], nearest=bind["child"], nearest_margin=bind["margin"], points=points)
 
     def control_active(self, module_actives):
         """neural_marionette.py:22-32."""
