@@ -156,6 +156,13 @@ int nm_ctx_set_gaussian_cat(nm_ctx* ctx, int32_t cat);
  * decode_from_dyna does), and the backward writes that parameter's gradient.  Call before nm_ctx_set_weights.  Not implemented together
  * with vol_fit_type 'gaussian' (NM_ERR_UNSUPPORTED). */
 int nm_ctx_set_learnable_sigma(nm_ctx* ctx, int32_t on);
+/* options.const_intensity (model/kypt_detector.py:308-347): 3 (default, every shipped configuration) - every frame's heat-map is propagated
+ * from the clip's spatio-temporal heat-map - or 2 - frame t >= 1 is propagated from the heat-map of frame t - 1 (:344-345), frame 0 as
+ * under 3; forward (nm_detector_forward*, nm_detector_keypoints, nm_forward_fused) and backward (the reverse scan over the clip's frames;
+ * the spatio-temporal head hears from frame 0 alone).  The two values share modules, state_dict and weights: takes effect at the next
+ * call, no new nm_ctx_set_weights.  0 (no spatio-temporal net: another weight table), 1 (the initial_heatmaps parameter) and 4 are
+ * NM_ERR_UNSUPPORTED - the value is judged before the context, so a null context with an unsupported value reports that. */
+int nm_ctx_set_const_intensity(nm_ctx* ctx, int32_t v);
 /* options.graph_loss_ver, keypoints_detach, using_local_const, using_time_const, using_sparsity_const and keypoints_graph
  * (model/kypt_detector.py:20-30,54-68,112-143; utils/kypt_detector_utils.py:172-265).  ver: 1 (default) or 0 / 2 - the local, time and
  * trajectory terms weighted by the keypoint intensity of the first index (ver 2 also symmetrises the influence, M + M^T); the intensity

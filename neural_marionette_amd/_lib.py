@@ -56,6 +56,7 @@ SIGNATURES = {
     "nm_ctx_set_affinity_ver": (C.c_int, [C.c_void_p, _I]),
     "nm_ctx_set_gaussian_cat": (C.c_int, [C.c_void_p, _I]),
     "nm_ctx_set_learnable_sigma": (C.c_int, [C.c_void_p, _I]),
+    "nm_ctx_set_const_intensity": (C.c_int, [C.c_void_p, _I]),
     "nm_ctx_set_graph_loss": (C.c_int, [C.c_void_p, _I, _I]),
     "nm_voxelize_clip": (C.c_int, [C.c_void_p, _P, _I, C.c_int64, C.c_double, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),

@@ -117,6 +117,7 @@ struct nm_ctx {
     int gauss_cat = 0;                     // options.gaussian_cat_type (kypt_detector.py:396-401): 0 'none', 1 'max', 2 'sum' (nm_ctx_set_gaussian_cat)
     int affinity_ver = 3;                  // get_affinity version (kypt_detector.py:171-210): 3 = the shipped configurations; 0 / 1 / 2 by nm_ctx_set_affinity_ver
     int graph_loss_ver = 1;                // options.graph_loss_ver (kypt_detector_utils.py:172-265): 1 = the shipped configurations; 0 / 2 by nm_ctx_set_graph_loss
+    int const_intensity = 3;               // options.const_intensity (kypt_detector.py:308-347): 3 = the shipped configurations; 2 (recurrent heat-maps) by nm_ctx_set_const_intensity
     int graph_flags = 0;                   // NM_GRAPH_* switches of include/nm355.h (0: every graph term on, keypoints attached, 'affinity_params')
     bool graph_none() const { return (graph_flags & NM_GRAPH_NONE) != 0; }
     int64_t affinity_numel() const {

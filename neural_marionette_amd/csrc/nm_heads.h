@@ -4,6 +4,9 @@
 
 int nm_launch_heatmap(const float* head, const float* clip_head, const float* prop, int F, int T, int K, int Kc /* channels per voxel of head / clip_head (>= K, % 4 == 0) */, int g,
                       float* heatmaps, float* part, hipStream_t s);
+// const_intensity 2 (kypt_detector.py:344-345): frame t propagated from the heat-map of frame t - 1; same outputs as nm_launch_heatmap
+int nm_launch_heatmap_recurrent(const float* head, const float* clip_head, const float* prop, int B, int T, int K, int Kc, int g,
+                                float* heatmaps, float* part, hipStream_t s);
 int nm_launch_keypoints(const float* part, int F, int K, int g, float* keypoints, float* heat_mean, hipStream_t s);
 int nm_launch_gauss_table(const float* keypoints, int FK, int g, float width, float* table, hipStream_t s,
                           const float* widthk = nullptr /* [K]: per-keypoint widths (fixed_sigma = 0) */, int K = 0);

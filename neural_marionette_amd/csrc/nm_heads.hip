@@ -2,6 +2,7 @@
 //
 //   heatmap_kernel      1x1 head outputs -> LeakyReLU -> propagate(2->1) -> Softplus, heat-maps in
 //                       NCDHW + per-plane marginal partial sums       (kypt_detector.py:336-343)
+//   heat_scan_kernel + heat_marginals_kernel  the same with frame t propagated from frame t - 1 (const_intensity 2, kypt_detector.py:344-345)
 //   keypoints_kernel    marginals -> (x1,x2,x3,intensity)             (kypt_detector_utils.py:28-55)
 //   gauss_table_kernel  separable 1-D gaussians per (frame, keypoint) (kypt_detector_utils.py:57-90)
 //   combined_kernel     [gauss_t | first_feature | gauss_0 | coords]  (kypt_detector.py:406-407)
@@ -37,33 +38,10 @@ __device__ __forceinline__ float block_sum256(float v, float* sh) {
     return r;
 }
 
-// grid (F, g): one z-plane of one frame.  LDS: K * g * g floats.
-// head / clip_head rows hold Kc = K rounded up to 8 channels per voxel (the heads run zero-padded for keypoint counts that are not
-// multiples of 8): channels >= K are read with the quad they share and dropped.
-__global__ __launch_bounds__(256) void heatmap_kernel(const float* __restrict__ head, const float* __restrict__ clip_head,
-                                                      const float* __restrict__ prop, int T, int K, int Kc, int g,
-                                                      float* __restrict__ heatmaps, float* __restrict__ part) {
-    extern __shared__ float tile[];                       // [K][g*g]
-    const int f = blockIdx.x, z = blockIdx.y, b = f / T;
-    const int g2 = g * g, g3 = g2 * g;
-    const float w0 = prop[0], w1 = prop[1], pb = prop[2];
-    for (int v = threadIdx.x; v < g2; v += 256) {
-        const size_t vox = (size_t)z * g2 + v;
-        const float* hp = head + ((size_t)f * g3 + vox) * Kc;
-        const float* cp = clip_head + ((size_t)b * g3 + vox) * Kc;
-        for (int k = 0; k < K; k += 4) {
-            f32x4 a = *reinterpret_cast<const f32x4*>(hp + k);
-            f32x4 c = *reinterpret_cast<const f32x4*>(cp + k);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (k + j >= K) break;
-                float hm = softplus(w0 * lrelu(a[j], 0.01f) + w1 * lrelu(c[j], 0.01f) + pb);
-                heatmaps[((size_t)f * K + k + j) * g3 + vox] = hm;
-                tile[(k + j) * g2 + v] = hm;
-            }
-        }
-    }
-    __syncthreads();
+// Marginal partial sums of one z-plane of one frame's K heat-maps (tile: [K][g*g] in LDS, complete and visible to the block) into the
+// frame's `part` record; every thread of the 256-thread block calls it.
+__device__ __forceinline__ void heat_plane_marginals(const float* tile, int f, int z, int K, int g, float* __restrict__ part) {
+    const int g2 = g * g;
     // Marginal sums of the plane by WAVEFRONT SHUFFLES (BASELINE north_star: "wavefront shuffles for the ... keypoint heatmap
     // reduction"): wave w takes the keypoints k = w, w + 4, ...; a plane row lives in a group of GP lanes (GP = 8 / 16 / 32 >= g), 64 / GP
     // rows per pass.  Row y: sum over x of (hm + 1e-6) - an xor butterfly inside the group; column x: every lane adds its rows in
@@ -96,6 +74,76 @@ __global__ __launch_bounds__(256) void heatmap_kernel(const float* __restrict__ 
         for (int off = 32; off > 0; off >>= 1) { tot += nm_sx(tot, off); tot6 += nm_sx(tot6, off); }
         if (lane == 0) { dst[2 * g] = tot; dst[2 * g + 1] = tot6; }
     }
+}
+
+// grid (F, g): one z-plane of one frame.  LDS: K * g * g floats.
+// head / clip_head rows hold Kc = K rounded up to 8 channels per voxel (the heads run zero-padded for keypoint counts that are not
+// multiples of 8): channels >= K are read with the quad they share and dropped.
+__global__ __launch_bounds__(256) void heatmap_kernel(const float* __restrict__ head, const float* __restrict__ clip_head,
+                                                      const float* __restrict__ prop, int T, int K, int Kc, int g,
+                                                      float* __restrict__ heatmaps, float* __restrict__ part) {
+    extern __shared__ float tile[];                       // [K][g*g]
+    const int f = blockIdx.x, z = blockIdx.y, b = f / T;
+    const int g2 = g * g, g3 = g2 * g;
+    const float w0 = prop[0], w1 = prop[1], pb = prop[2];
+    for (int v = threadIdx.x; v < g2; v += 256) {
+        const size_t vox = (size_t)z * g2 + v;
+        const float* hp = head + ((size_t)f * g3 + vox) * Kc;
+        const float* cp = clip_head + ((size_t)b * g3 + vox) * Kc;
+        for (int k = 0; k < K; k += 4) {
+            f32x4 a = *reinterpret_cast<const f32x4*>(hp + k);
+            f32x4 c = *reinterpret_cast<const f32x4*>(cp + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (k + j >= K) break;
+                float hm = softplus(w0 * lrelu(a[j], 0.01f) + w1 * lrelu(c[j], 0.01f) + pb);
+                heatmaps[((size_t)f * K + k + j) * g3 + vox] = hm;
+                tile[(k + j) * g2 + v] = hm;
+            }
+        }
+    }
+    __syncthreads();
+    heat_plane_marginals(tile, f, z, K, g, part);
+}
+
+// const_intensity 2 (kypt_detector.py:344-345, `prev_heatmap = heatmap`): frame t is propagated from the heat-map of frame t - 1, frame 0
+// from the clip's spatio-temporal heat-map.  The recurrence is pointwise, so the scan runs fully parallel over (clip, voxel, channel quad) -
+// thread (q, vox), vox fastest: the NCDHW stores of a wave are 64 consecutive floats - and every thread walks its T frames with the
+// previous values in registers.  Frame 0 is the arithmetic of heatmap_kernel expression for expression.  grid (ceil(g^3 K4 / 256), B),
+// K4 = ceil(K / 4).
+__global__ __launch_bounds__(256) void heat_scan_kernel(const float* __restrict__ head, const float* __restrict__ clip_head,
+                                                        const float* __restrict__ prop, int T, int K, int Kc, int g3,
+                                                        float* __restrict__ heatmaps) {
+    const int b = blockIdx.y, K4 = (K + 3) / 4;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= g3 * K4) return;
+    const int vox = i % g3, k = (i / g3) * 4;
+    const float w0 = prop[0], w1 = prop[1], pb = prop[2];
+    const f32x4 c = *reinterpret_cast<const f32x4*>(clip_head + ((size_t)b * g3 + vox) * Kc + k);
+    float prev[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) prev[j] = lrelu(c[j], 0.01f);
+    for (int t = 0; t < T; ++t) {
+        const size_t f = (size_t)b * T + t;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(head + (f * g3 + vox) * Kc + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (k + j >= K) break;
+            float hm = softplus(w0 * lrelu(a[j], 0.01f) + w1 * prev[j] + pb);
+            heatmaps[(f * K + k + j) * g3 + vox] = hm;
+            prev[j] = hm;
+        }
+    }
+}
+// grid (F, g): the marginal partial sums of one z-plane of one frame from the heat-maps heat_scan_kernel wrote - the second half of
+// heatmap_kernel, the same `part` record in the same order.  LDS: K * g * g floats.
+__global__ __launch_bounds__(256) void heat_marginals_kernel(const float* __restrict__ heatmaps, int K, int g, float* __restrict__ part) {
+    extern __shared__ float tile[];                       // [K][g*g]
+    const int f = blockIdx.x, z = blockIdx.y;
+    const int g2 = g * g, g3 = g2 * g;
+    for (int i = threadIdx.x; i < K * g2; i += 256) tile[i] = heatmaps[((size_t)f * K + i / g2) * g3 + (size_t)z * g2 + i % g2];
+    __syncthreads();
+    heat_plane_marginals(tile, f, z, K, g, part);
 }
 
 // one block per frame.  Phase 1: the K*3*g marginal weights w[k][d][j] in parallel (axis 0: the plane sums, axes 1/2: sums of the
@@ -617,6 +665,15 @@ int nm_launch_heatmap(const float* head, const float* clip_head, const float* pr
     size_t lds = (size_t)K * g * g * sizeof(float);
     hipLaunchKernelGGL(heatmap_kernel, dim3(F, g), dim3(256), lds, s, head, clip_head, prop, T, K, Kc, g, heatmaps, part);
     return nm_check_hip(hipGetLastError(), "heatmap launch");
+}
+
+int nm_launch_heatmap_recurrent(const float* head, const float* clip_head, const float* prop, int B, int T, int K, int Kc, int g,
+                                float* heatmaps, float* part, hipStream_t s) {
+    if (K < 1 || K > 32 || Kc % 4 || Kc < K || g > 32 || B > 65535) { nm_set_error("heatmap_recurrent: K=%d (row pitch %d), g=%d, B=%d unsupported", K, Kc, g, B); return NM_ERR_ARG; }
+    const int g3 = g * g * g, items = g3 * ((K + 3) / 4);
+    hipLaunchKernelGGL(heat_scan_kernel, dim3((items + 255) / 256, B), dim3(256), 0, s, head, clip_head, prop, T, K, Kc, g3, heatmaps);
+    hipLaunchKernelGGL(heat_marginals_kernel, dim3(B * T, g), dim3(256), (size_t)K * g * g * sizeof(float), s, heatmaps, K, g, part);
+    return nm_check_hip(hipGetLastError(), "heatmap_recurrent launch");
 }
 
 int nm_launch_keypoints(const float* part, int F, int K, int g, float* keypoints, float* heat_mean, hipStream_t s) {

@@ -21,6 +21,11 @@ size_t nm_heat_bwd_ws_floats(int F, int K, int g);
 int nm_launch_heat_bwd(const float* head, const float* clip_head, const float* prop, const float* heat_part, const float* heat_mean,
                        const float* keypoints, const float* dkp, const float* dloss, int B, int T, int K, int Kc /* channels per voxel of the head tensors (>= K) */, int g, float* ws, float* dhead,
                        float* dchead_t, float* dclip_head, float* dprop, hipStream_t s);
+// const_intensity 2 (kypt_detector.py:344-345): the reverse scan over the frames of a clip; dclip_head [B][g^3][Kc] comes from frame 0 alone
+size_t nm_heat_bwd_recurrent_ws_floats(int B, int T, int K, int Kc, int g);
+int nm_launch_heat_bwd_recurrent(const float* head, const float* clip_head, const float* prop, const float* heat_part, const float* heat_mean,
+                                 const float* keypoints, const float* dkp, const float* dloss, int B, int T, int K, int Kc, int g, float* ws,
+                                 float* dhead, float* dclip_head, float* dprop, hipStream_t s);
 // dinfl [B][K][K] (written when affinity != nullptr)
 int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const float* dloss, int B, int T, int K, int N, float sep_sigma,
                             int use_traj, float* dkp, float* dinfl, hipStream_t s,

@@ -431,6 +431,58 @@ __global__ __launch_bounds__(256) void heat_bwd_kernel(const float* __restrict__
     s0 = block_sum256(s0, sh); s1 = block_sum256(s1, sh); s2 = block_sum256(s2, sh);
     if (threadIdx.x == 0) { float* o = pp + ((size_t)f * g + z) * 3; o[0] = s0; o[1] = s1; o[2] = s2; }
 }
+// const_intensity 2 (kypt_detector.py:344-345): h_t = softplus(u_t), u_t = w0 lrelu(a_t) + w1 p_t + b with p_0 = lrelu(c), p_t = h_{t-1}.  The
+// recurrence is pointwise, so one thread owns one (clip, voxel, channel) entry and walks its T frames twice: forward, recomputing the scan
+// from the tape's head outputs and parking p_t in the entry's own dhead slot of frame t; then backward,
+//   G_t = D_t + w1 delta_{t+1},  delta_t = G_t sigmoid(u_t),  dhead_t = delta_t w0 lrelu'(a_t),  dchead = delta_0 w1 lrelu'(c)
+// (D_t: the affine direct derivative of heat_bwd_prep_kernel), overwriting the slot it has just read.  grid (blocks, B), blocks =
+// ceil(g^3 Kc / 256); pp[(b*blocks+blk)][3] = (sum delta lrelu(a), sum delta p, sum delta) over the block's entries and all t, in a fixed
+// order.  Padded channels (k >= K) get zeros.
+__global__ __launch_bounds__(256) void heat_bwd_recurrent_kernel(const float* __restrict__ head, const float* __restrict__ clip_head,
+                                                                 const float* __restrict__ prop, const float* __restrict__ coef, int T, int K,
+                                                                 int Kc, int g, float* dhead, float* __restrict__ dchead,
+                                                                 float* __restrict__ pp) {
+    __shared__ float sh[256];
+    const int b = blockIdx.y;
+    const int g2 = g * g;
+    const size_t per = (size_t)g2 * g * Kc;                      // entries of one frame
+    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
+    const float w0 = prop[0], w1 = prop[1], pb = prop[2];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    if (i < per) {
+        const int k = (int)(i % Kc), vox = (int)(i / Kc);
+        const int x = vox % g, y = (vox / g) % g, z = vox / g2;
+        const size_t e0 = (size_t)b * T * per + i;               // the entry in frame 0 of the clip
+        if (k >= K) {
+            for (int t = 0; t < T; ++t) dhead[e0 + t * per] = 0.f;
+            dchead[(size_t)b * per + i] = 0.f;
+        } else {
+            const float c = clip_head[(size_t)b * per + i];
+            float p = lrelu(c, 0.01f);
+            for (int t = 0; t < T; ++t) {
+                const float u = w0 * lrelu(head[e0 + t * per], 0.01f) + w1 * p + pb;
+                dhead[e0 + t * per] = p;
+                p = u > 20.f ? u : log1pf(expf(u));
+            }
+            const float lz = lin_coord(z, g), ly = lin_coord(y, g), lx = lin_coord(x, g);
+            float delta = 0.f;
+            for (int t = T - 1; t >= 0; --t) {
+                const float a = head[e0 + t * per], pt = dhead[e0 + t * per];
+                const float la = lrelu(a, 0.01f);
+                const float u = w0 * la + w1 * pt + pb;
+                const float sig = u > 20.f ? 1.0f : 1.0f / (1.0f + expf(-u));
+                const float* cf = coef + ((size_t)(b * T + t) * K + k) * 4;
+                const float dhm = cf[0] * lz + cf[1] * ly + cf[2] * lx + cf[3];
+                delta = (dhm + w1 * delta) * sig;
+                dhead[e0 + t * per] = delta * w0 * (a > 0.f ? 1.0f : 0.01f);
+                s0 += delta * la; s1 += delta * pt; s2 += delta;
+            }
+            dchead[(size_t)b * per + i] = delta * w1 * (c > 0.f ? 1.0f : 0.01f);
+        }
+    }
+    s0 = block_sum256(s0, sh); s1 = block_sum256(s1, sh); s2 = block_sum256(s2, sh);
+    if (threadIdx.x == 0) { float* o = pp + ((size_t)b * gridDim.x + blockIdx.x) * 3; o[0] = s0; o[1] = s1; o[2] = s2; }
+}
 // out[b][i] = sum_t in[b*T+t][i]
 __global__ __launch_bounds__(256) void sum_t_kernel(const float* __restrict__ in, int B, int T, size_t per, float* __restrict__ out) {
     const size_t total = (size_t)B * per;
@@ -848,6 +900,23 @@ int nm_launch_heat_bwd(const float* head, const float* clip_head, const float* p
     return nm_check_hip(hipGetLastError(), "heat_bwd launch");
 }
 size_t nm_heat_bwd_ws_floats(int F, int K, int g) { return (size_t)F * K * 4 + (size_t)F * g * 3 + 64; }
+
+static int heat_bwd_recurrent_blocks(int Kc, int g) { return (int)(((size_t)g * g * g * Kc + 255) / 256); }
+size_t nm_heat_bwd_recurrent_ws_floats(int B, int T, int K, int Kc, int g) {
+    return (size_t)B * T * K * 4 + (size_t)B * heat_bwd_recurrent_blocks(Kc, g) * 3 + 64;
+}
+int nm_launch_heat_bwd_recurrent(const float* head, const float* clip_head, const float* prop, const float* heat_part, const float* heat_mean,
+                                 const float* keypoints, const float* dkp, const float* dloss, int B, int T, int K, int Kc, int g, float* ws,
+                                 float* dhead, float* dclip_head, float* dprop, hipStream_t s) {
+    const int F = B * T, nblk = heat_bwd_recurrent_blocks(Kc, g);
+    if (K < 1 || K > 32 || Kc < K || B > 65535) { nm_set_error("heat_bwd_recurrent: K=%d (row pitch %d), B=%d unsupported", K, Kc, B); return NM_ERR_ARG; }
+    float* coef = ws;                         // [F][K][4]
+    float* pp = ws + (size_t)F * K * 4;       // [B*nblk][3]
+    hipLaunchKernelGGL(heat_bwd_prep_kernel, dim3(F), dim3(64), 0, s, heat_part, heat_mean, keypoints, dkp, dloss, F, K, g, coef);
+    hipLaunchKernelGGL(heat_bwd_recurrent_kernel, dim3(nblk, B), dim3(256), 0, s, head, clip_head, prop, coef, T, K, Kc, g, dhead, dclip_head, pp);
+    hipLaunchKernelGGL(sum_rows_kernel, dim3(3), dim3(256), 0, s, pp, B * nblk, 3, dprop);
+    return nm_check_hip(hipGetLastError(), "heat_bwd_recurrent launch");
+}
 
 int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const float* dloss, int B, int T, int K, int N, float sep_sigma,
                             int use_traj, float* dkp, float* dinfl, hipStream_t s, int graph_ver, int graph_flags) {

@@ -42,6 +42,7 @@ struct FeatRec {
 struct TrainTape {
     bool valid = false;
     int B = 0, T = 0, affinity_on = 0;
+    int const_intensity = 3;                                  // what the forward ran (nm_ctx_set_const_intensity)
     FeatRec frame, clip;
     ConvRec head, clip_head, adjust, d1, d4, d8, d11;
     const float *vox = nullptr, *feat = nullptr, *head_out = nullptr, *clip_head_out = nullptr, *heat_part = nullptr, *heat_mean = nullptr;
@@ -698,7 +699,8 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
         conv_gn(n, mk(feat, F, g, g, g, FEAT), d.head, nullptr, 1, 0, 1.0f, head, false, tape ? &tape->head : nullptr);
         if (n.live()) {
             n.run(nm_check_hip(hipStreamWaitEvent(n.s, c->ev_clip, 0), "join clip net"));
-            n.run(nm_launch_heatmap(head, clip_head, d.prop, F, T, K, Kc, g, heatmaps, heat_part, n.s));
+            if (c->const_intensity == 2) n.run(nm_launch_heatmap_recurrent(head, clip_head, d.prop, B, T, K, Kc, g, heatmaps, heat_part, n.s));
+            else n.run(nm_launch_heatmap(head, clip_head, d.prop, F, T, K, Kc, g, heatmaps, heat_part, n.s));
             n.run(nm_launch_keypoints(heat_part, F, K, g, keypoints, heat_mean, n.s));
             if (after_keypoints && n.ok()) n.run((*after_keypoints)());
         }
@@ -713,7 +715,7 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
     // (recon == nullptr: the keypoints-only pass of nm_detector_keypoints - no voxel decoder, no losses)
     if (recon) decode_frames(n, keypoints, feat, T, vox_in, T, B, T, vox_in, c->cfg.vol_fit_chamfer == 1, recon, tail_part, tape, c->learn_sigma != 0);
     if (tape) {
-        tape->B = B; tape->T = T; tape->affinity_on = affinity_on; tape->vox = vox_in; tape->feat = feat; tape->clip_head_out = clip_head;
+        tape->B = B; tape->T = T; tape->affinity_on = affinity_on; tape->const_intensity = c->const_intensity; tape->vox = vox_in; tape->feat = feat; tape->clip_head_out = clip_head;
         tape->heat_part = heat_part; tape->heat_mean = heat_mean; tape->tail_part = tail_part; tape->aff = aff;
         tape->keypoints = keypoints; tape->recon = recon;
     }
@@ -1186,14 +1188,20 @@ int backward_graph(nm_ctx* c, const TrainTape& t, const float* dloss, const std:
     {   // keypoints <- heat-maps <- heads; head conv back into the frame features
         const size_t m = b.ws.mark();
         float* dhead = b.alloc((size_t)F * g3 * Kc);
-        float* dchead_t = b.alloc((size_t)F * g3 * Kc);
-        float* hws = b.alloc(nm_heat_bwd_ws_floats(F, K, g));
+        // (const_intensity 2: the clip head hears from frame 0 alone - no per-frame gradient to sum over t)
+        const bool recurrent = t.const_intensity == 2;
+        float* dchead_t = recurrent ? nullptr : b.alloc((size_t)F * g3 * Kc);
+        float* hws = b.alloc(recurrent ? nm_heat_bwd_recurrent_ws_floats(B, T, K, Kc, g) : nm_heat_bwd_ws_floats(F, K, g));
         float* gprop = b.alloc(4);
         float* gpw = b.grad(v2k + ".propagate_heatmaps.0.weight", 2);
         float* gpb = b.grad(v2k + ".propagate_heatmaps.0.bias", 1);
         if (b.live()) {
-            b.run(nm_launch_heat_bwd(t.head_out, t.clip_head_out, d.prop, t.heat_part, t.heat_mean, t.keypoints, dkp, dloss, B, T, K, Kc, g, hws,
-                                     dhead, dchead_t, dchead, gprop, b.s));
+            if (recurrent)
+                b.run(nm_launch_heat_bwd_recurrent(t.head_out, t.clip_head_out, d.prop, t.heat_part, t.heat_mean, t.keypoints, dkp, dloss, B, T, K, Kc,
+                                                   g, hws, dhead, dchead, gprop, b.s));
+            else
+                b.run(nm_launch_heat_bwd(t.head_out, t.clip_head_out, d.prop, t.heat_part, t.heat_mean, t.keypoints, dkp, dloss, B, T, K, Kc, g, hws,
+                                         dhead, dchead_t, dchead, gprop, b.s));
             b.run(nm_check_hip(hipMemcpyAsync(gpw, gprop, 2 * sizeof(float), hipMemcpyDeviceToDevice, b.s), "backward: copy"));
             b.run(nm_check_hip(hipMemcpyAsync(gpb, gprop + 2, sizeof(float), hipMemcpyDeviceToDevice, b.s), "backward: copy"));
         }
@@ -1614,6 +1622,17 @@ int nm_ctx_set_affinity_ver(nm_ctx* c, int32_t ver) try { NmScope nm_scope_(c);
     if (ver != c->affinity_ver) { c->affinity_ver = ver; c->has_weights = false; }      // the parameter's shape changes: weights must be set again
     return NM_OK;
 } catch (...) { return nm_abi_catch("nm_ctx_set_affinity_ver"); }
+
+int nm_ctx_set_const_intensity(nm_ctx* c, int32_t v) try { NmScope nm_scope_(c);
+    // (the value is judged first: a caller without a device learns what the library supports from a null context)
+    if (v != 2 && v != 3) {
+        nm_set_error("ctx_set_const_intensity: %d (2 or 3; 0 has another weight table, 1 the initial_heatmaps parameter, 4 does not run in the reference)", v);
+        return NM_ERR_UNSUPPORTED;
+    }
+    if (!c) { nm_set_error("ctx_set_const_intensity: null context"); return NM_ERR_ARG; }
+    c->const_intensity = v;              // same 337 tensors for both values: loaded weights stay valid
+    return NM_OK;
+} catch (...) { return nm_abi_catch("nm_ctx_set_const_intensity"); }
 
 int nm_ctx_set_graph_loss(nm_ctx* c, int32_t ver, int32_t flags) try { NmScope nm_scope_(c);
     if (!c) { nm_set_error("ctx_set_graph_loss: null context"); return NM_ERR_ARG; }

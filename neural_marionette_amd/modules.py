@@ -98,6 +98,8 @@ class Engine:
                 _lib.check(self.ctx.lib.nm_ctx_set_gaussian_cat(self.ctx.handle, {"max": 1, "sum": 2}[o.gaussian_cat_type]), "set_gaussian_cat")
             if o.affinity_ver != 3:                        # (N, K, K) affinity parameters: before the first nm_ctx_set_weights
                 _lib.check(self.ctx.lib.nm_ctx_set_affinity_ver(self.ctx.handle, int(o.affinity_ver)), "set_affinity_ver")
+            if o.const_intensity == 2:                     # kypt_detector.py:344-345: heat-maps propagated frame to frame (same weights as 3)
+                _lib.check(self.ctx.lib.nm_ctx_set_const_intensity(self.ctx.handle, 2), "set_const_intensity")
             flags = o.graph_loss_flags()
             if o.graph_loss_ver != 1 or flags:             # kypt_detector.py:112-143 ('none': before the first nm_ctx_set_weights)
                 _lib.check(self.ctx.lib.nm_ctx_set_graph_loss(self.ctx.handle, int(o.graph_loss_ver), flags), "set_graph_loss")

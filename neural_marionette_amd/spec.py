@@ -89,7 +89,8 @@ class HotPathOptions:
         silently computing something different."""
         bad = []
         if self.input_dim != 3: bad.append("input_dim must be 3")
-        if self.const_intensity != 3: bad.append("const_intensity must be 3")
+        if self.const_intensity not in (2, 3):
+            bad.append("const_intensity must be 2 or 3 (0 drops the spatio-temporal net, 1 needs the initial_heatmaps parameter, 4 does not run in the reference)")
         if self.affinity_ver not in (0, 1, 2, 3): bad.append("affinity_ver must be 0, 1, 2 or 3 (4 draws Gumbel noise: not implemented)")
         if self.graph_loss_ver not in (0, 1, 2): bad.append("graph_loss_ver must be 0, 1 or 2")
         if self.gaussian_cat_type not in ("none", "max", "sum"): bad.append("gaussian_cat_type must be 'none', 'max' or 'sum'")
