@@ -190,6 +190,34 @@ int nm_ctx_set_graph_loss(nm_ctx* ctx, int32_t ver, int32_t flags);
 int nm_voxelize_clip(nm_ctx* ctx, const double* points, int32_t T, int64_t N, double scale, float* vox,
                      int32_t* idx_out);
 
+/* Input path on the device for a batch: crop_sequence + episodic_normalization (with translation and joints) + voxelize of
+ * utils/dataset_utils.py:6-31 as the dataset classes call them (dataset/dataset.py:47-88, :123-183), for B crops of sequences that
+ * stay in device memory, in the reference's arithmetic for the dtype the data has.
+ *   clips_dev (B) descriptors IN DEVICE MEMORY: points (frames,N,3) and joints (frames,J,3) or NULL of the sequence, its number of
+ *     frames, the crop's first frame and frame stride, pad != 0: frames past the end repeat the last one (dataset.py:65-68; without
+ *     it start + (T-1) sample_rate < frames must hold), and scale / x_trans / z_trans of episodic_normalization.
+ *   points_f64 / joints_f64: 0 = float32, 1 = float64, for every clip of the call.  float32 points are normalised in float32
+ *     (den = f32(blen + f32(1e-5)), every step rounded) and become float64 at the translation add, as numpy 2 promotes them; float64
+ *     points run nm_voxelize_clip's chain with (x_trans, 0, z_trans) added.
+ *   vox (B,T,1,G,G,G) fp32 {0,1}.  An index in [-G,-1] wraps to idx + G like numpy's; a row with an index outside [-G,G) or a
+ *     non-finite coordinate writes nothing and is counted in bad_rows (B) int32 (the reference raises "Dataset voxelizer error").
+ *   joints_out (B,T,J,3): ((j - bmin) scale / den) 2 - 1 without translation, float32 when points and joints both are, else float64;
+ *     required when J > 0.  idx_out (B,T,N,3) int32: the indices before the wrap (0 where the
+ *     quotient is not finite or beyond int32).  bbox_out (B,6) float64: bmin xyz, bmax xyz of each
+ *     clip's crop.  joints_out / idx_out / bbox_out may be NULL.
+ * The call copies nothing, synchronises nothing (but for the workspace's first growth) and needs no weights; the descriptors are
+ * therefore not readable by it: the caller checks them, the kernels never read past a sequence's last frame, and a clip whose crop
+ * does not fit (or whose descriptor is malformed) writes nothing and counts all its T N rows as bad.  NM_ERR_ARG: null
+ * clips_dev / vox / bad_rows, B, T, N < 1, J < 0, J > 0 without joints_out; NM_ERR_UNSUPPORTED: B > 65535. */
+typedef struct nm_clip_desc {
+    const void* points;
+    const void* joints;
+    int32_t frames, start, sample_rate, pad;
+    double scale, x_trans, z_trans;
+} nm_clip_desc;
+int nm_voxelize_batch(nm_ctx* ctx, const nm_clip_desc* clips_dev, int32_t B, int32_t T, int64_t N, int32_t J, int32_t points_f64,
+                      int32_t joints_f64, float* vox, void* joints_out, int32_t* idx_out, double* bbox_out, int32_t* bad_rows);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

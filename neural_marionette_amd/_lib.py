@@ -32,6 +32,11 @@ class NmNamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
 
+class NmClipDesc(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("joints", C.c_void_p), ("frames", C.c_int32), ("start", C.c_int32),
+                ("sample_rate", C.c_int32), ("pad", C.c_int32), ("scale", C.c_double), ("x_trans", C.c_double), ("z_trans", C.c_double)]
+
+
 _P = C.c_void_p   # device pointers travel as plain integers
 _I = C.c_int32
 _F = C.c_float
@@ -59,6 +64,7 @@ SIGNATURES = {
     "nm_ctx_set_const_intensity": (C.c_int, [C.c_void_p, _I]),
     "nm_ctx_set_graph_loss": (C.c_int, [C.c_void_p, _I, _I]),
     "nm_voxelize_clip": (C.c_int, [C.c_void_p, _P, _I, C.c_int64, C.c_double, _P, _P]),
+    "nm_voxelize_batch": (C.c_int, [C.c_void_p, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

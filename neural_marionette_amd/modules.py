@@ -800,6 +800,23 @@ class NeuralMarionette(nn.Module):
         eng.call("nm_voxelize_clip", _lib.ptr(pts), T, N, float(scale), _lib.ptr(vox), _lib.ptr(idx))
         return (vox, idx) if return_indices else vox
 
+    def voxelize_batch(self, bank, ids, starts, T, sample_rate: int = 1, scale=1.0, x_trans=0.0, z_trans=0.0, return_joints: bool = False,
+                       return_indices: bool = False, check: bool = False, pad=None):
+        """The reference's per-item input path (dataset/dataset.py:47-88, :123-183: crop_sequence -> episodic_normalization ->
+        voxelize) for a batch of crops of device-resident sequences, in one stream-ordered library call (nm_voxelize_batch), in the
+        reference's arithmetic for the dtype the data has: float32 sequences are normalised in float32 and become float64 at the
+        translation add, as numpy does it.  bank: data.ClipBank; clip b is frames starts[b] + t * sample_rate, t < T, of sequence
+        ids[b]; pad[b]: frames past the end repeat the last one (data.ClipSampler says when the reference does that), otherwise the
+        crop must fit.  scale / x_trans / z_trans: one value or one per clip.
+        Returns a dict: vox (B,T,1,G,G,G) fp32; joints (B,T,J,3) [return_joints: normalised with the clip's box, no translation,
+        float32 only when points and joints both are]; indices (B,T,N,3) int32 [return_indices: before numpy's negative-index wrap];
+        bbox (B,6) float64 (bmin, bmax); bad_rows (B) int32: rows with an index outside [-G,G) or a non-finite coordinate - they set
+        no voxel.  The reference raises for such a clip: check=True reads bad_rows (the call's one synchronisation) and raises
+        ValueError("Dataset voxelizer error") like it.  The descriptors travel through pinned staging; nothing else is copied."""
+        from . import data
+        return data.voxelize_batch(self, bank, ids, starts, T, sample_rate=sample_rate, scale=scale, x_trans=x_trans, z_trans=z_trans,
+                                   return_joints=return_joints, return_indices=return_indices, check=check, pad=pad)
+
     # -- sampling drivers (SURVEY 8(f3)): the rollout loops of the reference's demo scripts as methods ------------
     @torch.no_grad()
     def sample_generation(self, cond_voxel, Tgen=25, sample_num=3, eps_post=None, eps_prior=None):
