@@ -419,6 +419,56 @@ int nm_op_convT2_backward(nm_ctx* ctx, const float* in, int32_t N, int32_t D, in
                           int32_t outpad, const float* dy, float* d_in, float* d_weight, float* d_bias);
 int nm_op_gn_backward(nm_ctx* ctx, const float* y, int32_t N, int32_t voxels, int32_t C, int32_t groups, const float* gamma,
                       const float* beta, float slope, const float* dA, float* dy, float* dgamma, float* dbeta, float* dbias);
+/* Detector heads and losses, one launcher sequence of the network path per call on tensors the caller chooses (unit parity against
+ * fp64 in tests/test_heads_ops_gpu.py).  Scratch comes from the context's workspace: do not interleave with a network call whose
+ * results are still being read.  F = B T frames, g = heat-map edge, G = occupancy-grid edge, dloss = device vector of 11 loss weights
+ * (order of losses11).  Outputs the launchers accumulate into (dkp, dfeat) are zeroed by the call.
+ * nm_op_heatmaps[_backward]: head (F,g,g,g,Kc) / clip_head (B,g,g,g,Kc) channels-last head outputs (Kc >= K, Kc % 4 == 0), prop (3) =
+ *   propagate weight 0, 1, bias; recurrent 0 = const_intensity 3, 1 = const_intensity 2 -> heatmaps (F,K,g,g,g), keypoints (F,K,4),
+ *   heat_mean (F,K).  Backward: dkp (F,K,4) and dloss[4] (sparsity) -> dhead, dclip_head (layouts of head / clip_head), dprop (3).
+ * nm_op_combined[_backward]: Gaussian table (F,K,3,g; `table` may be NULL) of width 2 (sigma / g)^2, or per keypoint from sigma_param (K)
+ *   (fixed_sigma = 0: sigmoid(p) 2 sigma), and the combined representation out (F,g,g,g,Cc) = [gauss_t K | first_feature Fd | gauss_0 K |
+ *   3 coordinates | zeros]; first_feature (B,g,g,g,Fd); cat 0 / 1 / 2 = gaussian_cat_type none / max / sum.  Backward: dcomb (F,g,g,g,Cd) ->
+ *   dfeat (F,g,g,g,Fd) (frame 0 of every clip holds the clip's sum, the rest zeros), dkp (F,K,4), dsigma_param (K, with sigma_param).
+ * nm_op_decoder_tail[_backward]: x (F,G,G,G,C) raw with per-frame scale / shift (F,C) and LeakyReLU slope, w14 (C+1: weights, bias),
+ *   first_frames: frame b ff_stride_frames is clip b's, target / keypoints may be NULL -> recon (F,G,G,G), frame_sums (F,3) = BCE sum,
+ *   occupancy-masked chamfer sum, occupied count.  Backward (dloss[0], dloss[1]): dA (F,G,G,G,C), or with dvout (F,G,G,G; C == 32) only the
+ *   per-voxel factor (dA = dvout (x) w14[0..C)), dw14 (C+1), and with dkp (F,K,4) the chamfer term's keypoint gradient.
+ * nm_op_clip_losses[_backward]: the 11 losses from keypoints (F,K,4), affinity (N,K,K) or NULL, heat_mean (F,K), frame_sums (F,3) and
+ *   vol_override (F,2) or NULL (numerator, denominator of vol_fit 'gaussian'); vol_fit 0 writes a zero volume term.  Backward: dkp (F,K,4)
+ *   and dinfl (B,K,K) (with an affinity) of the separation, local, time and trajectory terms.
+ * nm_op_affinity[_backward]: get_affinity version 0-3 from params (N,K,K-1) [3] / (N,K,K) -> (N,K,K); backward from dinfl (B,K,K) and
+ *   dloss[7] (neighbour sparsity) -> dparams.
+ * nm_op_volfit_gauss[_backward]: vol_fit_type 'gaussian': vox (F,G,G,G), keypoints -> vol (F,2); backward dloss[1] -> dkp (F,K,4). */
+int nm_op_heatmaps(nm_ctx* ctx, const float* head, const float* clip_head, const float* prop, int32_t B, int32_t T, int32_t K, int32_t Kc,
+                   int32_t g, int32_t recurrent, float* heatmaps, float* keypoints, float* heat_mean);
+int nm_op_heatmaps_backward(nm_ctx* ctx, const float* head, const float* clip_head, const float* prop, int32_t B, int32_t T, int32_t K,
+                            int32_t Kc, int32_t g, int32_t recurrent, const float* dkp, const float* dloss, float* dhead,
+                            float* dclip_head, float* dprop);
+int nm_op_combined(nm_ctx* ctx, const float* keypoints, const float* first_feature, const float* sigma_param, int32_t B, int32_t T, int32_t K,
+                   int32_t Fd, int32_t g, int32_t Cc, float sigma, int32_t cat, float* table, float* out);
+int nm_op_combined_backward(nm_ctx* ctx, const float* dcomb, int32_t Cd, const float* keypoints, const float* sigma_param, int32_t B,
+                            int32_t T, int32_t K, int32_t Fd, int32_t g, float sigma, int32_t cat, float* dfeat, float* dkp,
+                            float* dsigma_param);
+int nm_op_decoder_tail(nm_ctx* ctx, const float* x, const float* scale, const float* shift, float slope, int32_t B, int32_t T, int32_t C,
+                       int32_t G, const float* w14, const float* first_frames, int32_t ff_stride_frames, const float* target,
+                       const float* keypoints, int32_t K, float* recon, float* frame_sums);
+int nm_op_decoder_tail_backward(nm_ctx* ctx, const float* x, const float* scale, const float* shift, float slope, int32_t F, int32_t C, int32_t G,
+                                const float* w14, const float* target, const float* recon, const float* frame_sums, const float* keypoints,
+                                int32_t K, const float* dloss, float* dA, float* dvout, float* dw14, float* dkp);
+int nm_op_clip_losses(nm_ctx* ctx, const float* keypoints, const float* affinity, const float* heat_mean, const float* frame_sums,
+                      const float* vol_override, int32_t B, int32_t T, int32_t K, int32_t N, int32_t G, float sep_sigma, int32_t graph_ver,
+                      int32_t graph_flags, int32_t use_traj, int32_t vol_fit, float* losses11);
+int nm_op_clip_losses_backward(nm_ctx* ctx, const float* keypoints, const float* affinity, const float* dloss, int32_t B, int32_t T, int32_t K,
+                               int32_t N, float sep_sigma, int32_t graph_ver, int32_t graph_flags, int32_t use_traj, float* dkp,
+                               float* dinfl);
+int nm_op_affinity(nm_ctx* ctx, const float* params, int32_t N, int32_t K, int32_t ver, float* affinity);
+int nm_op_affinity_backward(nm_ctx* ctx, const float* params, const float* affinity, const float* dinfl, const float* dloss, int32_t B, int32_t N,
+                            int32_t K, int32_t ver, int32_t graph_ver, int32_t graph_flags, float* dparams);
+int nm_op_volfit_gauss(nm_ctx* ctx, const float* vox, const float* keypoints, int32_t B, int32_t T, int32_t K, int32_t G, float sigma,
+                       float* vol);
+int nm_op_volfit_gauss_backward(nm_ctx* ctx, const float* vox, const float* keypoints, const float* dloss, int32_t B, int32_t T, int32_t K,
+                                int32_t G, float sigma, float* dkp);
 /* Conv arithmetic (per context: two contexts in one process may run in different modes; like every other launch-time
  * switch it lives in the nm_ctx).  mode 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32) for every conv.
  * mode 1 (default): layers with Cin % 16 == 0 run on the fp16 matrix cores with every fp32 operand split

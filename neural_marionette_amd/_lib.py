@@ -103,6 +103,18 @@ SIGNATURES = {
     "nm_op_conv5_occ_backward": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _P, _P, _P, _I]),
     "nm_op_convT2_backward": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P, _P, _P]),
     "nm_op_gn_backward": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
+    "nm_op_heatmaps": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "nm_op_heatmaps_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nm_op_combined": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P]),
+    "nm_op_combined_backward": (C.c_int, [C.c_void_p, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "nm_op_decoder_tail": (C.c_int, [C.c_void_p, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "nm_op_decoder_tail_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _F, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "nm_op_clip_losses": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _I, _I, _P]),
+    "nm_op_clip_losses_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _I, _P, _P]),
+    "nm_op_affinity": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _P]),
+    "nm_op_affinity_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "nm_op_volfit_gauss": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "nm_op_volfit_gauss_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "nm_set_conv_mode": (C.c_int, [C.c_void_p, _I]),
     "nm_get_conv_mode": (C.c_int, [C.c_void_p]),
     "nm_op_set_storage16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

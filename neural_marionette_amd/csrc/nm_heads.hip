@@ -659,10 +659,25 @@ __global__ void affinity_kernel(const float* __restrict__ params, int N, int K, 
 
 }  // namespace
 
+// The plane tile [K][g*g] of heatmap_kernel / heat_marginals_kernel is dynamic LDS: up to 128 KB (K = 32, g = 32), beyond the 64 KB a
+// kernel may ask for by default.  The limit is raised once per device and kernel (as nm_launch_clip_loss_bwd does for its kernel); a
+// runtime that refuses it reports NM_ERR_HIP here, not a failed launch later.
+static int heat_plane_lds_limit(const void* kernel, int which) {
+    static NmDeviceOnce attr_set[2];
+    if (attr_set[which].done()) return NM_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 32 * 32 * (int)sizeof(float)) != hipSuccess) {
+        nm_set_error("heatmap: cannot raise the dynamic LDS limit to 128 KB"); return NM_ERR_HIP;
+    }
+    attr_set[which].mark();
+    return NM_OK;
+}
+
 int nm_launch_heatmap(const float* head, const float* clip_head, const float* prop, int F, int T, int K, int Kc, int g,
                       float* heatmaps, float* part, hipStream_t s) {
     if (K < 1 || K > 32 || Kc % 4 || Kc < K || g > 32) { nm_set_error("heatmap: K=%d (row pitch %d), g=%d unsupported", K, Kc, g); return NM_ERR_ARG; }
     size_t lds = (size_t)K * g * g * sizeof(float);
+    int rc = heat_plane_lds_limit(reinterpret_cast<const void*>(heatmap_kernel), 0);
+    if (rc) return rc;
     hipLaunchKernelGGL(heatmap_kernel, dim3(F, g), dim3(256), lds, s, head, clip_head, prop, T, K, Kc, g, heatmaps, part);
     return nm_check_hip(hipGetLastError(), "heatmap launch");
 }
@@ -671,12 +686,15 @@ int nm_launch_heatmap_recurrent(const float* head, const float* clip_head, const
                                 float* heatmaps, float* part, hipStream_t s) {
     if (K < 1 || K > 32 || Kc % 4 || Kc < K || g > 32 || B > 65535) { nm_set_error("heatmap_recurrent: K=%d (row pitch %d), g=%d, B=%d unsupported", K, Kc, g, B); return NM_ERR_ARG; }
     const int g3 = g * g * g, items = g3 * ((K + 3) / 4);
+    int rc = heat_plane_lds_limit(reinterpret_cast<const void*>(heat_marginals_kernel), 1);
+    if (rc) return rc;
     hipLaunchKernelGGL(heat_scan_kernel, dim3((items + 255) / 256, B), dim3(256), 0, s, head, clip_head, prop, T, K, Kc, g3, heatmaps);
     hipLaunchKernelGGL(heat_marginals_kernel, dim3(B * T, g), dim3(256), (size_t)K * g * g * sizeof(float), s, heatmaps, K, g, part);
     return nm_check_hip(hipGetLastError(), "heatmap_recurrent launch");
 }
 
 int nm_launch_keypoints(const float* part, int F, int K, int g, float* keypoints, float* heat_mean, hipStream_t s) {
+    if (F < 1 || K < 1 || K > 32 || g < 2 || g > 32) { nm_set_error("keypoints: F=%d K=%d g=%d unsupported", F, K, g); return NM_ERR_ARG; }
     hipLaunchKernelGGL(keypoints_kernel, dim3(F), dim3(256), (size_t)(K * 3 * g + 4 * K) * sizeof(float), s, part, K, g, keypoints, heat_mean);
     return nm_check_hip(hipGetLastError(), "keypoints launch");
 }

@@ -682,10 +682,12 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                 float cs = 0.f;
                 for (int d = 0; d < 3; ++d) cs += (vk[d] / nk) * (vl[d] / nl);
                 if (wi) vs += ((-cs + 1.0f) / 2.0f) * infl[k * K + l];
-                // d cos / d v_k = (vhat_l - cos * vhat_k) / |v_k|   (norm clamped at eps: the clamp has no gradient)
+                // d cos / d v_k = (vhat_l - cos * vhat_k) / |v_k|.  Under the clamp (|v_k| < eps) torch's cosine_similarity divides by
+                // eps but still differentiates the norm it clamped: (vhat_l - cos * v_k / |v_k|) / eps with the TRUE unit vector, cos the
+                // clamped quotient - and v_k / |v_k| = 0 at v_k = 0, the norm's subgradient
                 const float ck = -0.5f * c_vel * wv;
                 for (int d = 0; d < 3; ++d) {
-                    const float dc = clamp_k ? (vl[d] / nl) / nk : ((vl[d] / nl) - cs * (vk[d] / nk)) / nk;
+                    const float dc = clamp_k ? ((vl[d] / nl) - (nkr > 0.f ? cs * (vk[d] / nkr) : 0.f)) / nk : ((vl[d] / nl) - cs * (vk[d] / nk)) / nk;
                     gvv[d] += l == k ? 0.f : ck * dc;      // (the influence has a zero diagonal)
                 }
                 if (has_a) {
@@ -703,7 +705,7 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
                     if (wi) as += ((-ca + 1.0f) / 2.0f) * infl[k * K + l];
                     const float cka = -0.5f * c_acc * wa;
                     for (int d = 0; d < 3; ++d) {
-                        const float dc = clamp_a ? (al[d] / ml) / mk : ((al[d] / ml) - ca * (ak[d] / mk)) / mk;
+                        const float dc = clamp_a ? ((al[d] / ml) - (mkr > 0.f ? ca * (ak[d] / mkr) : 0.f)) / mk : ((al[d] / ml) - ca * (ak[d] / mk)) / mk;
                         gaa[d] += l == k ? 0.f : cka * dc;
                     }
                 }
@@ -744,7 +746,7 @@ __global__ __launch_bounds__(256) void clip_loss_bwd_kernel(const float* __restr
 __global__ __launch_bounds__(256) void affinity_bwd_kernel(const float* __restrict__ params, const float* __restrict__ affinity,
                                                            const float* __restrict__ dinfl, const float* __restrict__ dloss, int B, int N,
                                                            int K, int ver, int gver, int gflags, float* __restrict__ dparams) {
-    extern __shared__ float dA[];       // [N][K][K]
+    extern __shared__ float dA[];       // [N][K][K]; version 1 keeps two more such blocks behind it
     const int KK = K * K;
     const float g_spc = (gflags & NM_GRAPH_SPARSITY_OFF) ? 0.f : dloss[7];
     for (int i = threadIdx.x; i < KK; i += 256) {
@@ -766,26 +768,34 @@ __global__ __launch_bounds__(256) void affinity_bwd_kernel(const float* __restri
         auto sp = [](float x) { return x > 20.f ? x : log1pf(expf(x)); };
         auto dsp = [](float x) { return x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); };
         if (ver == 1) {
-            // W = M' / (r + eps), M' = (S S^T) with a zero diagonal, S = softplus(params): dM' in place of dA, then dS = (dM' + dM'^T) S
+            // W = M' / (r + eps), M' = (S S^T) with a zero diagonal, S = softplus(params): dM', then dS = (dM' + dM'^T) S.
+            // dM'[j] = (d[j] (r + eps) - sum_j' d[j'] m[j']) / (r + eps)^2 is summed as sum_j' (d[j] - d[j']) m[j'] + d[j] eps: the two
+            // halves of d[j] / (r + eps) - d1 / (r + eps)^2 cancel to eps / r of their size, which float32 cannot hold
+            float* M = dA + (size_t)N * KK;     // [N][K][K] products m, then [N][K][K] dM'
+            float* dM = M + (size_t)N * KK;
             for (int row = threadIdx.x; row < N * K; row += 256) {
                 const int k = row % K;
                 const float* p = params + (size_t)row * K; const float* pn = params + (size_t)(row - k) * K;
-                float* d = dA + (size_t)row * K;
-                float r = 0.f, d1 = 0.f;
+                const float* d = dA + (size_t)row * K;
+                float* mr = M + (size_t)row * K;
+                float r = 0.f;
                 for (int j = 0; j < K; ++j) {
-                    if (j == k) continue;
                     float m = 0.f;
-                    for (int c = 0; c < K; ++c) m += sp(p[c]) * sp(pn[(size_t)j * K + c]);
-                    r += m; d1 += d[j] * m;
+                    if (j != k) for (int c = 0; c < K; ++c) m += sp(p[c]) * sp(pn[(size_t)j * K + c]);
+                    mr[j] = m; r += m;
                 }
                 const float inv = 1.f / (r + 1e-6f);
-                for (int j = 0; j < K; ++j) d[j] = (j == k) ? 0.f : d[j] * inv - d1 * inv * inv;
+                for (int j = 0; j < K; ++j) {
+                    float num = d[j] * 1e-6f;
+                    for (int i = 0; i < K; ++i) if (i != k && i != j) num += (d[j] - d[i]) * mr[i];
+                    dM[(size_t)row * K + j] = (j == k) ? 0.f : num * inv * inv;
+                }
             }
             __syncthreads();
             for (int row = threadIdx.x; row < N * K; row += 256) {
                 const int k = row % K, n = row / K;
                 const float* p = params + (size_t)row * K; const float* pn = params + (size_t)(row - k) * K;
-                const float* dn = dA + (size_t)n * KK;
+                const float* dn = dM + (size_t)n * KK;
                 for (int c = 0; c < K; ++c) {
                     float ds = 0.f;
                     for (int j = 0; j < K; ++j) ds += (dn[k * K + j] + dn[j * K + k]) * sp(pn[(size_t)j * K + c]);
@@ -937,7 +947,9 @@ int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const
 
 int nm_launch_affinity_bwd(const float* params, const float* affinity, const float* dinfl, const float* dloss, int B, int N, int K,
                            float* dparams, hipStream_t s, int ver, int graph_ver, int graph_flags) {
-    hipLaunchKernelGGL(affinity_bwd_kernel, dim3(1), dim3(256), (size_t)N * K * K * sizeof(float), s, params, affinity, dinfl, dloss, B, N, K,
+    const size_t lds = (size_t)(ver == 1 ? 3 : 1) * N * K * K * sizeof(float);
+    if (N < 1 || K < 2 || lds > 64 * 1024) { nm_set_error("affinity_bwd: N=%d K=%d unsupported", N, K); return NM_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(affinity_bwd_kernel, dim3(1), dim3(256), lds, s, params, affinity, dinfl, dloss, B, N, K,
                        ver, graph_ver, graph_flags, dparams);
     return nm_check_hip(hipGetLastError(), "affinity_bwd launch");
 }
