@@ -218,6 +218,36 @@ typedef struct nm_clip_desc {
 int nm_voxelize_batch(nm_ctx* ctx, const nm_clip_desc* clips_dev, int32_t B, int32_t T, int64_t N, int32_t J, int32_t points_f64,
                       int32_t joints_f64, float* vox, void* joints_out, int32_t* idx_out, double* bbox_out, int32_t* bad_rows);
 
+/* Device output path: thresholded voxels to ordered point sets - the host lines every consumer of the decoder's voxels starts with
+ * (vis_generation.py:137-170, vis_interpolation.py:141-177, vis/visualize.py:58-59, :130-137): binarise, np.where / torch.where per
+ * frame, divide into [-1, 1] coordinates, min_z / max_z of the last coordinate over a clip and the per-point (z - min_z) / z_len.
+ * vox (B,T,1,G,G,G) fp32 on the device, contiguous, any 4-byte alignment; G need not be the context's grid_size.  F = B T frames.
+ * Points come in np.where's order: frame after frame, inside a frame by rising flat position (i G + j) G + k.
+ *
+ * nm_occupied_count - which voxels are occupied, how many per frame, and each clip's range along the last axis.
+ *   mode NM_OCC_THRESHOLD: occupied iff NOT (v < thr) - what `x[x < thr] = 0; x[x >= thr] = 1` leaves non-zero, so a NaN is
+ *   occupied; NM_OCC_NONZERO: occupied iff v != 0 (torch.where(x); thr is ignored; NaN occupied, -0.0 empty).
+ *   bits: F * ceil(G^3 / 64) 64-bit words, caller-owned - bit j of word w of a frame is its flat voxel 64 w + j, pad bits are zero
+ *   (as bytes: np.packbits(occ, bitorder='little') per frame, padded to 8-byte multiples).  offsets (F + 1) int64: the first row of
+ *   each frame, offsets[F] = the number of points.  z_idx_range (B,2) int32: the smallest / largest last-axis index over the clip's
+ *   T frames, (INT32_MAX, -1) for a clip without a point.  z_range (B,2): the same as coordinates in the arithmetic coord_f64
+ *   selects (below), (1e4, -1) - the scripts' initial values - for a clip without a point.
+ * nm_occupied_write - the points, from the three arrays nm_occupied_count wrote (the voxels are not read again).
+ *   coord_f64 != 0: numpy's arithmetic, double(i) / ((G - 1) / 2.0) - 1.0, coords (N,3) float64; 0: torch's,
+ *   float(i) / float((G - 1) / 2.0) - 1.0f, coords (N,3) float32 (the two are not roundings of each other).  idx (N,3) int32: i, j, k.
+ *   depth (N) float64, coord_f64 != 0 only: (c_k - min_z) / (max_z - min_z) with the point's own clip's z_range; NaN where the range is
+ *   zero, as numpy gives.  Any of idx / coords / depth may be NULL.  Only rows below `capacity` are written (size the buffers by
+ *   offsets[F], or by a bound of the caller's - offsets always holds the true counts).
+ * Both are stream-ordered, synchronise nothing (but for the workspace's first growth), need no weights and give bit-identical
+ * results from run to run (no atomics).  NM_ERR_ARG: null ctx / vox / bits / offsets / z_idx_range / z_range, B, T < 1, G < 2, an
+ * unknown mode, depth with coord_f64 = 0, capacity < 0; NM_ERR_UNSUPPORTED: B T G^3 >= 2^31. */
+#define NM_OCC_THRESHOLD 0
+#define NM_OCC_NONZERO   1
+int nm_occupied_count(nm_ctx* ctx, const float* vox, int32_t B, int32_t T, int32_t G, int32_t mode, float thr, int32_t coord_f64,
+                      uint64_t* bits, int64_t* offsets, int32_t* z_idx_range, void* z_range);
+int nm_occupied_write(nm_ctx* ctx, const uint64_t* bits, const int64_t* offsets, const int32_t* z_idx_range, int32_t B, int32_t T,
+                      int32_t G, int32_t coord_f64, int64_t capacity, int32_t* idx, void* coords, double* depth);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

@@ -65,6 +65,8 @@ SIGNATURES = {
     "nm_ctx_set_graph_loss": (C.c_int, [C.c_void_p, _I, _I]),
     "nm_voxelize_clip": (C.c_int, [C.c_void_p, _P, _I, C.c_int64, C.c_double, _P, _P]),
     "nm_voxelize_batch": (C.c_int, [C.c_void_p, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "nm_occupied_count": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
+    "nm_occupied_write": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _P, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

@@ -817,14 +817,80 @@ class NeuralMarionette(nn.Module):
         return data.voxelize_batch(self, bank, ids, starts, T, sample_rate=sample_rate, scale=scale, x_trans=x_trans, z_trans=z_trans,
                                    return_joints=return_joints, return_indices=return_indices, check=check, pad=pad)
 
+    @torch.no_grad()
+    def occupied_points(self, vox, threshold=0.5, dtype=torch.float64, capacity=None, return_indices: bool = False,
+                        return_depth: bool = False, return_bits: bool = False):
+        """Device version of the host lines every consumer of the decoder's voxels starts with (vis_generation.py:137-170,
+        vis_interpolation.py:141-177, vis/visualize.py:58-59, :130-137): binarise at ``threshold``, np.where / torch.where per frame,
+        ``/ ((G - 1) / 2) - 1``, and the clip-wide min_z / max_z of the last coordinate with the shading's (z - min_z) / z_len.
+        vox: (T,1,G,G,G) - one clip - or (B,T,1,G,G,G), float32 and contiguous on the network's device; G is the tensor's and need not be
+        the network's grid.  It is not modified.  threshold: occupied iff NOT (v < threshold), what the scripts' two in-place assignments
+        leave non-zero (a NaN is occupied), the threshold rounded to float32 as torch rounds a Python number it compares a float32 tensor
+        with; None: occupied iff v != 0 (torch.where on an un-thresholded tensor).  dtype: torch.float64 - numpy's arithmetic, what the
+        vis_* scripts compute - or torch.float32 - torch's, what vis_recon computes; the two are not roundings of each other.
+        Returns a dict: coords (N,3) in np.where's order, frame after frame; offsets (F+1) int64, the first row of each of the F = B T
+        frames and the total; counts (B,T) int64; z_range (B,2), min_z / max_z per clip, (1e4, -1) for a clip without a point; indices
+        (N,3) int32 [return_indices]; depth (N) float64 [return_depth, float64 only]: (z - min_z) / (max_z - min_z) with the point's own
+        clip's range, NaN where that is zero; bits (F, 8 ceil(G^3 / 64)) uint8 [return_bits]: np.packbits(occ, bitorder='little') per
+        frame, zero-padded to whole 64-bit words.
+        capacity=None reads offsets[-1] - the call's one synchronisation - and allocates exactly N rows.  With a capacity the call
+        never synchronises and returns ``capacity`` rows, of which the first min(capacity, offsets[-1]) are written."""
+        if not isinstance(vox, torch.Tensor) or vox.dim() not in (5, 6):
+            raise ValueError("occupied_points: vox must be a (T,1,G,G,G) or (B,T,1,G,G,G) tensor" +
+                             (f", got {tuple(vox.shape)}" if isinstance(vox, torch.Tensor) else ""))
+        shape = tuple(vox.shape) if vox.dim() == 6 else (1,) + tuple(vox.shape)
+        B, T, G = shape[0], shape[1], shape[3]
+        if shape[2:] != (1, G, G, G) or G < 2 or B < 1 or T < 1:
+            raise ValueError(f"occupied_points: vox must be (T,1,G,G,G) or (B,T,1,G,G,G) with G >= 2 and at least one frame, got {tuple(vox.shape)}")
+        if vox.dtype != torch.float32:
+            raise ValueError(f"occupied_points: vox must be float32, got {vox.dtype}")
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"occupied_points: dtype must be torch.float64 (numpy's arithmetic) or torch.float32 (torch's), got {dtype}")
+        if return_depth and dtype != torch.float64:
+            raise ValueError("occupied_points: depth is float64 arithmetic (the vis_* scripts' shading): return_depth needs dtype=torch.float64")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError(f"occupied_points: capacity must be >= 0, got {capacity}")
+        if B * T * G ** 3 >= 2 ** 31:
+            raise ValueError(f"occupied_points: {B * T} frames of {G}^3 voxels, one call indexes fewer than 2^31")
+        pdev = next(self.parameters()).device
+        if not vox.is_cuda or vox.device != pdev:
+            raise ValueError(f"occupied_points: vox must be on the network's device (a HIP device; the network is on {pdev}), got {vox.device}")
+        if not vox.is_contiguous():
+            raise ValueError("occupied_points: vox must be contiguous")
+        eng = self._engine
+        ctx = eng.ready()
+        dev, F, W, f64 = ctx.device, B * T, (G ** 3 + 63) // 64, int(dtype == torch.float64)
+        bits = torch.empty(F * W, device=dev, dtype=torch.int64)
+        offsets = torch.empty(F + 1, device=dev, dtype=torch.int64)
+        zi = torch.empty(B, 2, device=dev, dtype=torch.int32)
+        zr = torch.empty(B, 2, device=dev, dtype=dtype)
+        eng.call("nm_occupied_count", _lib.ptr(vox), B, T, G, 1 if threshold is None else 0, 0.0 if threshold is None else float(threshold),
+                 f64, bits.data_ptr(), offsets.data_ptr(), _lib.ptr(zi), _lib.ptr(zr))
+        N = int(offsets[-1].item()) if capacity is None else int(capacity)
+        coords = torch.empty(N, 3, device=dev, dtype=dtype)
+        idx = torch.empty(N, 3, device=dev, dtype=torch.int32) if return_indices else None
+        depth = torch.empty(N, device=dev, dtype=torch.float64) if return_depth else None
+        if N:
+            eng.call("nm_occupied_write", bits.data_ptr(), offsets.data_ptr(), _lib.ptr(zi), B, T, G, f64, N, _lib.ptr(idx), _lib.ptr(coords),
+                     _lib.ptr(depth))
+        out = dict(coords=coords, offsets=offsets, counts=(offsets[1:] - offsets[:-1]).view(B, T), z_range=zr)
+        if return_indices:
+            out["indices"] = idx
+        if return_depth:
+            out["depth"] = depth
+        if return_bits:
+            out["bits"] = bits.view(torch.uint8).view(F, W * 8)
+        return out
+
     # -- sampling drivers (SURVEY 8(f3)): the rollout loops of the reference's demo scripts as methods ------------
     @torch.no_grad()
-    def sample_generation(self, cond_voxel, Tgen=25, sample_num=3, eps_post=None, eps_prior=None):
+    def sample_generation(self, cond_voxel, Tgen=25, sample_num=3, eps_post=None, eps_prior=None, return_points: bool = False):
         """vis_generation.py:81-136: condition on ``cond_voxel`` (Tcond,1,G,G,G) with best-of-``sample_num``
         posterior steps, then roll ``sample_num`` independent prior trajectories for ``Tgen`` steps and decode each.
         eps_post (Tcond,sample_num,Z) / eps_prior (Tgen,sample_num,Z) inject the noise.
         Returns keypoints_cond (1,Tcond,K,4) [the detected keypoints, as the script records], keypoints_gen
-        (1,Tgen,sample_num,K,4) and voxels (sample_num,Tcond+Tgen,1,G,G,G) binarised at 0.5."""
+        (1,Tgen,sample_num,K,4) and voxels (sample_num,Tcond+Tgen,1,G,G,G) binarised at 0.5.  return_points: also ``points``, the
+        script's next lines (:137-170) on the device - occupied_points(voxels_raw, 0.5, return_depth=True), a clip per sample."""
         _need_graph(self._engine.opts, "NeuralMarionette.sample_generation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
@@ -849,16 +915,21 @@ class NeuralMarionette(nn.Module):
         ff = det["first_feature"].expand(S, -1, -1, -1, -1).contiguous()
         fr = cond_voxel[None, 0].to(dev).expand(S, -1, -1, -1, -1).contiguous()
         vox = self.kypt_detector.decode_from_dyna(full, ff, fr)["gen"]
-        return dict(keypoints_cond=cond_k, keypoints_gen=gen_k, voxels=(vox >= 0.5).float(), voxels_raw=vox)
+        out = dict(keypoints_cond=cond_k, keypoints_gen=gen_k, voxels=(vox >= 0.5).float(), voxels_raw=vox)
+        if return_points:
+            out["points"] = self.occupied_points(vox, 0.5, return_depth=True)
+        return out
 
     @torch.no_grad()
-    def sample_interpolation(self, target_voxel, sample_rate=10, sample_num=10000, eps_a=None, eps_b=None, force_picks=None):
+    def sample_interpolation(self, target_voxel, sample_rate=10, sample_num=10000, eps_a=None, eps_b=None, force_picks=None,
+                             return_points: bool = False):
         """vis_interpolation.py:80-143: key frames every ``sample_rate`` steps (and the last one) are matched with a
         posterior sample, the frames in between come from the prior trajectory (out of ``sample_num``) that lands
         nearest the next key frame.  eps_a (T,sample_num,Z): the step's first draw (posterior at key frames, prior
         otherwise); eps_b (T,sample_num,Z): the second (prior, 'for choosing') draw at key frames.
         ``force_picks`` (list of (i1, i2) per key frame) replaces the two nearest-row selections (teacher forcing in tests).
-        Returns keypoints (1,T,K,4), voxels (T,1,G,G,G) binarised at 0.5, and the selected row per key frame."""
+        Returns keypoints (1,T,K,4), voxels (T,1,G,G,G) binarised at 0.5, and the selected row per key frame.  return_points: also
+        ``points``, the script's next lines (:141-177) on the device - occupied_points(voxels_raw, 0.5, return_depth=True)."""
         _need_graph(self._engine.opts, "NeuralMarionette.sample_interpolation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
@@ -895,7 +966,10 @@ class NeuralMarionette(nn.Module):
         sel = torch.stack(selected, 0)[None].clone()
         sel[0, :, :, -1] = sel[0, 0, :, -1]
         vox = self.kypt_detector.decode_from_dyna(sel, det["first_feature"], target_voxel[None, 0].to(dev))["gen"][0]
-        return dict(keypoints=sel, voxels=(vox >= 0.5).float(), voxels_raw=vox, picks=picks)
+        out = dict(keypoints=sel, voxels=(vox >= 0.5).float(), voxels_raw=vox, picks=picks)
+        if return_points:
+            out["points"] = self.occupied_points(vox.contiguous(), 0.5, return_depth=True)
+        return out
 
     @torch.no_grad()
     def sample_retarget(self, source_voxel, target_voxel, target_points, hardness=8.0, threshold=0.2, eps_source=None, eps_target=None,
@@ -1010,8 +1084,9 @@ class NeuralMarionette(nn.Module):
                    gae_recon_loss=torch.zeros((), dtype=torch.int64, device=dev), topo_recon_loss=torch.zeros((), dtype=torch.int64, device=dev), best_idx=best)
         return log
 
-    def generate(self, vox_seq, module_actives=None, eps_post=None, eps_prior=None):
-        """neural_marionette.py:58-103 ('dl' transition)."""
+    def generate(self, vox_seq, module_actives=None, eps_post=None, eps_prior=None, return_points: bool = False):
+        """neural_marionette.py:58-103 ('dl' transition).  return_points: also ``points`` = occupied_points(gen, 0.5, return_depth=True),
+        what the reference's plotting does with ``gen`` on the host."""
         if module_actives["learner"]:
             _need_graph(self._engine.opts, "NeuralMarionette.generate")
         B, T = vox_seq.shape[:2]
@@ -1026,4 +1101,6 @@ class NeuralMarionette(nn.Module):
             log.update(gen=torch.cat([det["recon"][:, :self.Tcond], gen], dim=1),
                        keypoints=torch.cat([keypoints[:, :self.Tcond], dyn["keypoints_gen"]], dim=1),
                        A_hats=None)
+            if return_points:
+                log["points"] = self.occupied_points(log["gen"], 0.5, return_depth=True)
         return log
