@@ -72,6 +72,7 @@ NmLaunchState::NmLaunchState()
       , up2y(env_int("NM355_UP2Y", 2))                      // 0: the fused-upsample layers keep the composite-weight kernel in all three axes (A/B); 1: conv_up2y_kernel (products on the coarse grid, interpolated along y) on the 64 -> 32 layer; 2: on the 128 -> 64 layer too
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
+      , up2c_shell(env_int("NM355_UP2C_SHELL", 1))          // the shell of the fused-upsample layers (split-fp16 mode, fp32 storage): 0: one line per face workgroup (A/B); 1: R lines per face workgroup (conv_up2c_face_r_kernel); 2: that and the edge items of the two-half layer with their loads in a ring (conv_up2c_edge_p_kernel: not the default, it does not clear the bar on the step); 3: the edge form alone; + 20 / 40: R = 2 / 4 at every layer (nm_up2c.hip)
 { store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
   chain_wgpoll = env_int("NM355_CHAIN_WGPOLL", 1);      // 0: every wave of the cross-XCD rollout chain polls for itself (round 5; A/B)
   chain_xcd_nogo = env_int("NM355_CHAIN_XCD_NOGO", 0);  // test hook: the one-XCD chain never starts (its fallback must do the work)

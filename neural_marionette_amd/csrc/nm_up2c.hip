@@ -1216,6 +1216,368 @@ __global__ __launch_bounds__(256, 4) void conv_up2c_edge_kernel(Up2cParams p, in
     }
 }
 
+// ---- the shell kernels of the split-fp16, fp32-storage instantiation (NM355_UP2C_SHELL, default) ---------------------------------
+// conv_up2c_face_kernel re-reads a class's 9 x Cin/16 weight k-steps (2 KB each) from L2 once per line of 32 cells: three MFMAs per
+// fetch, and the launch runs at the L2's gather rate instead of the matrix pipe's.  conv_up2c_face_r_kernel gives a workgroup R lines
+// of one (type, side, tile along the line) with adjacent across-indices f0 ... f0 + R - 1: the staged tile is R + 2 lines (the halo
+// lines are shared), a wave keeps its parity class, its weight stream and the three-deep prefetch, and one bh / bl pair feeds 3 R
+// MFMAs into R pairs of accumulators.  Per output cell nothing changes: the same operands in the same order into the same two
+// accumulators (c outer, tap inner; hi w_hi -> acc; hi w_lo, lo w_hi -> accl), the same store expression and the same partial slot
+// (one per parent line and wave, rows summed r ascending) - the two forms agree bit for bit.  What was per workgroup is per line:
+// `off` (the line lies on an edge for this class), the ownership of a row, a group that ends at the last across-index (lines
+// f >= AC are skipped, never padded; their MFMAs run on staged clamped lines and are dropped).  Under p.ypad the y faces have no
+// groups at all; their (empty) partial slots are zeroed by the workgroups of the frame, 256 floats per workgroup and round.
+template <int R> constexpr int face_r_fpv() { return (R + 2) * FP + 1; }      // slots per plane (odd)
+
+template <int R, int P>
+__global__ __launch_bounds__(256, 2) void conv_up2c_face_r_kernel(Up2cParams p, int TY, int TX) {
+    static_assert(P == 6 || P == 9, "prefetch depth: the ring index must be static in the unrolled k-loop");
+    constexpr int CU = P == 6 ? 2 : 1;                                // chunks per unrolled body (9 CU % P == 0; Cin / 16 is even)
+    constexpr int FPVR = face_r_fpv<R>();
+    extern __shared__ f32x4 lds_raw[];
+    half8* tile = reinterpret_cast<half8*>(lds_raw);               // [chunk*4 + hl*2 + h][FPVR], slot = staged line * FP + along
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, l31 = lane & 31;
+    const int GD = (p.ID + R - 1) / R, GH = (p.IH + R - 1) / R;       // line groups across z / across y
+    const int nX = 2 * p.ID * TY, nY = 2 * p.ID * TX;                // the parent's lines per frame (slot numbering)
+    const int gX = 2 * GD * TY, gY = p.ypad ? 0 : 2 * GD * TX, gZ = 2 * GH * TX, per_frame = gX + gY + gZ;
+    const int n = (int)blockIdx.x / per_frame; int g = (int)blockIdx.x % per_frame;
+    const int bricks = p.nbz * p.nby * p.nbx;
+    if (p.ypad && p.part) {
+        float* yz = p.part + (((size_t)n * p.nblk + 8 * bricks + 4 * nX) * p.Cout) * 2;
+        const int ny = nY * 4 * p.Cout * 2;
+        for (int i = g * 256 + tid; i < ny; i += per_frame * 256) yz[i] = 0.f;
+    }
+    // type 0: x face (line along y at z = f), 1: y face (along x at z = f), 2: z face (along x at y = f)
+    int type, side, f0, tl, qbase;
+    if (g < gX) { type = 0; tl = g % TY; f0 = (g / TY) % GD * R; side = g / (TY * GD); qbase = 0; }
+    else if (g < gX + gY) { g -= gX; type = 1; tl = g % TX; f0 = (g / TX) % GD * R; side = g / (TX * GD); qbase = nX; }
+    else { g -= gX + gY; type = 2; tl = g % TX; f0 = (g / TX) % GH * R; side = g / (TX * GH); qbase = nX + nY; }
+    const int LA = type == 0 ? p.IH : p.IW;                            // cells along the line's axis
+    const int AC = type == 2 ? p.IH : p.ID;                            // extent of the across axis
+    const int TL = type == 0 ? TY : TX;                                // tiles along a line
+    const int fb = side ? (type == 0 ? p.IW : type == 1 ? p.IH : p.ID) - 1 : 0;      // the face's coarse index on its own axis
+    const int C16 = p.Cin >> 4, NH = p.Cout >> 5;
+    const bool affine = p.in_scale != nullptr;
+    // ---- stage R + 2 lines x 34 voxels x Cin channels: staged line j is across-index clamp(f0 - 1 + j) ----
+    const int noct = p.Cin >> 3, nitems = (R + 2) * 34 * noct;       // (noct divides 256 - nm_launch_conv_up2c sees to it: a thread keeps its channel octet)
+    f32x4 sca = {0.f, 0.f, 0.f, 0.f}, sha = sca, scb = sca, shb = sca;
+    if (affine) {
+        const int oct = tid % noct;
+        const float* ps = p.in_scale + (size_t)n * p.Cin + oct * 8; const float* ph = p.in_shift + (size_t)n * p.Cin + oct * 8;
+        sca = *reinterpret_cast<const f32x4*>(ps); scb = *reinterpret_cast<const f32x4*>(ps + 4);
+        sha = *reinterpret_cast<const f32x4*>(ph); shb = *reinterpret_cast<const f32x4*>(ph + 4);
+    }
+    // eight items per thread and round: the loads of a round are all issued before the first of them is converted
+    constexpr int SB = 8;
+    for (int i0 = tid; i0 < nitems; i0 += 256 * SB) {
+        f32x4 va[SB], vb[SB];
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            const int i = i0 + 256 * j;
+            if (i < nitems) {
+                const int oct = i % noct, v = i / noct, s = v % 34, a = v / 34;
+                const int ca = min(max(f0 + a - 1, 0), AC - 1), cl = min(max(tl * 32 - 1 + s, 0), LA - 1);
+                const int gz = type == 2 ? fb : ca, gy = type == 0 ? cl : (type == 1 ? fb : ca), gx = type == 0 ? fb : cl;
+                ld8_raw<false>(p.in, ((((size_t)n * p.ID + gz) * p.IH + gy) * p.IW + gx) * p.Cin + oct * 8, va[j], vb[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SB; ++j) {
+            const int i = i0 + 256 * j;
+            if (i < nitems) {
+                const int oct = i % noct, v = i / noct, s = v % 34, a = v / 34;
+                half8 hi, lo;
+                split8(act4(va[j], sca, sha, affine, p.in_slope), act4(vb[j], scb, shb, affine, p.in_slope), hi, lo);
+                const int pl = (oct >> 1) * 4 + (oct & 1);
+                tile[pl * FPVR + a * FP + s] = hi;
+                tile[(pl + 2) * FPVR + a * FP + s] = lo;
+            }
+        }
+    }
+    lds_barrier();
+    // ---- this wave's parity class, rows, weights ----
+    const int pa = wave >> 1, pl_ = wave & 1;                        // parities of the across / along axes
+    int pz, py, px;
+    if (type == 0) { px = side; pz = pa; py = pl_; } else if (type == 1) { py = side; pz = pa; px = pl_; } else { pz = side; py = pa; px = pl_; }
+    const int par = pz * 4 + py * 2 + px;
+    const int S = 1 << type;
+    const int ab = pa ? AC - 1 : 0, lb = pl_ ? LA - 1 : 0;           // border indices of this class on the two in-face axes
+    const int nlines = min(R, AC - f0);                               // lines of this group that exist
+    bool any_on = false;                                              // (wave-uniform) a line that is not on an edge for this class
+#pragma unroll
+    for (int i = 0; i < R; ++i) any_on = any_on || (i < nlines && f0 + i != ab);
+    const size_t plane = (size_t)p.Co_pad, kstride = 4 * plane;
+    const int nk = 9 * C16;
+    const int OD = 2 * p.ID, OH = 2 * p.IH, OW = 2 * p.IW;
+    const int arow = h * FPVR + l31;
+    for (int nh = 0; nh < NH; ++nh) {
+        f32x16 acc[R], accl[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[i][r] = 0.f; accl[i][r] = 0.f; }
+        if (any_on) {
+            const half8* wq = p.wc + (size_t)set_tap_offset(8 + (S - 1) * 8 + par) * C16 * kstride + (size_t)h * plane + nh * 32 + l31;
+            // the weights of a k-step are requested P k-steps ahead: a wave's own stream is its only traffic in this loop, and at the
+            // L2's loaded latency (about 2 us) three k-steps of 12 MFMAs do not cover it
+            half8 bh[P], bl[P];
+#pragma unroll
+            for (int u = 0; u < P; ++u) { bh[u] = wq[(size_t)min(u, nk - 1) * kstride]; bl[u] = wq[(size_t)min(u, nk - 1) * kstride + 2 * plane]; }
+            for (int c0 = 0; c0 < C16; c0 += CU) {
+#pragma unroll
+                for (int tt = 0; tt < 9 * CU; ++tt) {
+                    const int c = c0 + tt / 9, t = tt % 9;
+                    const int k = c * 9 + t, s = tt % P;
+                    // (the row base is opaque per k-step: lines i and i + 1 read the same staged line at taps three apart, and merged
+                    //  reads held across k-steps cost more registers than the kernel has)
+                    int ar = arow + c * 4 * FPVR;
+                    asm volatile("" : "+v"(ar));
+                    half8 ah[R], al[R];
+#pragma unroll
+                    for (int i = 0; i < R; ++i) {
+                        ah[i] = tile[ar + (i + t / 3) * FP + (t % 3)];
+                        al[i] = tile[ar + 2 * FPVR + (i + t / 3) * FP + (t % 3)];
+                    }
+                    const half8 wh = bh[s], wl = bl[s];
+                    const int kn = min(k + P, nk - 1);
+                    bh[s] = wq[(size_t)kn * kstride]; bl[s] = wq[(size_t)kn * kstride + 2 * plane];
+#pragma unroll
+                    for (int i = 0; i < R; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], wh, acc[i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < R; ++i) accl[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], wl, accl[i], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < R; ++i) accl[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], wh, accl[i], 0, 0, 0);
+                }
+            }
+        }
+        const int co = nh * 32 + l31;
+        // element index of row rho of line f: base + f * across + (tl * 32 + rho) * along (the parent's index, term by term)
+        const size_t sX = (size_t)p.Cout, sY = (size_t)OW * sX, sZ = (size_t)OH * sY;
+        const size_t along = 2 * (type == 0 ? sY : sX), across = 2 * (type == 2 ? sY : sZ);
+        const size_t lane_base = (size_t)n * OD * sZ + pz * sZ + py * sY + px * sX + 2 * fb * (type == 0 ? sX : type == 1 ? sY : sZ) + co +
+                                 (size_t)(tl * 32 + 4 * h) * along;
+        // the old values of all lines in one batch of loads (one load-add-store round trip per output half, not one per row)
+        float old[R][16];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const bool on = i < nlines && f0 + i != ab;               // (off: the whole line lies on an edge for this class)
+            const size_t line_base = lane_base + (size_t)(f0 + i) * across;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int u = tl * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                old[i][r] = 0.f;
+                if (on && u < LA && u != lb) old[i][r] = nm_ld1<false>(p.out, line_base + (size_t)((r & 3) + 8 * (r >> 2)) * along);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if (i >= nlines) break;
+            const int f = f0 + i;
+            const bool off = f == ab;
+            const size_t line_base = lane_base + (size_t)f * across;
+            float s = 0.f, ss = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rho = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int u = tl * 32 + rho;
+                if (!off && u < LA && u != lb) {
+                    const size_t dst = line_base + (size_t)((r & 3) + 8 * (r >> 2)) * along;
+                    const float v = old[i][r] + (acc[i][r] + accl[i][r] * (1.0f / UP2C_SPLIT_SCALE));
+                    nm_st1<false>(p.out, dst, v);
+                    s += v; ss += v * v;
+                }
+            }
+            if (p.part) {
+                s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+                const int slot_part = 8 * bricks + (qbase + (side * AC + f) * TL + tl) * 4 + wave;
+                if (h == 0) { float* dst = p.part + (((size_t)n * p.nblk + slot_part) * p.Cout + co) * 2; dst[0] = s; dst[1] = ss; }
+            }
+        }
+    }
+}
+
+// conv_up2c_edge_p_kernel: conv_up2c_edge_kernel's items and arithmetic with the loads kept in flight.  An item's work is a sequence
+// of tap groups (subset S ascending, 16-channel chunk ascending, taps in threes ascending); the loads of the groups g + 1 ... g + 3 -
+// three A octet pairs and the weights of BOTH 32-channel output halves each - are in flight in a ring of four register sets during
+// the MFMAs of group g (one wave per SIMD: the registers are there, the parallelism is not).  For the layers with two output halves
+// (Cout = 64); NM355_UP2C_SHELL=2 / 3 only, not the default (it does not clear the bar on the step).  The A operands are
+// activated and split once and feed both halves' accumulators.  The pending GroupNorm scale / shift of the frame are copied to LDS
+// once per wave (wave-private rows: no workgroup barrier) and read from there with each group's loads.  Per accumulator the MFMA
+// sequence is conv_up2c_edge_kernel's.
+__global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, int TZ, int TY, int TX, int slot0) {
+    constexpr int NHT = 2;                                             // output halves
+    __shared__ __attribute__((aligned(16))) float aff[4][2][128];                                  // [wave][scale | shift][channel] (Cin <= 128: nm_up2c_eligible)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, l31 = lane & 31;
+    const int nXY = 8 * TZ, nXZ = 8 * TY, nYZ = 8 * TX, per_frame = nXY + nXZ + nYZ;
+    const long long gitem = (long long)blockIdx.x * 4 + wave;
+    if (gitem >= (long long)p.N * per_frame) return;
+    const int n = (int)(gitem / per_frame); int q = (int)(gitem % per_frame);
+    const int slot = slot0 + q;
+    // type 0: x-y edge (line along z), 1: x-z edge (along y), 2: y-z edge (along x); q -> (tile, parity class)
+    int type, tile, par;
+    if (q < nXY) { type = 0; tile = q / 8; par = q % 8; }
+    else if (q < nXY + nXZ) { q -= nXY; type = 1; tile = q / 8; par = q % 8; }
+    else { q -= nXY + nXZ; type = 2; tile = q / 8; par = q % 8; }
+    const int pz = par >> 2, py = (par >> 1) & 1, px = par & 1;
+    const int xb = px ? p.IW - 1 : 0, yb = py ? p.IH - 1 : 0, zb = pz ? p.ID - 1 : 0;
+    auto cell = [&](int rho, int& iz, int& iy, int& ix, bool& owned, int& bset) {
+        const int u = tile * 32 + rho;
+        if (type == 0) { iz = u; iy = yb; ix = xb; owned = u < p.ID; }
+        else if (type == 1) { iz = zb; iy = u; ix = xb; owned = u < p.IH && u != yb; }
+        else { iz = zb; iy = yb; ix = u; owned = u < p.IW && u != xb; }
+        iz = min(iz, p.ID - 1); iy = min(iy, p.IH - 1); ix = min(ix, p.IW - 1);
+        bset = (ix == xb ? 1 : 0) | (iy == yb ? 2 : 0) | (iz == zb ? 4 : 0);
+    };
+    int iz, iy, ix, bset; bool owned;
+    cell(l31, iz, iy, ix, owned, bset);
+    const int C16 = p.Cin >> 4;
+    const size_t plane = (size_t)p.Co_pad, kstride = 4 * plane;
+    const bool affine = p.in_scale != nullptr;
+    const int OD = 2 * p.ID, OH = 2 * p.IH, OW = 2 * p.IW;
+    if (affine) {
+        for (int i = lane; i < p.Cin; i += 64) {
+            aff[wave][0][i] = p.in_scale[(size_t)n * p.Cin + i];
+            aff[wave][1][i] = p.in_shift[(size_t)n * p.Cin + i];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // the wave's own rows: written before any lane of it reads them
+    }
+    // the subsets with a row to correct (wave-uniform), ascending
+    unsigned smask = 0;
+#pragma unroll
+    for (int S = 1; S < 8; ++S) {
+        const bool rowon = owned && (bset & S) == S;
+        if (__ballot(rowon) != 0ull && !(p.ypad && S == 2)) smask |= 1u << S;      // ({y} alone: left out by the main kernel's epilogue already)
+    }
+    smask = __builtin_amdgcn_readfirstlane(smask);
+    f32x16 acc[NHT], accl[NHT];
+#pragma unroll
+    for (int nh = 0; nh < NHT; ++nh)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[nh][r] = 0.f; accl[nh][r] = 0.f; }
+
+    struct It { int S, c, t0, ntaps; size_t wbase; };                  // a tap group; wbase: the set's offset in half8 units
+    struct Regs { f32x4 va[3], vb[3], sca, scb, sha, shb; half8 wh[3][NHT], wl[3][NHT]; int S, t0, ntaps; };
+    auto enter = [&](It& it, int S) {
+        // set_tap_offset(8 + (S - 1) * 8 + par) = 216 + 8 * (taps of the subsets below S) + par * taps(S), from two packed tables
+        // (taps 9 9 3 9 3 3 1 for S = 1 ... 7; their running sums 0 9 18 21 30 33 36)
+        const int nt = (int)((0x1339399ull >> (4 * (S - 1))) & 15), below = (int)((0x2485e552240ull >> (6 * (S - 1))) & 63);
+        it.S = S; it.c = 0; it.t0 = 0; it.ntaps = nt;
+        it.wbase = (size_t)(216 + 8 * below + par * nt) * C16 * kstride;
+    };
+    auto advance = [&](It& it) {                                       // false (and `it` unchanged) behind the last group
+        if (it.t0 + 3 < it.ntaps) { it.t0 += 3; return true; }
+        if (it.c + 1 < C16) { ++it.c; it.t0 = 0; return true; }
+        const unsigned rest = smask >> (it.S + 1);
+        if (rest == 0) return false;
+        enter(it, it.S + 1 + __builtin_ctz(rest));
+        return true;
+    };
+    // element offsets of the lane's three clamped neighbours per axis, once: a tap's address is three selects and three adds
+    auto eoff = [&](int i, int k, int ext, size_t stride) { return (size_t)min(max(i + k, 0), ext - 1) * stride; };
+    const size_t sx = (size_t)p.Cin, sy = (size_t)p.IW * sx, sz = (size_t)p.IH * sy;
+    const size_t z0 = eoff(iz, -1, p.ID, sz), z1 = eoff(iz, 0, p.ID, sz), z2 = eoff(iz, 1, p.ID, sz);
+    const size_t y0 = eoff(iy, -1, p.IH, sy), y1 = eoff(iy, 0, p.IH, sy), y2 = eoff(iy, 1, p.IH, sy);
+    const size_t x0 = eoff(ix, -1, p.IW, sx), x1 = eoff(ix, 0, p.IW, sx), x2 = eoff(ix, 1, p.IW, sx);
+    const size_t in_base = (size_t)n * p.ID * sz;
+    auto pick = [](size_t a, size_t b, size_t c, int d) { return d < 0 ? a : d == 0 ? b : c; };
+    auto load = [&](Regs& g, const It& it) __attribute__((always_inline)) {
+        g.S = it.S; g.t0 = it.t0; g.ntaps = it.ntaps;
+        const int cbase = it.c * 16 + 8 * h;
+        const half8* wq = p.wc + it.wbase + (size_t)h * plane + l31;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int t = min(it.t0 + u, it.ntaps - 1);
+            int d[3] = {0, 0, 0}, qd = t;                              // x, y, z offsets
+#pragma unroll
+            for (int a = 0; a < 3; ++a) if (!((it.S >> a) & 1)) { d[a] = qd % 3 - 1; qd /= 3; }
+            ld8_raw<false>(p.in, in_base + pick(z0, z1, z2, d[2]) + pick(y0, y1, y2, d[1]) + pick(x0, x1, x2, d[0]) + cbase, g.va[u], g.vb[u]);
+            const half8* wt = wq + ((size_t)it.c * it.ntaps + t) * kstride;
+#pragma unroll
+            for (int nh = 0; nh < NHT; ++nh) { g.wh[u][nh] = wt[nh * 32]; g.wl[u][nh] = wt[2 * plane + nh * 32]; }
+        }
+        if (affine) {
+            g.sca = *reinterpret_cast<const f32x4*>(&aff[wave][0][cbase]); g.scb = *reinterpret_cast<const f32x4*>(&aff[wave][0][cbase + 4]);
+            g.sha = *reinterpret_cast<const f32x4*>(&aff[wave][1][cbase]); g.shb = *reinterpret_cast<const f32x4*>(&aff[wave][1][cbase + 4]);
+        } else {
+            g.sca = g.scb = g.sha = g.shb = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto consume = [&](const Regs& g) __attribute__((always_inline)) {
+        const bool rowon = owned && (bset & g.S) == g.S;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            if (g.t0 + u < g.ntaps) {
+                f32x4 xa = act4(g.va[u], g.sca, g.sha, affine, p.in_slope), xb2 = act4(g.vb[u], g.scb, g.shb, affine, p.in_slope);
+                if (!rowon) { xa = f32x4{0.f, 0.f, 0.f, 0.f}; xb2 = xa; }
+                half8 hi, lo;
+                split8(xa, xb2, hi, lo);
+#pragma unroll
+                for (int nh = 0; nh < NHT; ++nh) acc[nh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hi, g.wh[u][nh], acc[nh], 0, 0, 0);
+#pragma unroll
+                for (int nh = 0; nh < NHT; ++nh) accl[nh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hi, g.wl[u][nh], accl[nh], 0, 0, 0);
+#pragma unroll
+                for (int nh = 0; nh < NHT; ++nh) accl[nh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(lo, g.wh[u][nh], accl[nh], 0, 0, 0);
+            }
+        }
+    };
+    if (smask) {
+        // NSET register sets in a ring: group g is consumed with the loads of g + 1 ... g + NSET - 1 in flight.  The loads are
+        // unconditional (behind the last group its own are issued again and dropped), so that the wait in front of a group's
+        // MFMAs counts exactly the loads of the groups after it.
+        constexpr int NSET = 4;
+        int ngroups = 0;
+#pragma unroll
+        for (int S = 1; S < 8; ++S) if ((smask >> S) & 1) ngroups += C16 * ((axes_taps(S) + 2) / 3);
+        It it; enter(it, __builtin_ctz(smask));
+        Regs g[NSET];
+        load(g[0], it);
+#pragma unroll
+        for (int j = 1; j < NSET - 1; ++j) { advance(it); load(g[j], it); }
+        for (int base = 0; base < ngroups; base += NSET) {
+#pragma unroll
+            for (int j = 0; j < NSET; ++j) {
+                advance(it);
+                load(g[(j + NSET - 1) % NSET], it);
+                if (base + j < ngroups) consume(g[j]);
+            }
+        }
+    }
+    // add to the main kernel's values, partial sums of the final values; the old values of both halves in one batch of loads
+    float old[NHT][16];
+#pragma unroll
+    for (int nh = 0; nh < NHT; ++nh)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            int rz, ry, rx, rb; bool ro;
+            cell((r & 3) + 8 * (r >> 2) + 4 * h, rz, ry, rx, ro, rb);
+            old[nh][r] = 0.f;
+            if (ro) old[nh][r] = nm_ld1<false>(p.out, ((((size_t)n * OD + 2 * rz + pz) * OH + 2 * ry + py) * OW + 2 * rx + px) * p.Cout + nh * 32 + l31);
+        }
+#pragma unroll
+    for (int nh = 0; nh < NHT; ++nh) {
+        float s = 0.f, ss = 0.f;
+        const int co = nh * 32 + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rho = (r & 3) + 8 * (r >> 2) + 4 * h;
+            int rz, ry, rx, rb; bool ro;
+            cell(rho, rz, ry, rx, ro, rb);
+            if (ro) {
+                const size_t dst = ((((size_t)n * OD + 2 * rz + pz) * OH + 2 * ry + py) * OW + 2 * rx + px) * p.Cout + co;
+                const float v = old[nh][r] + (acc[nh][r] + accl[nh][r] * (1.0f / UP2C_SPLIT_SCALE));
+                nm_st1<false>(p.out, dst, v);
+                s += v; ss += v * v;
+            }
+        }
+        if (p.part) {
+            s += __shfl_xor(s, 32); ss += __shfl_xor(ss, 32);
+            if (h == 0) { float* dst = p.part + (((size_t)n * p.nblk + slot) * p.Cout + co) * 2; dst[0] = s; dst[1] = ss; }
+        }
+    }
+}
+
 int g_cus = 0;
 
 }  // namespace
@@ -1262,6 +1624,8 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_face_r_kernel<2, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_face_r_kernel<4, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_up2c)");
         attr_set.mark();
     }
@@ -1311,7 +1675,20 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     int TZ, TY, TX; shell_tiles(in.D, in.H, in.W, TZ, TY, TX);
     const int fg = face_groups(in.D, in.H, in.W), ei = edge_items(in.D, in.H, in.W);
     const size_t face_lds = (size_t)(in.C / 16 * 4) * FPV * 16;
-    if (io == 3) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 3>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
+    // NM355_UP2C_SHELL (split-fp16, fp32 storage only; the one-product and 16-bit-storage instantiations keep the kernels below):
+    // units 0 the kernels below (A/B), 1 the face form (default), 2 the face and the edge form, 3 the edge form alone; tens: lines
+    // per face workgroup (2 or 4; else 4 at Cin <= 64 and 2 above: DESIGN 5).  The face form fixes a thread's channel octet across
+    // its staging items, so it takes the channel counts whose octets divide 256; any other keeps the kernel below.
+    const int shell = (io == 0 && !single) ? nm_ls().up2c_shell : 0;
+    const bool face_r = (shell % 10 == 1 || shell % 10 == 2) && 256 % (in.C / 8) == 0, edge_p = shell % 10 == 2 || shell % 10 == 3;
+    if (face_r) {
+        const int R = shell / 10 == 2 ? 2 : shell / 10 == 4 ? 4 : in.C <= 64 ? 4 : 2;
+        const int GD = (in.D + R - 1) / R, GH = (in.H + R - 1) / R;
+        const int groups = 2 * GD * TY + (p.ypad ? 0 : 2 * GD * TX) + 2 * GH * TX;
+        if (R == 2) hipLaunchKernelGGL((conv_up2c_face_r_kernel<2, 9>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<2>() * 16, s, p, TY, TX);
+        else hipLaunchKernelGGL((conv_up2c_face_r_kernel<4, 6>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<4>() * 16, s, p, TY, TX);
+    }
+    else if (io == 3) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 3>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
     else if (io == 2) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 2>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
     else if (io == 1) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 1>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
     else if (single) hipLaunchKernelGGL(conv_up2c_face_kernel<true>, dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
@@ -1319,7 +1696,10 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     rc = nm_check_hip(hipGetLastError(), "conv_up2c_face launch");
     if (rc) return rc;
     const long long items = (long long)p.N * ei;
-    if (io == 3) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 3>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+    // (one output half: the ring's registers leave one wave per SIMD, and 1.5 items per SIMD then run in two rounds - measured
+    //  slower than conv_up2c_edge_kernel on the 64 -> 32 layer, which keeps it)
+    if (edge_p && Cout == 64) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+    else if (io == 3) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 3>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
     else if (io == 2) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 2>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
     else if (io == 1) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 1>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
     else if (single) hipLaunchKernelGGL(conv_up2c_edge_kernel<true>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
