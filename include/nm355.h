@@ -518,7 +518,11 @@ int nm_op_volfit_gauss_backward(nm_ctx* ctx, const float* vox, const float* keyp
  * master weights, GroupNorm statistics / scale / shift, every partial sum and accumulator, the losses and the Adam state stay fp32,
  * as do the tensors below 32^3 (the hourglass, heads, keypoints) and the inference forward (which keeps mode 3's fp32 workspace).
  * Halves the training arena and the bytes of the GroupNorm-backward passes; gradients agree with the fp64 oracle to a few 1e-2 in
- * whole-gradient L2 (tests state the bound). */
+ * whole-gradient L2 (tests state the bound).  A training step keeps all B * T frames in one pass, at any frame count: the 3x3x3 weight
+ * gradient of bfloat16 operands runs on wgrad16z_kernel alone, whose per-frame scale / shift table in LDS holds 96 frames, so above
+ * 96 frames it is launched once per group of at most 96 frames (equal groups, e.g. 240 = 3 x 80), each group on its own partial-sum
+ * slots, and one fixed-order reduce sums all slots: no atomics, run-to-run bit-identical, the workspace grows with the group count;
+ * up to 96 frames the single launch and its bits are unchanged.  (The fp32-storage modes run wgrad16_kernel above 96 frames.) */
 int nm_set_conv_mode(nm_ctx* ctx, int32_t mode);
 int nm_get_conv_mode(nm_ctx* ctx);
 /* Element type of the tensors the op-level entry points below (nm_op_*) read and write, for unit parity of the 16-bit storage kernels

@@ -2399,6 +2399,19 @@ bool wgrad16_eligible(int OD, int OH, int OW, int ks, int stride) {
     return ks == 3 && stride == 1 && OD % 2 == 0 && OH % 8 == 0 && OW % 8 == 0;
 }
 
+// wgrad16t/u/z_kernel keep the per-frame scale / shift rows of their input in LDS (256 B per frame): at 96 frames wgrad16t/u ask for
+// 159808 of the 163840 B.  Bfloat16 operands exist on wgrad16z_kernel only, so above that count launch_wgrad16 runs it once per group
+// of at most W16_TAB_FRAMES frames (equal groups: 97 frames are 49 + 48, not 96 + 1), every group on its own range of partial-sum slots.
+#define W16_TAB_FRAMES 96
+int w16_group_frames(int N) { const int groups = (N + W16_TAB_FRAMES - 1) / W16_TAB_FRAMES; return (N + groups - 1) / groups; }
+// slots of all groups together: a group has no more workgroups per tile pair than (frame, y, x) columns
+int w16_group_slots(int N, int S, int cols_per_frame) {
+    const int gf = w16_group_frames(N);
+    int slots = 0;
+    for (int f0 = 0; f0 < N; f0 += gf) slots += max(1, min(S, min(gf, N - f0) * cols_per_frame));
+    return slots;
+}
+
 WgradPlan plan_wgrad(int N, int OD, int OH, int OW, int M, int Nc, int ks, int stride, bool k5occ, bool f16 = false) {
     WgradPlan q;
     WgradParams& p = q.p;
@@ -2417,8 +2430,13 @@ WgradPlan plan_wgrad(int N, int OD, int OH, int OW, int M, int Nc, int ks, int s
         const int wgs = nm_ls().wgrad_wgs > 0 ? nm_ls().wgrad_wgs : (nm_ls().wgrad_async == 1 && !nm_ls().single ? 224 : 256);
         p.S = max(1, min(total, max(tiles, wgs) / tiles));
         // wgrad16z_kernel hands out whole (frame, y, x) columns: no more workgroups per tile pair than columns
-        if (nm_ls().wgrad_tr && nm_ls().wgrad_z && p.nbz >= 2 && N <= 96) p.S = max(1, min(p.S, N * p.nby * p.nbx));
-        q.slots = p.S; q.lds = W16_LDS; q.ws_floats = (size_t)q.slots * tiles * 27 * 1024;
+        if (nm_ls().wgrad_tr && nm_ls().wgrad_z && p.nbz >= 2 && N <= W16_TAB_FRAMES) p.S = max(1, min(p.S, N * p.nby * p.nbx));
+        q.slots = p.S; q.lds = W16_LDS;
+        // 16-bit storage above W16_TAB_FRAMES frames: one wgrad16z launch per frame group, each with its own slots (launch_wgrad16)
+        int ws_slots = q.slots;
+        if (nm_ls().store16 && nm_ls().wgrad_tr && nm_ls().wgrad_z && p.nbz >= 2 && N > W16_TAB_FRAMES)
+            ws_slots = max(ws_slots, w16_group_slots(N, p.S, p.nby * p.nbx));
+        q.ws_floats = (size_t)ws_slots * tiles * 27 * 1024;
         return q;
     }
     if (stride == 2) { bz = 2; by = 4; bx = 8; }
@@ -2458,14 +2476,57 @@ int launch_wgrad_t(const WgradPlan& q, hipStream_t s) {
 }
 
 
-int launch_wgrad16(const WgradPlan& q, hipStream_t s) {
+int w16z_set_attr() {
+    static NmDeviceOnce attr_z;
+    if (!attr_z.done()) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+            nm_set_error("wgrad16z: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
+        }
+        attr_z.mark();
+    }
+    return NM_OK;
+}
+
+// q.slots: the partial-sum slots the launch filled (the fixed-order reduce of run_wgrad walks them all)
+int launch_wgrad16(WgradPlan& q, hipStream_t s) {
     // 16-bit storage: both operands bfloat16, on the z-walking kernel only (every layer of >= 32^3 voxels has nbz >= 16)
     const bool h16 = q.p.in.h || q.p.dy.h;
-    if (h16 && !(q.p.in.h && q.p.dy.h && nm_conv_single() && nm_ls().wgrad_tr && nm_ls().wgrad_z && q.p.nbz >= 2 && q.p.in.N <= 96)) {
+    // (above W16_TAB_FRAMES frames plan_wgrad sized the partial sums for the frame groups in the storage mode only)
+    if (h16 && !(q.p.in.h && q.p.dy.h && nm_conv_single() && nm_ls().wgrad_tr && nm_ls().wgrad_z && q.p.nbz >= 2 &&
+                 (q.p.in.N <= W16_TAB_FRAMES || nm_ls().store16))) {
         nm_set_error("wgrad16: bfloat16 operands (in %d, dy %d) need conv mode 4, both tensors bfloat16 and the wgrad16z kernel", q.p.in.h, q.p.dy.h);
         return NM_ERR_UNSUPPORTED;
     }
-    if (nm_ls().wgrad_tr && q.p.in.N <= 96) {                       // (the per-frame scale / shift table of wgrad16t_kernel lives in LDS: 256 B per frame)
+    if (h16 && q.p.in.N > W16_TAB_FRAMES) {
+        // more frames than table rows: one launch per frame group - the group's frames as a tensor of their own (data and scale / shift
+        // rows offset by its first frame), its partials behind those of the groups before it.  Groups and slots in a fixed order, one
+        // reduce over all of them: deterministic, no atomics.
+        if (int rc = w16z_set_attr()) return rc;
+        const int N = q.p.in.N, gf = w16_group_frames(N), tiles = q.m_tiles * q.p.n_tiles;
+        const size_t xframe = (size_t)q.p.in.D * q.p.in.H * q.p.in.W * q.p.in.C, dframe = (size_t)q.p.dy.D * q.p.dy.H * q.p.dy.W * q.p.dy.C;
+        int slot0 = 0;
+        for (int f0 = 0; f0 < N; f0 += gf) {
+            WgradParams pz = q.p;
+            const int n = min(gf, N - f0);
+            pz.in.N = pz.dy.N = n;
+            pz.in.p = nm_eptr(q.p.in.p, f0 * xframe, q.p.in.h); pz.dy.p = nm_eptr(q.p.dy.p, f0 * dframe, q.p.dy.h);
+            if (pz.in.scale) { pz.in.scale += (size_t)f0 * pz.in.C; pz.in.shift += (size_t)f0 * pz.in.C; }
+            if (pz.dy.scale) { pz.dy.scale += (size_t)f0 * pz.dy.C; pz.dy.shift += (size_t)f0 * pz.dy.C; }
+            pz.S = max(1, min(q.p.S, n * pz.nby * pz.nbx));
+            pz.part = q.p.part + (size_t)slot0 * tiles * 27 * 1024;
+            const size_t ldsz = WZ_LDS + (size_t)n * 64 * sizeof(float) + 64 + 256;
+            hipLaunchKernelGGL((wgrad16z_kernel<0, true, true>), dim3(pz.S, tiles), dim3(512), ldsz, s, pz);
+            if (int rc = nm_check_hip(hipGetLastError(), "wgrad16z launch")) return rc;
+            slot0 += pz.S;
+        }
+        q.slots = slot0;
+        return NM_OK;
+    }
+    if (nm_ls().wgrad_tr && q.p.in.N <= W16_TAB_FRAMES) {                       // (the per-frame scale / shift table of wgrad16t_kernel lives in LDS: 256 B per frame)
         static NmDeviceOnce attr_t;
         if (!attr_t.done()) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16t_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
@@ -2486,17 +2547,7 @@ int launch_wgrad16(const WgradPlan& q, hipStream_t s) {
         const size_t ldsb = WT_LDS + (size_t)q.p.in.N * 64 * sizeof(float) + 64;
         const dim3 grid(q.p.S, q.m_tiles * q.p.n_tiles);
         if (nm_ls().wgrad_z && q.p.nbz >= 2) {
-            static NmDeviceOnce attr_z;
-            if (!attr_z.done()) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                    nm_set_error("wgrad16z: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-                }
-                attr_z.mark();
-            }
+            if (int rc = w16z_set_attr()) return rc;
             const WgradParams& pz = q.p;                  // (plan_wgrad bounded S by the column count)
             const size_t ldsz = WZ_LDS + (size_t)q.p.in.N * 64 * sizeof(float) + 64 + 256;   // tiles, X affine table, dummy item, dY affine table
             const dim3 gz(pz.S, q.m_tiles * q.p.n_tiles);
