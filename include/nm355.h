@@ -248,6 +248,36 @@ int nm_occupied_count(nm_ctx* ctx, const float* vox, int32_t B, int32_t T, int32
 int nm_occupied_write(nm_ctx* ctx, const uint64_t* bits, const int64_t* offsets, const int32_t* z_idx_range, int32_t B, int32_t T,
                       int32_t G, int32_t coord_f64, int64_t capacity, int32_t* idx, void* coords, double* depth);
 
+/* ---- surface path: normals, plate frames and shading of those points (vis_generation.py:157-171, vis_interpolation.py:160-177: open3d's
+ * estimate_normals + orient_normals_consistent_tangent_plane, then the scripts' per-point loop with drawPlate :27-44) ----
+ * nm_occupied_surface takes the three arrays nm_occupied_count wrote (the voxels are not read again) and writes one row per point, in
+ * nm_occupied_write's order; only rows below `capacity` are written, any output may be NULL.  For the point p = (i, j, k) of frame f:
+ *   neighbourhood  the occupied voxels q of the same frame, inside the grid, with |q - p|^2 <= radius2 (1 .. 16), p itself included.
+ *   moments (N,10) int32, exact: with d = q - p: n, S = sum d (x, y, z), Q = sum d d^T (xx, xy, xz, yy, yz, zz).
+ *   normals (N,3) float64: C = n Q - S S^T is an exact integer matrix; the unit eigenvector of its smallest eigenvalue, solved in float64.
+ *     n < 3: (0, 0, 1), as open3d gives a neighbourhood without extent.  spread (N,3) float64: C's eigenvalues, ascending.
+ *   orientation  NM_SURF_OUTWARD: n . o >= 0 for o = -S, away from the local mass; if S = 0 as integers, o = N_f p - sum_f q, away from
+ *     the frame's centroid; if that is 0 too, o = (1, 1, 1); a dot product of exactly 0.0 leaves the solver's sign.  NM_SURF_TOWARDS:
+ *     n is flipped when n . (orient_point[b] - coords(p)) < 0, orient_point (B,3) float64 on the device - open3d's
+ *     orient_normals_towards_camera_location - with coords as nm_occupied_write's float64 arithmetic gives them.
+ *   plates (N,3,4) float64: rows [R | centre] of drawPlate's transform for centre = coords(p) and the oriented normal:
+ *     line2 = n / (|n| + 1e-6), c = line2_z + 1e-8, R = I + K + K^2 / (1 + c), and R = diag(-1, 1, -1) where |c + 1| < 1e-4.
+ *   colors (N,3) float64: base[f] * (depth * shade_a + shade_b) (+ add[f] when add is not NULL), base / add (F,3) float64 on the
+ *     device, depth as nm_occupied_write defines it (NaN where the clip's range is zero), in numpy's operation order, unfused.
+ * These are NOT open3d's normals: on a voxel lattice its 30-nearest-neighbour set is cut inside a shell of equidistant points by the
+ * tie-breaking of its k-d tree, so the neighbourhood here is the lattice ball above and the result is defined by this text alone.
+ * Stream-ordered, synchronises nothing (but for the workspace's first growth), needs no weights, bit-identical from run to run (no
+ * atomics).  NM_ERR_ARG: radius2 outside 1 .. 16 (judged first, before the context), null ctx / bits / offsets / z_idx_range, an unknown
+ * orient, NM_SURF_TOWARDS with normals or plates but no orient_point (moments, spread and colors take no orientation: with only those
+ * outputs orient_point is never read and may be NULL), colors without base, B, T < 1, G < 2, capacity < 0; NM_ERR_UNSUPPORTED:
+ * B T G^3 >= 2^31. */
+#define NM_SURF_OUTWARD 0
+#define NM_SURF_TOWARDS 1
+int nm_occupied_surface(nm_ctx* ctx, const uint64_t* bits, const int64_t* offsets, const int32_t* z_idx_range, int32_t B, int32_t T,
+                        int32_t G, int32_t radius2, int32_t orient, const double* orient_point, const double* base, const double* add,
+                        double shade_a, double shade_b, int64_t capacity, int32_t* moments, double* normals, double* spread,
+                        double* plates, double* colors);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

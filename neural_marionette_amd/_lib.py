@@ -67,6 +67,7 @@ SIGNATURES = {
     "nm_voxelize_batch": (C.c_int, [C.c_void_p, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nm_occupied_count": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
     "nm_occupied_write": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _P, _P, _P]),
+    "nm_occupied_surface": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

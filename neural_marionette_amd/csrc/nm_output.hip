@@ -290,7 +290,7 @@ __global__ __launch_bounds__(NM_OUT_BLOCK) void occ_write_kernel(const unsigned 
     }
 }
 
-struct OutGeom { int F, V, W, nC; };
+using OutGeom = NmOutGeom;
 // NM_ERR_ARG / NM_ERR_UNSUPPORTED of the shapes, else the launch geometry
 int out_geom(const char* who, int B, int T, int G, OutGeom* g) {
     if (B < 1 || T < 1 || G < 2) { nm_set_error("%s: B = %d clips, T = %d frames, G = %d", who, B, T, G); return NM_ERR_ARG; }
@@ -304,6 +304,12 @@ int out_geom(const char* who, int B, int T, int G, OutGeom* g) {
 }
 
 }  // namespace
+
+// for nm_surface.hip (nm_output.h)
+int nm_out_geom(const char* who, int B, int T, int G, NmOutGeom* g) { return out_geom(who, B, T, G, g); }
+void nm_out_launch_chunk_scan(hipStream_t s, const unsigned long long* bits, const NmOutGeom& g, int32_t* coff) {
+    hipLaunchKernelGGL(occ_chunk_scan_kernel, dim3((unsigned)g.F), dim3(NM_OUT_BLOCK), 0, s, bits, g.W, g.nC, coff);
+}
 
 extern "C" {
 

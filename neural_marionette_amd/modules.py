@@ -835,28 +835,32 @@ class NeuralMarionette(nn.Module):
         frame, zero-padded to whole 64-bit words.
         capacity=None reads offsets[-1] - the call's one synchronisation - and allocates exactly N rows.  With a capacity the call
         never synchronises and returns ``capacity`` rows, of which the first min(capacity, offsets[-1]) are written."""
+        return self._occupied("occupied_points", vox, threshold, dtype, capacity, return_indices, return_depth, return_bits)[0]
+
+    def _occupied(self, who, vox, threshold, dtype, capacity, return_indices, return_depth, return_bits):
+        """occupied_points for the shell ``who``: its dict, and (B, T, G, bits, z_idx_range) for a second library call on the same masks"""
         if not isinstance(vox, torch.Tensor) or vox.dim() not in (5, 6):
-            raise ValueError("occupied_points: vox must be a (T,1,G,G,G) or (B,T,1,G,G,G) tensor" +
+            raise ValueError(f"{who}: vox must be a (T,1,G,G,G) or (B,T,1,G,G,G) tensor" +
                              (f", got {tuple(vox.shape)}" if isinstance(vox, torch.Tensor) else ""))
         shape = tuple(vox.shape) if vox.dim() == 6 else (1,) + tuple(vox.shape)
         B, T, G = shape[0], shape[1], shape[3]
         if shape[2:] != (1, G, G, G) or G < 2 or B < 1 or T < 1:
-            raise ValueError(f"occupied_points: vox must be (T,1,G,G,G) or (B,T,1,G,G,G) with G >= 2 and at least one frame, got {tuple(vox.shape)}")
+            raise ValueError(f"{who}: vox must be (T,1,G,G,G) or (B,T,1,G,G,G) with G >= 2 and at least one frame, got {tuple(vox.shape)}")
         if vox.dtype != torch.float32:
-            raise ValueError(f"occupied_points: vox must be float32, got {vox.dtype}")
+            raise ValueError(f"{who}: vox must be float32, got {vox.dtype}")
         if dtype not in (torch.float64, torch.float32):
-            raise ValueError(f"occupied_points: dtype must be torch.float64 (numpy's arithmetic) or torch.float32 (torch's), got {dtype}")
+            raise ValueError(f"{who}: dtype must be torch.float64 (numpy's arithmetic) or torch.float32 (torch's), got {dtype}")
         if return_depth and dtype != torch.float64:
-            raise ValueError("occupied_points: depth is float64 arithmetic (the vis_* scripts' shading): return_depth needs dtype=torch.float64")
+            raise ValueError(f"{who}: depth is float64 arithmetic (the vis_* scripts' shading): return_depth needs dtype=torch.float64")
         if capacity is not None and int(capacity) < 0:
-            raise ValueError(f"occupied_points: capacity must be >= 0, got {capacity}")
+            raise ValueError(f"{who}: capacity must be >= 0, got {capacity}")
         if B * T * G ** 3 >= 2 ** 31:
-            raise ValueError(f"occupied_points: {B * T} frames of {G}^3 voxels, one call indexes fewer than 2^31")
+            raise ValueError(f"{who}: {B * T} frames of {G}^3 voxels, one call indexes fewer than 2^31")
         pdev = next(self.parameters()).device
         if not vox.is_cuda or vox.device != pdev:
-            raise ValueError(f"occupied_points: vox must be on the network's device (a HIP device; the network is on {pdev}), got {vox.device}")
+            raise ValueError(f"{who}: vox must be on the network's device (a HIP device; the network is on {pdev}), got {vox.device}")
         if not vox.is_contiguous():
-            raise ValueError("occupied_points: vox must be contiguous")
+            raise ValueError(f"{who}: vox must be contiguous")
         eng = self._engine
         ctx = eng.ready()
         dev, F, W, f64 = ctx.device, B * T, (G ** 3 + 63) // 64, int(dtype == torch.float64)
@@ -880,17 +884,94 @@ class NeuralMarionette(nn.Module):
             out["depth"] = depth
         if return_bits:
             out["bits"] = bits.view(torch.uint8).view(F, W * 8)
+        return out, (B, T, G, bits, zi)
+
+    @torch.no_grad()
+    def surface_points(self, vox, threshold=0.5, radius2=6, orient="outward", base_colors=None, add_colors=None, shade=(0.8, 0.2),
+                       capacity=None, return_moments: bool = False):
+        """Device version of what the demo scripts do with every decoded frame after occupied_points' lines (vis_generation.py:157-171,
+        vis_interpolation.py:160-177): a surface normal per point, the [R | centre] rows of drawPlate's transform and the shaded colour
+        (nm_occupied_surface, csrc/nm_surface.hip).  The normals are NOT open3d's: on a voxel lattice its 30-nearest-neighbour set is
+        decided by tie-breaking inside a shell of equidistant points, so the neighbourhood here is the occupied voxels of the point's
+        frame within squared lattice distance ``radius2`` (1 .. 16), the moments are exact integers, and the normal is the unit
+        eigenvector of the smallest eigenvalue of n Q - S S^T in float64 - (0, 0, 1) for fewer than three neighbours.
+        vox, threshold, capacity: as occupied_points (float64 arithmetic).  orient: "outward" - away from the local mass (n . -S > 0;
+        S = 0: away from the frame's centroid; then (1, 1, 1); a dot product of exactly zero keeps the solver's sign) - or a point (3) /
+        one per clip (B,3): n is flipped where n . (point - coords) < 0 (open3d's orient_normals_towards_camera_location).
+        base_colors / add_colors: (3), (T,3), (B,T,3) or (B T,3), one colour per frame; colors = base * (depth * shade[0] + shade[1])
+        (+ add) in numpy's operation order - shade (0.8, 0.2) is vis_generation's, (0.9, 0.1) with an additive term
+        vis_interpolation's.  Colours and an orientation point given as lists, numpy arrays or CPU tensors are copied to the device
+        by the call, a pageable copy that makes the host wait: with ``capacity`` the call never synchronises only if they are float64
+        tensors on the network's device already (they are then used as they are).
+        Returns occupied_points' dict with depth - coords (N,3), offsets, counts, z_range, depth (N) - and normals (N,3), spread (N,3)
+        [the eigenvalues, ascending], plates (N,3,4), colors (N,3) [base_colors given], moments (N,10) int32 [return_moments: n, S (x, y,
+        z), Q (xx, xy, xz, yy, yz, zz) over the offsets q - p].  The camera, the cylinder mesh and the draw calls stay the caller's."""
+        who = "surface_points"
+        try:
+            r2 = int(radius2)
+        except (TypeError, ValueError):
+            r2 = 0
+        if r2 != radius2 or not 1 <= r2 <= 16:
+            raise ValueError(f"{who}: radius2 must be an integer from 1 to 16, got {radius2!r}")
+        try:
+            shade_a, shade_b = (float(v) for v in shade)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: shade must be two numbers (a, b) of depth * a + b, got {shade!r}") from None
+        if add_colors is not None and base_colors is None:
+            raise ValueError(f"{who}: add_colors without base_colors")
+        if isinstance(orient, str) and orient != "outward":
+            raise ValueError(f'{who}: orient must be "outward" or a point (3) / one point per clip (B,3), got {orient!r}')
+        out, (B, T, G, bits, zi) = self._occupied(who, vox, threshold, torch.float64, capacity, False, True, False)
+        dev, F = bits.device, B * T
+
+        def per_frame(x, name):
+            try:
+                t = torch.as_tensor(x, dtype=torch.float64)
+                t = t.reshape(B, T, 3) if tuple(t.shape) == (F, 3) else torch.broadcast_to(t, (B, T, 3))
+            except (RuntimeError, TypeError, ValueError):
+                raise ValueError(f"{who}: {name} must be (3), (T,3), (B,T,3) or (B T,3) numbers for {B} x {T} frames") from None
+            return t.to(dev).contiguous()
+
+        point = None
+        if not isinstance(orient, str):
+            try:
+                point = torch.broadcast_to(torch.as_tensor(orient, dtype=torch.float64), (B, 3)).to(dev).contiguous()
+            except (RuntimeError, TypeError, ValueError):
+                raise ValueError(f'{who}: orient must be "outward" or a point (3) / one point per clip (B,3) for {B} clips') from None
+        base = per_frame(base_colors, "base_colors") if base_colors is not None else None
+        add = per_frame(add_colors, "add_colors") if add_colors is not None else None
+        N = int(out["coords"].shape[0])
+        out["normals"] = torch.empty(N, 3, device=dev, dtype=torch.float64)
+        out["spread"] = torch.empty(N, 3, device=dev, dtype=torch.float64)
+        out["plates"] = torch.empty(N, 3, 4, device=dev, dtype=torch.float64)
+        if base is not None:
+            out["colors"] = torch.empty(N, 3, device=dev, dtype=torch.float64)
+        if return_moments:
+            out["moments"] = torch.empty(N, 10, device=dev, dtype=torch.int32)
+        if N:
+            self._engine.call("nm_occupied_surface", bits.data_ptr(), out["offsets"].data_ptr(), _lib.ptr(zi), B, T, G, r2, 0 if point is None else 1,
+                              _lib.ptr(point), _lib.ptr(base), _lib.ptr(add), shade_a, shade_b, N, _lib.ptr(out.get("moments")),
+                              _lib.ptr(out["normals"]), _lib.ptr(out["spread"]), _lib.ptr(out["plates"]), _lib.ptr(out.get("colors")))
         return out
+
+    def _points(self, who, vox, return_points):
+        """the drivers' ``return_points``: True - occupied_points(vox, 0.5, return_depth=True); "surface" - surface_points(vox, 0.5)"""
+        if not isinstance(return_points, str):
+            return self.occupied_points(vox, 0.5, return_depth=True)
+        if return_points == "surface":
+            return self.surface_points(vox, 0.5)
+        raise ValueError(f'{who}: return_points must be False, True or "surface", got {return_points!r}')
 
     # -- sampling drivers (SURVEY 8(f3)): the rollout loops of the reference's demo scripts as methods ------------
     @torch.no_grad()
-    def sample_generation(self, cond_voxel, Tgen=25, sample_num=3, eps_post=None, eps_prior=None, return_points: bool = False):
+    def sample_generation(self, cond_voxel, Tgen=25, sample_num=3, eps_post=None, eps_prior=None, return_points=False):
         """vis_generation.py:81-136: condition on ``cond_voxel`` (Tcond,1,G,G,G) with best-of-``sample_num``
         posterior steps, then roll ``sample_num`` independent prior trajectories for ``Tgen`` steps and decode each.
         eps_post (Tcond,sample_num,Z) / eps_prior (Tgen,sample_num,Z) inject the noise.
         Returns keypoints_cond (1,Tcond,K,4) [the detected keypoints, as the script records], keypoints_gen
         (1,Tgen,sample_num,K,4) and voxels (sample_num,Tcond+Tgen,1,G,G,G) binarised at 0.5.  return_points: also ``points``, the
-        script's next lines (:137-170) on the device - occupied_points(voxels_raw, 0.5, return_depth=True), a clip per sample."""
+        script's next lines (:137-170) on the device - occupied_points(voxels_raw, 0.5, return_depth=True), a clip per sample;
+        return_points="surface": surface_points(voxels_raw, 0.5) instead, with the normals and plate frames of :157-171."""
         _need_graph(self._engine.opts, "NeuralMarionette.sample_generation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
@@ -917,19 +998,20 @@ class NeuralMarionette(nn.Module):
         vox = self.kypt_detector.decode_from_dyna(full, ff, fr)["gen"]
         out = dict(keypoints_cond=cond_k, keypoints_gen=gen_k, voxels=(vox >= 0.5).float(), voxels_raw=vox)
         if return_points:
-            out["points"] = self.occupied_points(vox, 0.5, return_depth=True)
+            out["points"] = self._points("sample_generation", vox, return_points)
         return out
 
     @torch.no_grad()
     def sample_interpolation(self, target_voxel, sample_rate=10, sample_num=10000, eps_a=None, eps_b=None, force_picks=None,
-                             return_points: bool = False):
+                             return_points=False):
         """vis_interpolation.py:80-143: key frames every ``sample_rate`` steps (and the last one) are matched with a
         posterior sample, the frames in between come from the prior trajectory (out of ``sample_num``) that lands
         nearest the next key frame.  eps_a (T,sample_num,Z): the step's first draw (posterior at key frames, prior
         otherwise); eps_b (T,sample_num,Z): the second (prior, 'for choosing') draw at key frames.
         ``force_picks`` (list of (i1, i2) per key frame) replaces the two nearest-row selections (teacher forcing in tests).
         Returns keypoints (1,T,K,4), voxels (T,1,G,G,G) binarised at 0.5, and the selected row per key frame.  return_points: also
-        ``points``, the script's next lines (:141-177) on the device - occupied_points(voxels_raw, 0.5, return_depth=True)."""
+        ``points``, the script's next lines (:141-177) on the device - occupied_points(voxels_raw, 0.5, return_depth=True);
+        return_points="surface": surface_points(voxels_raw, 0.5) instead, with the normals and plate frames of :160-177."""
         _need_graph(self._engine.opts, "NeuralMarionette.sample_interpolation")
         d = self.dyna_module
         S, K, Z = int(sample_num), d.nkeypoints, d.nlatent_kypt
@@ -968,7 +1050,7 @@ class NeuralMarionette(nn.Module):
         vox = self.kypt_detector.decode_from_dyna(sel, det["first_feature"], target_voxel[None, 0].to(dev))["gen"][0]
         out = dict(keypoints=sel, voxels=(vox >= 0.5).float(), voxels_raw=vox, picks=picks)
         if return_points:
-            out["points"] = self.occupied_points(vox.contiguous(), 0.5, return_depth=True)
+            out["points"] = self._points("sample_interpolation", vox.contiguous(), return_points)
         return out
 
     @torch.no_grad()
@@ -1084,9 +1166,10 @@ class NeuralMarionette(nn.Module):
                    gae_recon_loss=torch.zeros((), dtype=torch.int64, device=dev), topo_recon_loss=torch.zeros((), dtype=torch.int64, device=dev), best_idx=best)
         return log
 
-    def generate(self, vox_seq, module_actives=None, eps_post=None, eps_prior=None, return_points: bool = False):
+    def generate(self, vox_seq, module_actives=None, eps_post=None, eps_prior=None, return_points=False):
         """neural_marionette.py:58-103 ('dl' transition).  return_points: also ``points`` = occupied_points(gen, 0.5, return_depth=True),
-        what the reference's plotting does with ``gen`` on the host."""
+        what the reference's plotting does with ``gen`` on the host; return_points="surface": surface_points(gen, 0.5) instead, with the
+        normals and plate frames the demo scripts compute per frame."""
         if module_actives["learner"]:
             _need_graph(self._engine.opts, "NeuralMarionette.generate")
         B, T = vox_seq.shape[:2]
@@ -1102,5 +1185,5 @@ class NeuralMarionette(nn.Module):
                        keypoints=torch.cat([keypoints[:, :self.Tcond], dyn["keypoints_gen"]], dim=1),
                        A_hats=None)
             if return_points:
-                log["points"] = self.occupied_points(log["gen"], 0.5, return_depth=True)
+                log["points"] = self._points("generate", log["gen"], return_points)
         return log
