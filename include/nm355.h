@@ -278,6 +278,54 @@ int nm_occupied_surface(nm_ctx* ctx, const uint64_t* bits, const int64_t* offset
                         double shade_a, double shade_b, int64_t capacity, int32_t* moments, double* normals, double* spread,
                         double* plates, double* colors);
 
+/* ---- render path: those plates drawn as flat discs through a pinhole camera (vis_generation.py:171-190, vis_interpolation.py:177-185:
+ * a cylinder mesh per plate into open3d's off-screen visualiser, capture_screen_float_buffer, (img * 255).astype(uint8)) ----
+ * This is NOT open3d's image: its lighting, MSAA and GL rasterisation rules are neither available nor reproducible.  The result is
+ * defined by this text alone, in float64, unfused, in exactly this operation order (tests/render_ref.py restates it in numpy).
+ *   scene    N plates in F frames, frame f owns the rows offsets[f] .. offsets[f+1] of plates (N,3,4) - nm_occupied_surface's arrays;
+ *     only rows below `rows` are read, the others are not drawn.  Plate i is the disc with centre c = plates[i,:,3], axis
+ *     a = plates[i,:,2] (the third column of drawPlate's R, the image of (0,0,1)) and radius `radius` (the scripts' cylinder: 0.03): the
+ *     cylinder's cap at the centre.  Its 0.01 side wall is not drawn; both faces are visible.
+ *   camera   open3d's PinholeCameraParameters as nm_camera, a HOST struct: extrinsic = the world -> camera matrix E, row-major (E[r][c] =
+ *     extrinsic[4 r + c]; open3d's JSON lists it column-major), fx, fy, cx, cy, width, height and a near plane (open3d has none; 1e-3 is
+ *     the shells' default).  Camera axes: x right, y down, z forward.  Pixel (px, py), row 0 at the top as capture_screen_float_buffer
+ *     gives it, looks along d = ((px - cx) / fx, (py - cy) / fy, 1) from the origin - open3d's convention, the principal point
+ *     cx = width / 2 - 0.5 is the centre of the middle pixel.
+ *   per plate, once   c'_r = ((E[r,0] c_x + E[r,1] c_y) + E[r,2] c_z) + E[r,3];  a'_r = (E[r,0] a_x + E[r,1] a_y) + E[r,2] a_z;
+ *     q = (a'_x c'_x + a'_y c'_y) + a'_z c'_z.  A plate with c'_z - radius < near, or with a non-finite component of c' or a', is not
+ *     drawn at all.
+ *   per pixel and plate   den = (a'_x dx + a'_y dy) + a'_z, den == 0 is a miss;  s = q / den, a miss unless s >= near;
+ *     h = (s dx - c'_x, s dy - c'_y, s - c'_z), m = (h_x^2 + h_y^2) + h_z^2;  a hit iff m <= radius * radius.
+ *   winner   the hit with the smallest s; among equal s the lowest row index.
+ *   outputs, any of which may be NULL:  index (F,H,W) int32, the winner's row or -1 for background;  depth (F,H,W) float64, the winner's
+ *     s or +inf;  image (F,H,W,3) uint8:  v = colors[i,ch] * (light_a + light_b * |den| / sqrt((dx^2 + dy^2) + 1)) with the winner's
+ *     den, NaN -> 0, clamped to [0, 1], stored as uint8(v * 255.0), truncated; background pixels take `background` (3 doubles on the
+ *     HOST, NULL = white) through the same NaN / clamp / truncation.  light (1, 0) gives colors as they are - the scripts' depth shading
+ *     is in nm_occupied_surface's colors already; light_b weighs the cosine between the plate's axis and the ray (for a unit axis).
+ * nm_render_bin - per plate c', a', q and the frame into xf (rows,8) float64 and into rect (rows,4) int32 a pixel rectangle x0, x1, y0,
+ *   y1 that contains every pixel the plate can hit (x0 > x1: not drawn); then the number of plates per (frame, 16 x 16-pixel tile),
+ *   scanned: tile_offsets (F TY TX + 1) int64, TX = ceil(width / 16), TY = ceil(height / 16), tile (f, ty, tx) at (f TY + ty) TX + tx.
+ *   Its last entry is the number of list entries nm_render_draw needs - always the true number.
+ * nm_render_draw - fills list (capacity) int32 with the tiles' rows from xf / rect / tile_offsets as nm_render_bin wrote them for the same
+ *   arguments, then draws: a workgroup per tile, a thread per pixel.  Only list entries below `capacity` are written or read: with a
+ *   capacity below tile_offsets' last entry nothing faults and nothing is written out of bounds, but the image is INCOMPLETE (which
+ *   plates the cut tiles lose is not defined); compare the two numbers.  colors (rows,3) float64 may be NULL without image.
+ * Integer atomics order the tile lists; the per-pixel minimum over (s, row) does not depend on that order, and no atomic touches an
+ * output: results are bit-identical from run to run.  Both are stream-ordered, synchronise nothing (but for the workspace's first
+ * growth) and need no weights.  NM_ERR_ARG: null ctx / offsets / camera / tile_offsets, null plates / xf / rect with rows > 0, null list
+ * with capacity > 0, image with rows > 0 but no colors, F, width, height < 1, rows < 0, radius not a finite number > 0, capacity < 0, a
+ * non-finite camera number, fx or fy of 0, near <= 0; NM_ERR_UNSUPPORTED: F height width >= 2^31, rows >= 2^31. */
+typedef struct {
+    double extrinsic[16];
+    double fx, fy, cx, cy, near;
+    int32_t width, height;
+} nm_camera;
+int nm_render_bin(nm_ctx* ctx, const double* plates, const int64_t* offsets, int32_t F, int64_t rows, const nm_camera* camera, double radius,
+                  double* xf, int32_t* rect, int64_t* tile_offsets);
+int nm_render_draw(nm_ctx* ctx, const double* xf, const int32_t* rect, const int64_t* offsets, const int64_t* tile_offsets,
+                   const double* colors, int32_t F, int64_t rows, const nm_camera* camera, double radius, double light_a, double light_b,
+                   const double* background, int64_t capacity, int32_t* list, int32_t* index, double* depth, uint8_t* image);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

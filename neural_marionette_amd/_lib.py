@@ -32,6 +32,11 @@ class NmNamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
 
+class NmCamera(C.Structure):
+    _fields_ = [("extrinsic", C.c_double * 16), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("near", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class NmClipDesc(C.Structure):
     _fields_ = [("points", C.c_void_p), ("joints", C.c_void_p), ("frames", C.c_int32), ("start", C.c_int32),
                 ("sample_rate", C.c_int32), ("pad", C.c_int32), ("scale", C.c_double), ("x_trans", C.c_double), ("z_trans", C.c_double)]
@@ -68,6 +73,9 @@ SIGNATURES = {
     "nm_occupied_count": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
     "nm_occupied_write": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _P, _P, _P]),
     "nm_occupied_surface": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P]),
+    "nm_render_bin": (C.c_int, [C.c_void_p, _P, _P, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, _P, _P, _P]),
+    "nm_render_draw": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, C.c_double, C.c_double,
+                                 C.POINTER(C.c_double), C.c_int64, _P, _P, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

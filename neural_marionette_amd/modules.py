@@ -905,7 +905,7 @@ class NeuralMarionette(nn.Module):
         tensors on the network's device already (they are then used as they are).
         Returns occupied_points' dict with depth - coords (N,3), offsets, counts, z_range, depth (N) - and normals (N,3), spread (N,3)
         [the eigenvalues, ascending], plates (N,3,4), colors (N,3) [base_colors given], moments (N,10) int32 [return_moments: n, S (x, y,
-        z), Q (xx, xy, xz, yy, yz, zz) over the offsets q - p].  The camera, the cylinder mesh and the draw calls stay the caller's."""
+        z), Q (xx, xy, xz, yy, yz, zz) over the offsets q - p].  render_plates draws the result through a pinhole camera."""
         who = "surface_points"
         try:
             r2 = int(radius2)
@@ -952,6 +952,99 @@ class NeuralMarionette(nn.Module):
             self._engine.call("nm_occupied_surface", bits.data_ptr(), out["offsets"].data_ptr(), _lib.ptr(zi), B, T, G, r2, 0 if point is None else 1,
                               _lib.ptr(point), _lib.ptr(base), _lib.ptr(add), shade_a, shade_b, N, _lib.ptr(out.get("moments")),
                               _lib.ptr(out["normals"]), _lib.ptr(out["spread"]), _lib.ptr(out["plates"]), _lib.ptr(out.get("colors")))
+        return out
+
+    @torch.no_grad()
+    def render_plates(self, points, camera, radius=0.03, light=(1.0, 0.0), background=(1.0, 1.0, 1.0), bin_capacity=None,
+                      return_index: bool = False, return_depth: bool = False):
+        """Device version of the demo scripts' last step (vis_generation.py:171-190, vis_interpolation.py:177-185: a cylinder mesh per
+        plate into open3d's off-screen visualiser and capture_screen_float_buffer): every plate of ``points`` - surface_points' dict, or
+        a driver's ``points`` under return_points="surface" chained with colours - drawn as a flat disc of ``radius`` through
+        ``camera`` (render.PinholeCamera), the nearest disc winning each pixel (nm_render_bin + nm_render_draw, csrc/nm_render.hip).
+        **This is not open3d's image**: its lighting, MSAA and GL rasterisation rules are not reproducible, so the result is defined by
+        the contract of include/nm355.h alone (tests/render_ref.py restates it): plate i is the disc about plates[i,:,3] with axis
+        plates[i,:,2] - the cylinder's cap, both faces visible, its 0.01 side wall not drawn; pixel (px, py), row 0 at the top, looks
+        along ((px - cx) / fx, (py - cy) / fy, 1); plates that reach in front of ``camera.near`` are not drawn; of equal depths the lower
+        row wins.  The pixel is colors[i] * (light[0] + light[1] * |cos(axis, ray)|) clamped to [0, 1] (NaN: 0) and truncated to uint8 as
+        the scripts' (img * 255).astype(uint8); light (1, 0) leaves the colours - which carry the scripts' depth shading already - flat.
+        points needs ``plates`` (N,3,4), ``offsets`` (F+1) and ``colors`` (N,3) [surface_points(base_colors=...)]; ``counts`` (B,T) gives
+        the result its leading shape, (1,F) without it.
+        Returns a dict: image (B,T,H,W,3) uint8; bin_total, a 0-d int64 device tensor - the number of (tile, plate) list entries the
+        draw needs; index (B,T,H,W) int32 [return_index]: the winner's row, -1 for background; depth (B,T,H,W) float64 [return_depth]:
+        its distance along the camera's z, +inf for background.
+        bin_capacity=None reads bin_total - the call's one synchronisation - and sizes the lists exactly.  With a bin_capacity the
+        call never synchronises; if bin_total turns out larger, nothing faults but the image is INCOMPLETE (the tiles past the capacity
+        lose plates): compare ``bin_total`` with it afterwards.  No atomics touch an output: results are bit-identical from run to run."""
+        from .render import PinholeCamera
+        who = "render_plates"
+        if not isinstance(camera, PinholeCamera):
+            raise ValueError(f"{who}: camera must be a neural_marionette_amd.PinholeCamera, got {type(camera).__name__}")
+        if not isinstance(points, dict) or "plates" not in points or "offsets" not in points:
+            raise ValueError(f"{who}: points must be surface_points' dict with 'plates' and 'offsets'")
+        if "colors" not in points:
+            raise ValueError(f"{who}: points has no 'colors': call surface_points with base_colors (one colour per frame)")
+        try:
+            radius = float(radius)
+            light_a, light_b = (float(v) for v in light)
+            bg = [float(v) for v in background]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: radius must be a number, light two numbers (a, b) and background three") from None
+        if len(bg) != 3:
+            raise ValueError(f"{who}: background must be three numbers, got {background!r}")
+        if not (radius > 0.0 and radius < float("inf")):
+            raise ValueError(f"{who}: radius must be a finite number > 0, got {radius}")
+        if bin_capacity is not None and int(bin_capacity) < 0:
+            raise ValueError(f"{who}: bin_capacity must be >= 0, got {bin_capacity}")
+        plates, offsets, colors = points["plates"], points["offsets"], points["colors"]
+        eng = self._engine
+        ctx = eng.ready()
+        dev = ctx.device
+        N = int(plates.shape[0])
+        if plates.dtype != torch.float64 or tuple(plates.shape) != (N, 3, 4) or colors.dtype != torch.float64 or tuple(colors.shape) != (N, 3):
+            raise ValueError(f"{who}: plates must be (N,3,4) and colors (N,3) float64, got {tuple(plates.shape)} {plates.dtype} and {tuple(colors.shape)} {colors.dtype}")
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2:
+            raise ValueError(f"{who}: offsets must be (F+1) int64, got {tuple(offsets.shape)} {offsets.dtype}")
+        for name, t in (("plates", plates), ("offsets", offsets), ("colors", colors)):
+            if not t.is_cuda or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous on the network's device ({dev}), got {t.device}")
+        F = int(offsets.numel()) - 1
+        lead = tuple(points["counts"].shape) if "counts" in points and points["counts"].numel() == F else (1, F)
+        H, W = camera.height, camera.width
+        if F * H * W >= 2 ** 31:
+            raise ValueError(f"{who}: {F} frames of {W} x {H} pixels, one call indexes fewer than 2^31")
+        cam = camera.c_struct()
+        TX, TY = (W + 15) // 16, (H + 15) // 16
+        xf = torch.empty(N, 8, device=dev, dtype=torch.float64)
+        rect = torch.empty(N, 4, device=dev, dtype=torch.int32)
+        tile_offsets = torch.empty(F * TX * TY + 1, device=dev, dtype=torch.int64)
+        eng.call("nm_render_bin", plates.data_ptr(), offsets.data_ptr(), F, N, C.byref(cam), radius, xf.data_ptr(), rect.data_ptr(), tile_offsets.data_ptr())
+        cap = int(tile_offsets[-1].item()) if bin_capacity is None else int(bin_capacity)
+        lst = torch.empty(cap, device=dev, dtype=torch.int32)
+        out = dict(image=torch.empty(lead + (H, W, 3), device=dev, dtype=torch.uint8), bin_total=tile_offsets[-1])
+        if return_index:
+            out["index"] = torch.empty(lead + (H, W), device=dev, dtype=torch.int32)
+        if return_depth:
+            out["depth"] = torch.empty(lead + (H, W), device=dev, dtype=torch.float64)
+        null = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        eng.call("nm_render_draw", null(xf), null(rect), offsets.data_ptr(), tile_offsets.data_ptr(), null(colors), F, N, C.byref(cam), radius, light_a,
+                 light_b, (C.c_double * 3)(*bg), cap, null(lst), null(out.get("index")), null(out.get("depth")), out["image"].data_ptr())
+        return out
+
+    @torch.no_grad()
+    def render_frames(self, vox, camera, threshold=0.5, radius2=6, base_colors=(0.6, 1.0, 0.6), add_colors=None, shade=(0.8, 0.2), radius=0.03,
+                      orient="outward", light=(1.0, 0.0), background=(1.0, 1.0, 1.0), bin_capacity=None, return_index: bool = False,
+                      return_depth: bool = False, return_points: bool = False):
+        """The demo scripts' whole inner loop from a decoded batch (vis_generation.py:137-190, vis_interpolation.py:141-185):
+        surface_points(vox, threshold, radius2, orient, base_colors, add_colors, shade) followed by render_plates(points, camera, radius,
+        light, background, bin_capacity, ...).  base_colors' default is vis_generation's green.  Returns render_plates' dict, with
+        surface_points' under ``points`` [return_points].  **Not open3d's image**: see render_plates."""
+        if base_colors is None:
+            raise ValueError("render_frames: base_colors must give one colour per frame (or one for all)")
+        pts = self.surface_points(vox, threshold, radius2=radius2, orient=orient, base_colors=base_colors, add_colors=add_colors, shade=shade)
+        out = self.render_plates(pts, camera, radius=radius, light=light, background=background, bin_capacity=bin_capacity,
+                                 return_index=return_index, return_depth=return_depth)
+        if return_points:
+            out["points"] = pts
         return out
 
     def _points(self, who, vox, return_points):
