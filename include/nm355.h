@@ -326,6 +326,94 @@ int nm_render_draw(nm_ctx* ctx, const double* xf, const int32_t* rect, const int
                    const double* colors, int32_t F, int64_t rows, const nm_camera* camera, double radius, double light_a, double light_b,
                    const double* background, int64_t capacity, int32_t* list, int32_t* index, double* depth, uint8_t* image);
 
+/* ---- render path for the retargeting demo: the posed triangle mesh, the skeleton, and the skeleton over the mesh (vis_retarget.py:400-557:
+ * a TriangleMesh per frame, drawSphere per visible joint, drawCone1 + drawCone2 per bone, img[cone_img.sum(-1) != 3] = cone_img[...]) ----
+ * As for the plates this is NOT open3d's image; the result is defined by this text alone, in float64, unfused, in exactly this operation
+ * order (tests/mesh_ref.py restates it in numpy).  The camera, the pixel rays d = (dx, dy, 1) = ((px - cx) / fx, (py - cy) / fy, 1), the depth
+ * s along the camera's z, the conversion v -> uint8 (NaN -> 0, clamped to [0, 1], uint8(v * 255.0) truncated), `background` (3 doubles on
+ * the HOST, NULL = white) and the point formula p'_r = ((E[r,0] p_x + E[r,1] p_y) + E[r,2] p_z) + E[r,3] are the plate contract's above: a
+ * mesh depth, a skeleton depth and a plate depth at the same pixel are comparable.  Below A = (dx^2 + dy^2) + 1, a dot product of
+ * 3-vectors is u . v = (u_x v_x + u_y v_y) + u_z v_z, one with the ray is u . d = (u_x dx + u_y dy) + u_z, and the headlight of a normal
+ * n with den = n . d is  shade = light_a + light_b * |den| / (sqrt(n . n) * sqrt(A)) - light (1, 0) gives the colours as they are.
+ *
+ * MESH.  vertices (F,V,3) float64 (sample_retarget's points), triangles (M,3) int32 shared by all frames, colours either vertex_colors
+ * (V,3) float64 on the device, shared by all frames, or with vertex_colors NULL the uniform `color` (3 doubles on the HOST, NULL = 0.7
+ * grey).  All arithmetic is in camera space.
+ *   per triangle and frame, once   p'_0, p'_1, p'_2;  e1 = p'_1 - p'_0, e2 = p'_2 - p'_0;  n = e1 x e2 = (e1_y e2_z - e1_z e2_y,
+ *     e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x);  q = n . p'_0;  X_k = p'_kx / p'_kz, Y_k = p'_ky / p'_kz, iz_k = 1.0 / p'_kz.
+ *     A triangle is not drawn at all if one of its indices lies outside [0, V) (judged on the device, nothing is read through it), if a
+ *     component of a p'_k, of n or q is not finite, if any vertex has p'_kz < near - the WHOLE triangle is culled, there is NO clipping
+ *     against the near plane - or if n is the zero vector.
+ *   per pixel: coverage   a_k = X_k - dx, b_k = Y_k - dy;  w0 = a_1 * b_2 - b_1 * a_2, w1 = a_2 * b_0 - b_2 * a_0, w2 = a_0 * b_1 - b_0 * a_1.
+ *     (Swapping an edge's two vertices negates its w exactly in IEEE arithmetic, so two triangles that share an edge never leave a crack
+ *     along it.)  Covered iff w0, w1, w2 are all >= 0 or all <= 0 - both faces are visible - and (w0 + w1) + w2 != 0, and the pixel lies
+ *     in the triangle's rectangle: floor(min_k u_k - 1.0) <= px <= ceil(max_k u_k + 1.0) with u_k = cx + fx * X_k, and the same for py with
+ *     v_k = cy + fy * Y_k.  (For a triangle with area the rectangle excludes nothing the edge functions cover; for one seen edge-on,
+ *     whose edge functions are rounding noise all along its line, it bounds what that noise can reach.)
+ *   per pixel: depth   den = n . d, den == 0 is a miss;  s = q / den, a miss unless s >= near.
+ *   winner   the smallest s; among equal s the lowest triangle row (a pixel on a shared edge belongs to both triangles).
+ *   colour   l_k = w_k * iz_k, L = (l_0 + l_1) + l_2, colour_ch = ((l_0 c_0,ch + l_1 c_1,ch) + l_2 c_2,ch) / L from the winner's three vertex
+ *     colours (perspective-correct), or the uniform colour;  v_ch = colour_ch * shade with the flat face normal n and the winner's den.
+ *   outputs, any of which may be NULL:  index (F,H,W) int32, the winner's triangle row or -1;  depth (F,H,W) float64, its s or +inf;
+ *     image (F,H,W,3) uint8.
+ * nm_mesh_bin - per (frame, triangle), record f M + m: rec (F M,16) float64 = X_0 Y_0 X_1 Y_1 X_2 Y_2, n, q, iz_0 iz_1 iz_2, three zeros
+ *   (all zeros for a triangle that is not drawn), and into rect (F M,4) int32 a pixel rectangle x0, x1, y0, y1 that contains every pixel
+ *   the triangle can cover (x0 > x1: not drawn); then the number of records per (frame, 16 x 16-pixel tile), scanned: tile_offsets
+ *   (F TY TX + 1) int64 laid out as nm_render_bin's, its last entry the number of list entries nm_mesh_draw needs - always the true number.
+ * nm_mesh_draw - fills list (capacity) int32 with the tiles' records from rect / tile_offsets as nm_mesh_bin wrote them for the same
+ *   arguments, then draws: a workgroup per tile, a thread per pixel, the tile's records through LDS 128 at a time, the vertex colours
+ *   fetched for the winner only.  `capacity` works as nm_render_draw's: below tile_offsets' last entry nothing faults and nothing is
+ *   written out of bounds, but the image is INCOMPLETE.  triangles may be NULL without vertex_colors or image.  With index, depth and
+ *   image all NULL the call does nothing: the list is not filled either.
+ *
+ * SKELETON.  keypoints (F,K,4) float32 on the device (x, y, z, intensity; converted to float64 first), parents (K) int32 on the device,
+ * K <= 32.  Joint k is VISIBLE iff clip(intensity_k, 0, 1) >= threshold (vis_retarget.py:516-522; the script's VIS_THRESHOLD is 0.2; a NaN
+ * is not) and its p'_k is finite.
+ *   sphere k (primitive k)   for a visible joint with p'_kz - radius >= near (the plates' rule), centre c = p'_k:  C = c . c - radius * radius.
+ *     per pixel  B = c . d, D = B * B - A * C;  a hit iff D >= 0 and B > 0;  s = C / (B + sqrt(D)) (the near root, free of cancellation);
+ *     normal h = (s dx - c_x, s dy - c_y, s - c_z).
+ *   bone of joint k (primitive K + k)   iff k and p = parents[k] are visible, 0 <= p < K, p != k, b = p'_k - p'_p has b . b > 0 (finite), and
+ *     both ends have p'_z - bone_radius >= near (no clipping).  It is the script's double cone: two finite nappes that share the base
+ *     circle of radius bone_radius about g = p'_p + 0.2 * b (componentwise), perpendicular to the bone, with their apexes at the parent
+ *     and at the child.  The shared base disc is interior and is not drawn.  drawCone2's 0.195 margin and the + 1e-6 of the heights are
+ *     NOT reproduced: the nappes meet exactly.
+ *   nappe with apex a (first p'_p, then p'_k)   v = g - a, vv = v . v, kappa = (vv + bone_radius * bone_radius) / (vv * vv), av = a . v,
+ *     aa = a . a (a bone with vv == 0 or a non-finite kappa on either side is not drawn).  Its surface is kappa ((X - a) . v)^2 = |X - a|^2
+ *     with 0 <= (X - a) . v <= vv.  per pixel  dv = v . d, da = a . d, kd = kappa * dv;  c2 = kd * dv - A, c1 = kd * av - da,
+ *     c0 = (kappa * av) * av - aa: the ray meets the full cone where c2 s^2 - 2 c1 s + c0 = 0.  c2 == 0 is a miss;  D = c1 * c1 - c2 * c0, a
+ *     miss unless D >= 0.  The root (c1 + g sqrt(D)) / c2, g = +-1, has the axis parameter (P + g dv sqrt(D)) / c2 with P = c1 * dv - av * c2;
+ *     it is ON the nappe iff that lies in [0, vv], which is decided without a square root: for c2 > 0 iff ge0(P, g dv) and
+ *     ge0(-P2, -g dv), for c2 < 0 iff ge0(-P, -g dv) and ge0(P2, g dv), where P2 = P - vv * c2 and ge0(p, q), "p + q sqrt(D) >= 0", is: for
+ *     q >= 0, p >= 0 or (q * q) * D >= p * p; for q < 0, p >= 0 and p * p >= (q * q) * D.  The hit is the nearer root (g = -1 for c2 > 0, +1 for
+ *     c2 < 0) if it is on the nappe, else the other root if that one is, else a miss.  (A ray steeper than the cone meets the nappe at
+ *     its far root only, the near one lying on the mirror nappe behind the apex.)  Only now  r = sqrt(D), qq = c1 + r for c1 >= 0 and
+ *     c1 - r otherwise, qq == 0 a miss;  the root with g = +1 is qq / c2 for c1 >= 0 and c0 / qq otherwise, the root with g = -1 the other
+ *     of the two.  Normal h = (s d - a) - (kappa * (s * dv - av)) v.  A bone's s is the smaller of its nappes' (the parent's on a tie).
+ *     A skeleton hit is not compared with near again: what is drawn lies wholly beyond it.
+ *   winner   the smallest s, then the lowest primitive number; index stores that number, depth s.
+ *   image   v_ch = colour_ch * shade with the normal h at the hit; a sphere takes joint_colors[k] ((K,3) float64 on the device) or with
+ *     joint_colors NULL `joint_color`, a bone `bone_color` (3 doubles each on the HOST; NULL = the script's (0.7, 0.1, 0) and (0, 0.6, 0.1)).
+ *     With overlay != 0 image is in-out: pixels the skeleton does not cover are left as they are - the script's paste (:463, :550) without
+ *     its accident of treating white skeleton pixels as background; otherwise they take `background`.
+ * nm_skeleton_draw - one launch, a workgroup per tile, a thread per pixel; the frame's joints and bones are transformed into LDS by the
+ *   workgroup, at most 32 spheres and 31 bones, no binning.
+ *
+ * Integer atomics order the mesh's tile lists only; no atomic touches an output: results are bit-identical from run to run.  All three are
+ * stream-ordered, synchronise nothing (but for the workspace's first growth) and need no weights.  Arguments are judged before any launch.
+ * NM_ERR_ARG: null ctx / camera, null tile_offsets, null vertices / triangles / rec / rect with M > 0, null list with capacity > 0,
+ * vertex_colors with an image but no triangles, null keypoints / parents, F, V, K, width, height < 1, M < 0, K > 32, radius or bone_radius
+ * not a finite number > 0, capacity < 0, a non-finite camera number, fx or fy of 0, near <= 0; NM_ERR_UNSUPPORTED: F height width >= 2^31,
+ * F M >= 2^31. */
+int nm_mesh_bin(nm_ctx* ctx, const double* vertices, const int32_t* triangles, int32_t F, int32_t V, int64_t M, const nm_camera* camera,
+                double* rec, int32_t* rect, int64_t* tile_offsets);
+int nm_mesh_draw(nm_ctx* ctx, const double* rec, const int32_t* rect, const int64_t* tile_offsets, const int32_t* triangles,
+                 const double* vertex_colors, const double* color, int32_t F, int32_t V, int64_t M, const nm_camera* camera, double light_a,
+                 double light_b, const double* background, int64_t capacity, int32_t* list, int32_t* index, double* depth, uint8_t* image);
+int nm_skeleton_draw(nm_ctx* ctx, const float* keypoints, const int32_t* parents, int32_t F, int32_t K, const nm_camera* camera,
+                     double threshold, double radius, double bone_radius, const double* joint_colors, const double* joint_color,
+                     const double* bone_color, double light_a, double light_b, const double* background, int32_t overlay, int32_t* index,
+                     double* depth, uint8_t* image);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

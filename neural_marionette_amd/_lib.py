@@ -76,6 +76,11 @@ SIGNATURES = {
     "nm_render_bin": (C.c_int, [C.c_void_p, _P, _P, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, _P, _P, _P]),
     "nm_render_draw": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, C.c_double, C.c_double,
                                  C.POINTER(C.c_double), C.c_int64, _P, _P, _P, _P]),
+    "nm_mesh_bin": (C.c_int, [C.c_void_p, _P, _P, _I, _I, C.c_int64, C.POINTER(NmCamera), _P, _P, _P]),
+    "nm_mesh_draw": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, C.POINTER(C.c_double), _I, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, C.c_double,
+                               C.POINTER(C.c_double), C.c_int64, _P, _P, _P, _P]),
+    "nm_skeleton_draw": (C.c_int, [C.c_void_p, _P, _P, _I, _I, C.POINTER(NmCamera), C.c_double, C.c_double, C.c_double, _P, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double), _I, _P, _P, _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

@@ -41,6 +41,7 @@ Priority = namedtuple("Priority", ["values", "indices"])   # what torch.topk ret
 CONV_MODES = {"fp32": 0, "0": 0, "exact": 0, "split16": 1, "1": 1, "f16": 3, "3": 3, "bf16": 4, "4": 4, "auto": 1}
 NM_ERR_RANGE = -5
 CONV_MODE_NAMES = ("split16", "fp32", "f16", "bf16", "auto")
+MESH_RECORD_BYTES = 512 << 20   # render_mesh draws its frames in groups whose triangle records (144 bytes per frame and triangle) stay under this
 
 
 class Engine:
@@ -1046,6 +1047,208 @@ class NeuralMarionette(nn.Module):
         if return_points:
             out["points"] = pts
         return out
+
+    @staticmethod
+    def _render_numbers(who, camera, light, background, **colors):
+        """the arguments render_mesh and render_skeleton share, as floats: (light_a, light_b), background, and each named colour"""
+        from .render import PinholeCamera
+        if not isinstance(camera, PinholeCamera):
+            raise ValueError(f"{who}: camera must be a neural_marionette_amd.PinholeCamera, got {type(camera).__name__}")
+        try:
+            la, lb = (float(v) for v in light)
+            out = {name: [float(v) for v in value] for name, value in dict(colors, background=background).items()}
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: light must be two numbers (a, b), background and {', '.join(colors) or 'colours'} three each") from None
+        for name, value in out.items():
+            if len(value) != 3:
+                raise ValueError(f"{who}: {name} must be three numbers, got {len(value)}")
+        return (la, lb), out
+
+    @torch.no_grad()
+    def render_mesh(self, vertices, triangles, camera, vertex_colors=None, color=(0.7, 0.7, 0.7), light=(0.3, 0.7), background=(1.0, 1.0, 1.0),
+                    bin_capacity=None, return_index: bool = False, return_depth: bool = False, record_bytes: Optional[int] = None):
+        """Device version of vis_retarget.py's mesh images (:400-430, :497-512: a TriangleMesh per frame into open3d's off-screen
+        visualiser): the triangles ``triangles`` (M,3) int32 over the posed ``vertices`` (F,V,3) float64 - sample_retarget's ``points``
+        - drawn through ``camera`` (render.PinholeCamera), the nearest triangle winning each pixel (nm_mesh_bin + nm_mesh_draw,
+        csrc/nm_mesh.hip).  **This is not open3d's image**: the result is defined by the contract of include/nm355.h alone
+        (tests/mesh_ref.py restates it): a pixel is covered where its three edge functions in the projected vertices agree in sign
+        (both faces are visible, triangles that share an edge leave no crack), a triangle with a vertex in front of ``camera.near``
+        is culled WHOLE (no clipping), as are triangles with an index outside the vertices or a non-finite vertex; of equal depths the
+        lower row wins.  The pixel is the perspective-correct mix of the winner's ``vertex_colors`` (V,3) float64 - or ``color`` without
+        them - times light[0] + light[1] * |cos(face normal, ray)|, clamped to [0, 1] (NaN: 0) and truncated to uint8; light (1, 0)
+        leaves the colours flat.  Loop subdivision, textures and smooth vertex normals are the caller's.
+        The records take 144 bytes per frame and triangle, so the frames are drawn in groups whose records stay under
+        ``record_bytes`` (MESH_RECORD_BYTES = 512 MiB by default; a single frame past the bound is drawn alone).  The result does not
+        depend on the grouping.
+        Returns a dict: image (F,H,W,3) uint8; bin_total, a 0-d int64 device tensor - the (tile, triangle) list entries of all groups
+        together; index (F,H,W) int32 [return_index]: the winner's row in triangles, -1 for background; depth (F,H,W) float64
+        [return_depth]: its distance along the camera's z, +inf for background.
+        bin_capacity=None reads each group's number of list entries - one synchronisation per group - and sizes its list exactly.
+        With a bin_capacity, the capacity of a group's list, the call never synchronises; if a group needs more, nothing faults but the
+        image is INCOMPLETE: bin_total <= bin_capacity afterwards rules that out.  No atomics touch an output: results are
+        bit-identical from run to run."""
+        who = "render_mesh"
+        (light_a, light_b), num = self._render_numbers(who, camera, light, background, color=color)
+        if bin_capacity is not None and int(bin_capacity) < 0:
+            raise ValueError(f"{who}: bin_capacity must be >= 0, got {bin_capacity}")
+        bound = MESH_RECORD_BYTES if record_bytes is None else int(record_bytes)
+        if bound < 1:
+            raise ValueError(f"{who}: record_bytes must be >= 1, got {record_bytes}")
+        for name, t in (("vertices", vertices), ("triangles", triangles)) + ((("vertex_colors", vertex_colors),) if vertex_colors is not None else ()):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if vertices.dtype != torch.float64 or vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1:
+            raise ValueError(f"{who}: vertices must be (F,V,3) float64 with F, V >= 1, got {tuple(vertices.shape)} {vertices.dtype}")
+        F, V = int(vertices.shape[0]), int(vertices.shape[1])
+        if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3:
+            raise ValueError(f"{who}: triangles must be (M,3) int32, got {tuple(triangles.shape)} {triangles.dtype}")
+        M = int(triangles.shape[0])
+        if vertex_colors is not None and (vertex_colors.dtype != torch.float64 or tuple(vertex_colors.shape) != (V, 3)):
+            raise ValueError(f"{who}: vertex_colors must be ({V},3) float64, got {tuple(vertex_colors.shape)} {vertex_colors.dtype}")
+        H, W = camera.height, camera.width
+        if H * W >= 2 ** 31 or M >= 2 ** 31:
+            raise ValueError(f"{who}: {W} x {H} pixels and {M} triangles, one frame indexes fewer than 2^31 of either")
+        tensors = [("vertices", vertices), ("triangles", triangles)] + ([("vertex_colors", vertex_colors)] if vertex_colors is not None else [])
+        for name, t in tensors:
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous on the network's device, got {t.device}")
+        eng = self._engine
+        dev = eng._device()
+        for name, t in tensors:
+            if t.device != dev:
+                raise ValueError(f"{who}: {name} must be on the network's device ({dev}), got {t.device}")
+        eng.ready()
+        cam = camera.c_struct()
+        TX, TY = (W + 15) // 16, (H + 15) // 16
+        group = max(1, min(F, bound // max(1, 144 * M), (2 ** 31 - 1) // (H * W), (2 ** 31 - 1) // max(1, M)))
+        rec = torch.empty(group * M, 16, device=dev, dtype=torch.float64)
+        rect = torch.empty(group * M, 4, device=dev, dtype=torch.int32)
+        tile_offsets = torch.empty(group * TX * TY + 1, device=dev, dtype=torch.int64)
+        out = dict(image=torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8), bin_total=torch.zeros((), device=dev, dtype=torch.int64))
+        if return_index:
+            out["index"] = torch.empty(F, H, W, device=dev, dtype=torch.int32)
+        if return_depth:
+            out["depth"] = torch.empty(F, H, W, device=dev, dtype=torch.float64)
+        null = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        part = lambda t, f0: t[f0:].data_ptr() if t is not None else None
+        lst = torch.empty(int(bin_capacity), device=dev, dtype=torch.int32) if bin_capacity is not None else None
+        for f0 in range(0, F, group):
+            n = min(group, F - f0)
+            last = tile_offsets[n * TX * TY]
+            eng.call("nm_mesh_bin", vertices[f0:].data_ptr(), null(triangles), n, V, M, C.byref(cam), null(rec), null(rect), tile_offsets.data_ptr())
+            if bin_capacity is None:
+                lst = torch.empty(int(last.item()), device=dev, dtype=torch.int32)
+            out["bin_total"] += last
+            eng.call("nm_mesh_draw", null(rec), null(rect), tile_offsets.data_ptr(), null(triangles), null(vertex_colors), (C.c_double * 3)(*num["color"]),
+                     n, V, M, C.byref(cam), light_a, light_b, (C.c_double * 3)(*num["background"]), int(lst.numel()), null(lst),
+                     part(out.get("index"), f0), part(out.get("depth"), f0), out["image"][f0:].data_ptr())
+        return out
+
+    @torch.no_grad()
+    def render_skeleton(self, keypoints, parents, camera, threshold=0.2, radius=0.03, bone_radius=0.03, joint_colors=(0.7, 0.1, 0.0),
+                        bone_color=(0.0, 0.6, 0.1), light=(0.3, 0.7), background=(1.0, 1.0, 1.0), over=None, return_index: bool = False,
+                        return_depth: bool = False):
+        """Device version of vis_retarget.py's skeleton images (:514-547: drawSphere per visible joint, drawCone1 + drawCone2 per bone
+        into open3d's off-screen visualiser): ``keypoints`` (F,K,4) float32 (x, y, z, intensity; sample_retarget's (1,T,K,4) is taken
+        as (T,K,4)) with ``parents`` (K), K <= 32, drawn through ``camera`` in one launch (nm_skeleton_draw, csrc/nm_mesh.hip).  **Not
+        open3d's image**: the contract is include/nm355.h's (tests/mesh_ref.py restates it).  Joint k gets a sphere of ``radius`` iff
+        clip(intensity_k, 0, 1) >= ``threshold``, and a bone to parents[k] iff both are visible, parents[k] != k and the bone is not of
+        length 0; a bone is the script's double cone - two nappes sharing a base circle of ``bone_radius`` at a fifth of the bone from
+        the parent, apexes at the parent and at the child (drawCone2's 0.195 margin and + 1e-6 are not reproduced).  Spheres and nappes
+        are intersected analytically per pixel and shaded by light[0] + light[1] * |cos(surface normal, ray)|; spheres and bones that
+        reach in front of ``camera.near`` are not drawn.  ``joint_colors``: one colour or (K,3); ``bone_color``: one colour.
+        ``over`` (F,H,W,3) uint8: the skeleton is pasted over a COPY of it (the script's overlay :550, without its accident of treating
+        white skeleton pixels as background); the input is not modified.  Without it uncovered pixels take ``background``.
+        Returns a dict: image (F,H,W,3) uint8; index (F,H,W) int32 [return_index]: joint k's sphere is k, its bone K + k, -1 for
+        background; depth (F,H,W) float64 [return_depth]."""
+        who = "render_skeleton"
+        flat = not (isinstance(joint_colors, (torch.Tensor, np.ndarray)) and joint_colors.ndim == 2) and not (
+            isinstance(joint_colors, (list, tuple)) and len(joint_colors) and isinstance(joint_colors[0], (list, tuple)))
+        (light_a, light_b), num = self._render_numbers(who, camera, light, background, bone_color=bone_color, **(dict(joint_colors=joint_colors) if flat else {}))
+        try:
+            threshold, radius, bone_radius = float(threshold), float(radius), float(bone_radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: threshold, radius and bone_radius must be numbers") from None
+        for name, r in (("radius", radius), ("bone_radius", bone_radius)):
+            if not (r > 0.0 and r < float("inf")):
+                raise ValueError(f"{who}: {name} must be a finite number > 0, got {r}")
+        if not isinstance(keypoints, torch.Tensor):
+            raise ValueError(f"{who}: keypoints must be a tensor, got {type(keypoints).__name__}")
+        if keypoints.dim() == 4 and keypoints.shape[0] == 1:
+            keypoints = keypoints[0]
+        if keypoints.dtype != torch.float32 or keypoints.dim() != 3 or keypoints.shape[2] != 4 or keypoints.shape[0] < 1 or not 1 <= keypoints.shape[1] <= 32:
+            raise ValueError(f"{who}: keypoints must be (F,K,4) float32 with F >= 1 and 1 <= K <= 32, got {tuple(keypoints.shape)} {keypoints.dtype}")
+        F, K = int(keypoints.shape[0]), int(keypoints.shape[1])
+        par = torch.as_tensor(parents)
+        if par.dim() != 1 or par.numel() != K or par.is_floating_point():
+            raise ValueError(f"{who}: parents must be ({K}) integers, got {tuple(par.shape)} {par.dtype}")
+        jc = None
+        if not flat:
+            jc = torch.as_tensor(joint_colors)
+            if tuple(jc.shape) != (K, 3):
+                raise ValueError(f"{who}: joint_colors must be one colour or ({K},3), got {tuple(jc.shape)}")
+        H, W = camera.height, camera.width
+        if F * H * W >= 2 ** 31:
+            raise ValueError(f"{who}: {F} frames of {W} x {H} pixels, one call indexes fewer than 2^31")
+        if over is not None and (not isinstance(over, torch.Tensor) or over.dtype != torch.uint8 or tuple(over.shape) != (F, H, W, 3)):
+            raise ValueError(f"{who}: over must be ({F},{H},{W},3) uint8, got {tuple(over.shape) if isinstance(over, torch.Tensor) else type(over).__name__}")
+        if not keypoints.is_cuda or (over is not None and not over.is_cuda):
+            raise ValueError(f"{who}: keypoints and over must be on the network's device, got {keypoints.device}")
+        eng = self._engine
+        dev = eng._device()
+        if keypoints.device != dev or (over is not None and over.device != dev):
+            raise ValueError(f"{who}: keypoints and over must be on the network's device ({dev}), got {keypoints.device}")
+        eng.ready()
+        keypoints = keypoints.contiguous()
+        par = par.to(device=dev, dtype=torch.int32).contiguous()
+        if jc is not None:
+            jc = jc.to(device=dev, dtype=torch.float64).contiguous()
+        out = dict(image=over.clone(memory_format=torch.contiguous_format) if over is not None else torch.empty(F, H, W, 3, device=dev, dtype=torch.uint8))
+        if return_index:
+            out["index"] = torch.empty(F, H, W, device=dev, dtype=torch.int32)
+        if return_depth:
+            out["depth"] = torch.empty(F, H, W, device=dev, dtype=torch.float64)
+        cam = camera.c_struct()
+        raw = lambda t: t.data_ptr() if t is not None else None
+        eng.call("nm_skeleton_draw", keypoints.data_ptr(), par.data_ptr(), F, K, C.byref(cam), threshold, radius, bone_radius, raw(jc),
+                 (C.c_double * 3)(*num["joint_colors"]) if flat else None, (C.c_double * 3)(*num["bone_color"]), light_a, light_b,
+                 (C.c_double * 3)(*num["background"]), int(over is not None), raw(out.get("index")), raw(out.get("depth")), out["image"].data_ptr())
+        return out
+
+    @torch.no_grad()
+    def render_retarget(self, result, triangles, camera, skin_colors: bool = False, joint_colors=None, parents=None, threshold=0.2, radius=0.03,
+                        bone_radius=0.03, color=(0.7, 0.7, 0.7), joint_color=(0.7, 0.1, 0.0), bone_color=(0.0, 0.6, 0.1), light=(0.3, 0.7),
+                        background=(1.0, 1.0, 1.0), record_bytes: Optional[int] = None):
+        """vis_retarget.py's loop :497-553 from sample_retarget's dict ``result``: per frame the posed mesh (``triangles`` (M,3) int32 over
+        result['points']), the skeleton of the retargeted keypoints, the skeleton of the source keypoints, and the first pasted over
+        the mesh - render_mesh and render_skeleton, which see.  ``parents`` defaults to the learner's tree as sample_retarget left it.
+        skin_colors=True colours the mesh as :415 does, vertex_colors = skin_weights @ joint_colors with ``joint_colors`` (K,3) - a
+        torch matmul on the device; the spheres take ``joint_color`` either way, as in the script's loop.
+        Returns a dict of (T,H,W,3) uint8 images: mesh, skeleton, source_skeleton, overlay."""
+        who = "render_retarget"
+        if not isinstance(result, dict) or any(k not in result for k in ("points", "keypoints", "source_keypoints", "skin_weights")):
+            raise ValueError(f"{who}: result must be sample_retarget's dict with 'points', 'keypoints', 'source_keypoints' and 'skin_weights'")
+        vc = None
+        if skin_colors:
+            if joint_colors is None:
+                raise ValueError(f"{who}: skin_colors needs joint_colors (K,3)")
+            w = result["skin_weights"]
+            jc = torch.as_tensor(joint_colors)
+            if jc.dim() != 2 or tuple(jc.shape) != (int(w.shape[1]), 3):
+                raise ValueError(f"{who}: joint_colors must be ({int(w.shape[1])},3), got {tuple(jc.shape)}")
+            vc = (w.double() @ jc.to(device=w.device, dtype=torch.float64)).contiguous()
+        if parents is None:
+            parents = self.dyna_module.parents
+            if parents is None:
+                raise ValueError(f"{who}: the learner has no tree yet: pass parents (K)")
+        common = dict(light=light, background=background)
+        mesh = self.render_mesh(result["points"], triangles, camera, vertex_colors=vc, color=color, record_bytes=record_bytes, **common)["image"]
+        skel = dict(threshold=threshold, radius=radius, bone_radius=bone_radius, joint_colors=joint_color, bone_color=bone_color, **common)
+        drawn = self.render_skeleton(result["keypoints"], parents, camera, return_index=True, **skel)
+        skeleton = drawn["image"]
+        source = self.render_skeleton(result["source_keypoints"], parents, camera, **skel)["image"]
+        overlay = torch.where((drawn["index"] >= 0)[..., None], skeleton, mesh)     # render_skeleton(over=mesh) without a second launch
+        return dict(mesh=mesh, skeleton=skeleton, source_skeleton=source, overlay=overlay)
 
     def _points(self, who, vox, return_points):
         """the drivers' ``return_points``: True - occupied_points(vox, 0.5, return_depth=True); "surface" - surface_points(vox, 0.5)"""
