@@ -154,6 +154,19 @@ struct NmDeviceOnce {
     void mark() { mask |= bit(); }
 };
 int nm_check_hip(hipError_t e, const char* what);
+// raises the dynamic-LDS limit of the given kernels to `bytes`, once per device; `what` goes to nm_check_hip with the first failure
+template <typename... K>
+int nm_raise_lds_limit(NmDeviceOnce& once, int bytes, const char* what, K... kernels) {
+    if (once.done()) return NM_OK;
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+    if (e != hipSuccess) return nm_check_hip(e, what);
+    once.mark();
+    return NM_OK;
+}
+// compute units of the current device (256 where the runtime reports none), asked once per process; 0 with the error set when the
+// query fails
+int nm_num_cus();
 // the catch-all of every extern "C" entry point (no C++ exception crosses the ABI): message for nm_last_error(), NM_ERR_INTERNAL
 int nm_abi_catch(const char* fn) noexcept;
 
@@ -183,7 +196,7 @@ struct NmLaunchState {
     unsigned* nf_flag = nullptr;           // sticky device word gn_finalize ORs a 1 into (null: no reporting)
     // A/B and diagnostic switches (NM355_SUPERTILE, _SMALL16, _KSPLIT, _OCC16, _POOL16, _F16P2, _F16P, _WGRAD_TR, _UP2C, _UP2C_DIAG,
     // _VRNN_MID, _VRNN_GEMM, _VRNN_GRAPH, _SPARSE_FIRST, ..., _UP2Y_YPAD, _UP2C_SHELL)
-    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, wgrad_u, tail_rank1, wgrad_z, up2c, up2c_diag, vrnn_mid, vrnn_postmid, vrnn_nb, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, f16p_dma, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, up2c_x16, up2c_all, f16p_late, p2_defer, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell;
+    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, wgrad_u, tail_rank1, wgrad_z, up2c, up2c_diag, vrnn_mid, vrnn_postmid, vrnn_nb, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, f16p_dma, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, up2c_x16, up2c_all, p2_defer, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell;
     NmLaunchState();
 };
 NmLaunchState& nm_ls();        // the state of the context whose ABI call runs on this thread
@@ -229,7 +242,7 @@ bool nm_conv_pool16_eligible(int Cin, int OD, int OH, int OW, bool have_w16);
 void nm_conv_prof_enable(int on, hipStream_t stream);
 int nm_conv_prof_collect(int variant, double* ms_total, double* flops_total, long long* launches);
 void nm_conv_prof_reset();
-// a launch (sequence) outside nm_conv.hip bracketed for the same profiler: begin records the first event when the profiler is on for
+// a launch (sequence) bracketed for the profiler: begin records the first event when the profiler is on for
 // stream s, end the second and files the record under `variant` (nm_prof_kernel_name)
 struct NmProfScope {
     bool on = false; NmProfRec rec{}; hipStream_t s = nullptr;

@@ -1746,18 +1746,8 @@ __global__ __launch_bounds__(256, 2) void conv_pool_f16q_kernel(ConvParams p) {
 typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 
 // IO: bit 0 = bfloat16 input (a producer piece is then an 8-byte load of the same four channels), bit 1 = bfloat16 output
-// LATE (round 6; NM355_F16P_LATE=1 - opt-in, NOT the default: the schedule below is 5 % faster on this kernel, and on some boxes one
-// evaluation in ~1500 of the detector's training forward came back non-finite under it, never under the round-2 schedule - a load still in
-// flight somewhere in the two-step body; not root-caused in the round, profiles/r06_not_shipped_ab.txt): in-kernel stamps of the 32 -> 32 @64^3 layer
-// (tools/diag_f16p_steps.py) showed the MFMA waves waiting 760 + 1188 of a 10 400-tick step at the first two barriers - the producers
-// arrive last there: each weight group was loaded and WAITED for inside the phase that stores it (an L2 round trip per phase, the whole
-// third phase nothing else), and the tile of step s + 1 had to be complete at the SECOND barrier (pieces dealt 4 / 6 / 0).  As in
-// conv_f16p2 since round 3: the tile is complete at the step's LAST barrier (pieces 3 / 4 / 3; the MFMA waves request a step's first two
-// taps' A operands behind that barrier instead of during taps 25 / 26), and every weight group is requested one phase before it is
-// stored (two register sets, their roles alternate with the step's parity).
-template <bool UP2, bool SINGLE = false, int IO = 0, int LATE_ = 1>
+template <bool SINGLE = false, int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
-    constexpr bool LATE = LATE_ == 1, LATE_M = LATE_ != 0;      // (LATE_ == 2: diagnostic - old producer schedule, MFMA waves read the next tile late)
     constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
     constexpr unsigned EB = IH ? 2u : 4u;                           // bytes per input element
     constexpr int HV = 600, ZP = 100, HX = 10;
@@ -1832,9 +1822,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
         }
         using RawT = std::conditional_t<IH, nm_u32x2, f32x4>;
-        RawT raw[NP]; f32x4 sc, sh, scB = {0.f, 0.f, 0.f, 0.f}, shB = scB, wreg[5], wreg2[5];      // (scB / shB: LATE's second affine pair)
+        RawT raw[NP]; f32x4 sc, sh, wreg[5];
 #pragma unroll
-        for (int i = 0; i < 5; ++i) { wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f}; wreg2[i] = wreg[i]; }       // (SINGLE uses three of them; all five are operands of the counted waits)
+        for (int i = 0; i < 5; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};       // (SINGLE uses three of them; all five are operands of the counted waits)
         const bool has_affine = p.in_scale != nullptr;
         const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * EB;   // halo voxel (1,1,1): always inside
         // bit k: piece k of a brick's halo tile lies inside the volume
@@ -1857,20 +1847,17 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             if constexpr (IH) raw[k] = load8_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
             else raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
         };
-        auto load_affine = [&](const Work& w, int cb, auto AFF) {             // always two loads: the waits below count instructions
+        auto load_affine = [&](const Work& w, int cb) {                       // always two loads: the waits below count instructions
             const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
             const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            if constexpr (decltype(AFF)::value) { scB = load16_untracked(ps, 16u * quad); shB = load16_untracked(ph, 16u * quad); }
-            else { sc = load16_untracked(ps, 16u * quad); sh = load16_untracked(ph, 16u * quad); }
+            sc = load16_untracked(ps, 16u * quad); sh = load16_untracked(ph, 16u * quad);
         };
         // wait until all but the N youngest vector-memory operations are done; ties every load destination to the wait
 #define NM_PRODUCER_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" \
             : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]), "+v"(raw[6]), "+v"(raw[7]), \
-              "+v"(raw[8]), "+v"(raw[9]), "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]), "+v"(wreg[4]), \
-              "+v"(wreg2[0]), "+v"(wreg2[1]), "+v"(wreg2[2]), "+v"(wreg2[3]), "+v"(wreg2[4]), "+v"(scB), "+v"(shB) :: "memory")
-        auto convert = [&](int buf, unsigned mask, auto K, auto AFF) {        // activate, split, write piece k into halo buffer buf (AFF: affine pair)
+              "+v"(raw[8]), "+v"(raw[9]), "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]), "+v"(wreg[4]) :: "memory")
+        auto convert = [&](int buf, unsigned mask, auto K) {                  // activate, split, write piece k into halo buffer buf
             constexpr int k = decltype(K)::value;
-            const f32x4& sc_ = decltype(AFF)::value ? scB : sc; const f32x4& sh_ = decltype(AFF)::value ? shB : sh;
             half4v hi4, lo4;
             const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
 #pragma unroll
@@ -1878,7 +1865,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
                 float v0, v1;
                 if constexpr (IH) { const unsigned u = raw[k][e >> 1]; v0 = nm_bf_lo(u); v1 = nm_bf_hi(u); }
                 else { v0 = raw[k][e]; v1 = raw[k][e + 1]; }
-                if (has_affine) { v0 = __builtin_fmaf(v0, sc_[e], sh_[e]); v1 = __builtin_fmaf(v1, sc_[e + 1], sh_[e + 1]); }
+                if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
                 // LeakyReLU (slope in (0, 1]) and the padding mask in two instructions per value: max(v, slope v) * keep
                 v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
                 half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
@@ -1910,15 +1897,15 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
         }
         // Through registers, not direct-to-LDS: an LDS-DMA instruction holds the issuing wave for ~200 cycles in this kernel
         // (15 per producer wave and step), a 16-byte load + ds_write_b128 pair a fraction of that.
-        auto load_b_group = [&](int cg, int cb, int g, auto SET) {
+        auto load_b_group = [&](int cg, int cb, int g) {
             const float* base = reinterpret_cast<const float*>(w8 + ((size_t)(9 * g) * C16 * 4 + (size_t)cb * 4) * plane + cg * 32);
 #pragma unroll
-            for (int i = 0; i < NWP; ++i) { if constexpr (decltype(SET)::value) wreg2[i] = load16_untracked(base, dma_src[i]); else wreg[i] = load16_untracked(base, dma_src[i]); }
+            for (int i = 0; i < NWP; ++i) wreg[i] = load16_untracked(base, dma_src[i]);
         };
-        auto store_b_group = [&](int g, auto SET) {
+        auto store_b_group = [&](int g) {
             char* lbase = reinterpret_cast<char*>(ldb + g * GB);
 #pragma unroll
-            for (int i = 0; i < NWP; ++i) *reinterpret_cast<f32x4*>(lbase + dma_dst[i]) = decltype(SET)::value ? wreg2[i] : wreg[i];
+            for (int i = 0; i < NWP; ++i) *reinterpret_cast<f32x4*>(lbase + dma_dst[i]) = wreg[i];
         };
 
         // The input runs two steps ahead of the MFMA waves: during step s the tile of step s+1 (loaded during step s-1) is
@@ -1930,80 +1917,18 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
         unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first two weight groups in the open, loads of the second tile in flight
-        load_b_group(cur.w.cg, 0, 0, ic<0>{});
-        load_affine(cur.w, 0, ic<0>{});
+        load_b_group(cur.w.cg, 0, 0);
+        load_affine(cur.w, 0);
         { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         NM_PRODUCER_WAIT(0);
-        store_b_group(0, ic<0>{});
-        load_b_group(cur.w.cg, 0, 1, ic<0>{});
-        static_for<NP>([&](auto K) { convert(0, m_cvt, K, ic<0>{}); });
+        store_b_group(0);
+        load_b_group(cur.w.cg, 0, 1);
+        static_for<NP>([&](auto K) { convert(0, m_cvt, K); });
         NM_PRODUCER_WAIT(0);
-        store_b_group(1, ic<0>{});
+        store_b_group(1);
         m_cvt = inside_mask(s1.w);
-        load_affine(s1.w, s1.cb, ic<0>{});
+        load_affine(s1.w, s1.cb);
         { const float* b = tile_base(s1.w, s1.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
-        if constexpr (LATE) {
-        // (weight group 2 of the first step: requested here, stored in its first phase)
-        load_b_group(cur.w.cg, cur.cb, 2, ic<0>{});
-        lds_barrier();
-        // Loads per step and thread, in issue order: phase 0 [W0' x NWP][pieces 0-2], phase 1 [W1' x NWP][pieces 3-6], phase 2 [W2' x NWP]
-        // [pieces 7-9][affine x 2]; Wg' = tap group g of the NEXT step (group 2: of the step after this phase, i.e. also the next).
-        // Set PAR holds the group requested in the previous phase.
-        auto step_body = [&](auto PARC) {
-            constexpr int PAR = decltype(PARC)::value;
-            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = inside_mask(s2.w);
-            else m_ld = m_cvt;
-            const float* b2 = tile_base(s2.w, s2.cb);
-            NM_PSTAMP(0);
-            // phase 0: request W0 of the next step; then wait for W2 of this step and everything older (this tile's pieces, its affine) - NOT
-            // for the three piece loads phase 2 has just issued (pieces 7-9 of the tile after this one: an HBM round trip)
-            load_b_group(s1.w.cg, s1.cb, 0, ic<PAR ^ 1>{});
-            if constexpr (SINGLE) { NM_PRODUCER_WAIT(6); } else { NM_PRODUCER_WAIT(8); }
-            NM_PSTAMP(1);
-            static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K, ic<PAR>{}); load_piece(b2, m_ld, K); });
-            store_b_group(2, ic<PAR>{});                            // W2 of THIS step (buffer 2 was last read before the previous step's last barrier)
-            NM_PSTAMP(2);
-            lds_barrier();
-            NM_PSTAMP(3);
-            // phase 1: request W1 of the next step, store its W0 (younger than W0': 3 + NWP + 4 + 2 loads)
-            load_b_group(s1.w.cg, s1.cb, 1, ic<PAR>{});
-            static_for<4>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 3>{}, ic<PAR>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 3>{}); });
-            load_affine(s2.w, s2.cb, ic<PAR ^ 1>{});                 // the NEXT tile's affine into the other pair, a phase and a half before its first use
-            NM_PSTAMP(4);
-            if constexpr (SINGLE) { NM_PRODUCER_WAIT(12); } else { NM_PRODUCER_WAIT(14); }
-            store_b_group(0, ic<PAR ^ 1>{});
-            NM_PSTAMP(5);
-            lds_barrier();
-            NM_PSTAMP(6);
-            // phase 2: request W2 of the next step (stored in its phase 0), store its W1 (younger than W1': 4 + 2 + NWP + 3); the tile of
-            // step s + 1 is complete at this barrier
-            load_b_group(s1.w.cg, s1.cb, 2, ic<PAR ^ 1>{});
-            static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 7>{}, ic<PAR>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 7>{}); });
-            if constexpr (SINGLE) { NM_PRODUCER_WAIT(12); } else { NM_PRODUCER_WAIT(14); }
-            store_b_group(1, ic<PAR>{});
-            NM_PSTAMP(7);
-            lds_barrier();
-            NM_PSTAMP(8);
-        };
-        // ONE straight-line body of two steps (the register sets swap roles with the step's parity): with the two parities as two
-        // branches of a loop the compiler reconciles their register assignments at the join - by moving registers whose untracked loads
-        // are still in flight (wrong weights whenever consecutive steps differ by more than their parity: found by the C16 = 4 tests)
-        auto next_step = [&]() {
-            cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
-            m_cvt = m_ld; hb ^= 1;
-#ifdef NM_DIAG
-            ++step_no;
-#endif
-        };
-        for (;;) {
-            step_body(ic<0>{});
-            if (!has1) break;
-            next_step();
-            step_body(ic<1>{});
-            if (!has1) break;
-            next_step();
-        }
-        } else {
         lds_barrier();
         for (;;) {
             // the tile being loaded (step s+2); its inside mask changes only with the brick
@@ -2013,29 +1938,29 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             NM_PSTAMP(0);
             // tap group 0: weights of this step's group 2; pieces 0-3.  Everything older than the 5 weight loads has landed
             // after the first wait (the tile of step s+1 and its affine were issued a step ago).
-            load_b_group(cur.w.cg, cur.cb, 2, ic<0>{});
+            load_b_group(cur.w.cg, cur.cb, 2);
             if constexpr (SINGLE) { NM_PRODUCER_WAIT(3); } else { NM_PRODUCER_WAIT(5); }      // (the NWP weight loads are the youngest)
             NM_PSTAMP(1);
-            static_for<4>([&](auto K) { convert(hb ^ 1, m_cvt, K, ic<0>{}); load_piece(b2, m_ld, K); });
+            static_for<4>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
             NM_PRODUCER_WAIT(4);                                    // the weight loads (older than the 4 new piece loads)
-            store_b_group(2, ic<0>{});
+            store_b_group(2);
             NM_PSTAMP(2);
             lds_barrier();
             NM_PSTAMP(3);
             // tap group 1: weights of the next step's group 0; pieces 4-9; the halo tile is complete at this barrier
-            load_b_group(s1.w.cg, s1.cb, 0, ic<0>{});
-            static_for<6>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 4>{}, ic<0>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 4>{}); });
-            load_affine(s2.w, s2.cb, ic<0>{});                               // (sc / sh are free: piece 9 was their last user)
+            load_b_group(s1.w.cg, s1.cb, 0);
+            static_for<6>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 4>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 4>{}); });
+            load_affine(s2.w, s2.cb);                               // (sc / sh are free: piece 9 was their last user)
             NM_PSTAMP(4);
             NM_PRODUCER_WAIT(8);                                    // the weight loads: 6 piece + 2 affine loads are younger
-            store_b_group(0, ic<0>{});
+            store_b_group(0);
             NM_PSTAMP(5);
             lds_barrier();
             NM_PSTAMP(6);
             // tap group 2: weights of the next step's group 1
-            load_b_group(s1.w.cg, s1.cb, 1, ic<0>{});
+            load_b_group(s1.w.cg, s1.cb, 1);
             NM_PRODUCER_WAIT(0);                                    // (everything: the input loads are a group or more old)
-            store_b_group(1, ic<0>{});
+            store_b_group(1);
             NM_PSTAMP(7);
             lds_barrier();
             NM_PSTAMP(8);
@@ -2045,7 +1970,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 #ifdef NM_DIAG
             ++step_no;
 #endif
-        }
         }
         NM_PRODUCER_WAIT(0);                                        // loads still in flight for a step that does not exist
         lds_barrier();                                              // the two barriers of the MFMA waves' drain
@@ -2103,13 +2027,13 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             *reinterpret_cast<f32x2*>(red + (wave * 32 + c) * 2) = f32x2{outv[0][r], outv[1][r]};
         }
     };
-    auto epi_part = [&]() {                                         // after a barrier: 32 threads sum the four wave partials
+    auto epi_part = [&](const Work& w) {                            // after a barrier: 32 threads sum the four wave partials of brick w
         if (p.part && tid < 32) {
             float a = 0.f, b = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) { a += red[(i * 32 + tid) * 2]; b += red[(i * 32 + tid) * 2 + 1]; }
-            const int br = ((epi.oz0 >> 2) * nby + (epi.oy0 >> 3)) * nbx + (epi.ox0 >> 3);
-            float* dst = p.part + (((size_t)epi.n * nbr + br) * p.Cout + epi.cg * 32 + tid) * 2;
+            const int br = ((w.oz0 >> 2) * nby + (w.oy0 >> 3)) * nbx + (w.ox0 >> 3);
+            float* dst = p.part + (((size_t)w.n * nbr + br) * p.Cout + w.cg * 32 + tid) * 2;
             dst[0] = a; dst[1] = b;
         }
     };
@@ -2146,13 +2070,14 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
                        "+v"(bhv[0]), "+v"(blv[0]), "+v"(bhv[1]), "+v"(blv[1]) :: "memory");
     }
     bool pending = false;                                           // outv / epi hold a brick whose epilogue has not run
-    bool part_due = false;                                          // red[] holds that brick's partial sums
+    bool part_due = false;                                          // red[] holds the partial sums of brick part_w
+    Work part_w = epi;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     for (;;) {
         Step nxt = cur;
         const bool has_next = advance(nxt);
-        if (part_due) { epi_part(); part_due = false; }
+        if (part_due) { epi_part(part_w); part_due = false; }
         const bool run_epi = pending;
         // One read per MFMA gap, issued two taps (12 MFMAs, ~400 cycles) before its first use; before each MFMA "all but the
         // 10 youngest LDS operations are done" covers both of its operands (other LDS traffic only makes that stricter).
@@ -2177,16 +2102,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             constexpr int AO = (ug * ZP + (ut / 3) * HX + (ut % 3)) * 16;          // byte offsets of tap tt + 2 (taps 25, 26: of the
             constexpr int BO = (ug * GB + ut * 128) * 16;                           // next step's taps 0, 1)
             const unsigned vau = (u < 27) ? va : van;
-            constexpr bool aread = !LATE_M || u < 27;               // LATE: the next tile is complete only at the step's last barrier
 #define NM_WAIT_OPERANDS(x, y) asm volatile("" : "+v"(x), "+v"(y))
             // one wait per tap: this tap's six operands were issued during tap tt - 2; the six reads of tap tt - 1 are the only
             // younger LDS operations (anything else in the gaps only makes the wait stricter)
-            // (LATE: tap 25 requests only the two B operands of the next step's tap 0 - its A operands wait for the step's last barrier -
-            //  so at tap 26 the reads of tap 24 are covered by "all but the 2 youngest")
-            if constexpr (LATE_M && tt == 26)
-                asm volatile("s_waitcnt lgkmcnt(2)"
-                             : "+v"(ah0[i]), "+v"(al0[i]), "+v"(ah1[i]), "+v"(al1[i]), "+v"(bhv[i]), "+v"(blv[i]) :: "memory");
-            else
             asm volatile("s_waitcnt lgkmcnt(6)"
                          : "+v"(ah0[i]), "+v"(al0[i]), "+v"(ah1[i]), "+v"(al1[i]), "+v"(bhv[i]), "+v"(blv[i]) :: "memory");
             __builtin_amdgcn_sched_barrier(0);
@@ -2199,7 +2117,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             NM_WAIT_OPERANDS(ah0[i], blv[i]);
             if constexpr (tt == 0 && with_epi) accl[0] = nm_mfma_lo<SINGLE>(blv[i], ah0[i], zero16);
             else accl[0] = nm_mfma_lo<SINGLE>(blv[i], ah0[i], accl[0]);
-            if constexpr (aread) ah0[j] = lds_read16_untracked<AO>(vau);
+            ah0[j] = lds_read16_untracked<AO>(vau);
             gap(ic<1>{});
             __builtin_amdgcn_sched_barrier(0);
             NM_WAIT_OPERANDS(ah1[i], bhv[i]);
@@ -2211,17 +2129,17 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             NM_WAIT_OPERANDS(ah1[i], blv[i]);
             if constexpr (tt == 0 && with_epi) accl[1] = nm_mfma_lo<SINGLE>(blv[i], ah1[i], zero16);
             else accl[1] = nm_mfma_lo<SINGLE>(blv[i], ah1[i], accl[1]);
-            if constexpr (aread) ah1[j] = lds_read16_untracked<AO + YO>(vau);
+            ah1[j] = lds_read16_untracked<AO + YO>(vau);
             gap(ic<3>{});
             __builtin_amdgcn_sched_barrier(0);
             NM_WAIT_OPERANDS(al0[i], bhv[i]);
             accl[0] = nm_mfma_lo<SINGLE>(bhv[i], al0[i], accl[0]);
-            if constexpr (aread) al0[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO>(vau);
+            al0[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO>(vau);
             gap(ic<4>{});
             __builtin_amdgcn_sched_barrier(0);
             NM_WAIT_OPERANDS(al1[i], bhv[i]);
             accl[1] = nm_mfma_lo<SINGLE>(bhv[i], al1[i], accl[1]);
-            if constexpr (aread) al1[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO + YO>(vau);
+            al1[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO + YO>(vau);
             gap(ic<5>{});
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (t == 8) {
@@ -2233,12 +2151,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
                 NM_PSTAMP(2 + 2 * (tt / 9));
             }
         });
-        if constexpr (LATE_M) {                                     // the next step's tile is complete since the barrier of tap 26
-            ah0[0] = lds_read16_untracked<0>(van); al0[0] = SINGLE ? half8{} : lds_read16_untracked<LO>(van);
-            ah1[0] = lds_read16_untracked<YO>(van); al1[0] = SINGLE ? half8{} : lds_read16_untracked<LO + YO>(van);
-            ah0[1] = lds_read16_untracked<16>(van); al0[1] = SINGLE ? half8{} : lds_read16_untracked<LO + 16>(van);
-            ah1[1] = lds_read16_untracked<YO + 16>(van); al1[1] = SINGLE ? half8{} : lds_read16_untracked<LO + YO + 16>(van);
-        }
         // the operands of the next step's taps 0, 1 were read one / two gaps ago; the two copies of the stream may keep them in
         // different registers, so they must have landed before the compiler moves them
         asm volatile("s_waitcnt lgkmcnt(0)"
@@ -2246,7 +2158,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
                        "+v"(bhv[0]), "+v"(blv[0]), "+v"(bhv[1]), "+v"(blv[1]) :: "memory");
         };
         if (run_epi) stream(std::true_type{}); else stream(std::false_type{});
-        if (run_epi) { pending = false; part_due = true; }
+        if (run_epi) { pending = false; part_due = true; part_w = epi; }      // (epi_take may name the next brick at once: one-chunk layers)
         if (cur.cb == C16 - 1) { epi_take(cur.w); pending = true; }
         NM_PSTAMP(7);
         if (!has_next) break;
@@ -2256,14 +2168,14 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 #endif
     }
     // ---- drain: the last brick's epilogue in the open
-    if (part_due) epi_part();
+    if (part_due) epi_part(part_w);
     lds_barrier();
     static_for<8>([&](auto E) { epi_store(E); });
     static_for<16>([&](auto R) { epi_sum_local(R); });
     static_for<160>([&](auto I) { epi_sum_lanes(I); });
     static_for<16>([&](auto R) { epi_red(R); });
     lds_barrier();
-    epi_part();
+    epi_part(epi);
 }
 
 // ---- conv_f16p2: the producer / consumer kernel with 64 output channels per step -------------------------------------
@@ -2277,12 +2189,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 //     the barrier that publishes them; operands one tap (12 MFMAs) ahead, double buffered.
 //   LDS: halo [2][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [2][9 taps][4 planes][64] x 16 B, GroupNorm scratch, bias.
 // IO: bit 0 = bfloat16 input (a producer piece is then an 8-byte load of the same four channels), bit 1 = bfloat16 output
-// WEMU (diagnostic build only, tools/diag_winograd_emu.py; WRONG RESULTS): the resource profile of a 1-D Winograd F(2,3) form of this
-// kernel along z - the one fast-convolution form whose accumulators (4 positions x 32 tile rows x 64 channels = 128 registers in the
-// single-accumulator form) and transformed tile (8 planes for 6) fit this machine mapping - without its arithmetic: bit 0 = a step is
-// 4 position groups x 9 (ky, kx) taps x 6 MFMAs (216 for 324), one A tile and the four B reads per tap, FOUR weight groups and four
-// barriers per step; bit 1 = the producers also convert 13 pieces for 10 (8 transformed planes for 6 raw ones; the extra loads and the
-// transform's adds are left out).  An upper bound of what such a kernel could reach, DESIGN 4 "Why there is no Winograd kernel".
 // DEFER (round 6; NM355_P2_DEFER=1, NOT the default - built, correct, slower): in-kernel stamps (tools/diag_f16p2_steps.py) put the
 // exposed epilogue at 7 800 of a 64-channel brick's 58 000 cycles (24 % at Cin = 32) - 128 values per lane to combine, store, square,
 // sum over 32 lanes (320 DPP adds) and park, all on the vector ALU with the matrix pipe idle.  With ONE accumulator per tile
@@ -2296,9 +2202,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 // registers the brick decode's hoisted division constants spill (a scratch reload per step).  What would be left after moving the
 // decode to the producers (an LDS ring of brick origins): <= 5 % of this kernel.  The exposed epilogue got the cheap part instead:
 // its arithmetic on value pairs (v_pk_*), 8 900 -> 8 160 stamped cycles.
-template <bool UP2, bool SINGLE = false, int IO = 0, int WEMU = 0, bool DEFER = false>
+template <bool SINGLE = false, int IO = 0, bool DEFER = false>
 __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
-    static_assert(!DEFER || (!SINGLE && WEMU == 0), "the deferred epilogue exists for the three-product form");
+    static_assert(!DEFER || !SINGLE, "the deferred epilogue exists for the three-product form");
     constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
     constexpr unsigned EB = IH ? 2u : 4u;                           // bytes per input element
     constexpr int HV = 600, ZP = 100, HX = 10;
@@ -2499,7 +2405,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             load_b_group(cur.w.cg, cur.cb, 1, gpar ^ 1);
             if constexpr (SINGLE) { NM_PRODUCER2_WAIT(5); } else { NM_PRODUCER2_WAIT(9); }      // (NW weight loads are the youngest)
             NM_PSTAMP(1);
-            static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K); if constexpr ((WEMU & 2) != 0 && decltype(K)::value == 0) convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
+            static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
             NM_PRODUCER2_WAIT(3);                                   // the weight loads (older than the 3 new piece loads)
             store_b_group(gpar ^ 1);
             NM_PSTAMP(2);
@@ -2507,19 +2413,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             NM_PSTAMP(3);
             // tap group 1: weights of this step's group 2; pieces 3-7
             load_b_group(cur.w.cg, cur.cb, 2, gpar ^ 1);
-            if constexpr (WEMU != 0) {                              // (emulation: pieces 3-5 here, 6-7 behind a fourth weight group)
-                static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 3>{}); if constexpr ((WEMU & 2) != 0 && decltype(K)::value == 0) convert(hb ^ 1, m_cvt, ic<3>{});
-                                            load_piece(b2, m_ld, ic<decltype(K)::value + 3>{}); });
-                NM_PRODUCER2_WAIT(3);
-                store_b_group(gpar ^ 1);
-                lds_barrier(); gpar ^= 1;
-                load_b_group(cur.w.cg, cur.cb, 1, gpar ^ 1);
-                static_for<2>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 6>{}); if constexpr ((WEMU & 2) != 0 && decltype(K)::value == 0) convert(hb ^ 1, m_cvt, ic<6>{});
-                                            load_piece(b2, m_ld, ic<decltype(K)::value + 6>{}); });
-                NM_PRODUCER2_WAIT(2);
-                store_b_group(gpar ^ 1);
-                lds_barrier(); gpar ^= 1;
-            } else {
             static_for<5>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 3>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 3>{}); });
             NM_PSTAMP(4);
             NM_PRODUCER2_WAIT(5);                                   // the weight loads: 5 piece loads are younger
@@ -2527,7 +2420,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             NM_PSTAMP(5);
             lds_barrier(); gpar ^= 1;
             NM_PSTAMP(6);
-            }
             // tap group 2: weights of the next step's group 0; pieces 8-9; the halo tile is complete at this barrier
             load_b_group(s1.w.cg, s1.cb, 0, gpar ^ 1);
             static_for<2>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 8>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 8>{}); });
@@ -2761,8 +2653,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
         const unsigned van = (unsigned)(size_t)(ldh + (hb ^ 1) * 4 * HV + h * HV + arow0);   // the next step's
         const unsigned vbe = vb0 + (unsigned)(gpar * GB * 16), vbo = vb0 + (unsigned)((gpar ^ 1) * GB * 16);   // buffers of groups 0/2 and 1
         NM_PSTAMP(0);
-        constexpr int NTAP = WEMU != 0 ? 36 : 27;
-        static_for<NTAP>([&](auto TT) {
+        static_for<27>([&](auto TT) {
             constexpr int tt = decltype(TT)::value, g = tt / 9, t = tt % 9, i = tt & 1, j = i ^ 1;
             const unsigned vb = (g & 1) ? vbo : vbe;
             constexpr int BT = t * 256 * 16;                        // byte offset of this tap in its weight buffer
@@ -2774,10 +2665,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(ah0[i]), "+v"(al0[i]), "+v"(ah1[i]), "+v"(al1[i]), "+v"(bh0[i]), "+v"(bh1[i]), "+v"(bl0[i]), "+v"(bl1[i]) :: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            constexpr int u = tt + 1, ug = (u < NTAP) ? (u / 9) % 3 : 0, ut = (u < NTAP) ? u % 9 : 0;
+            constexpr int u = tt + 1, ug = (u < 27) ? u / 9 : 0, ut = (u < 27) ? u % 9 : 0;
             constexpr int AO = (ug * ZP + (ut / 3) * HX + (ut % 3)) * 16;           // A byte offset of tap tt + 1
-            constexpr bool anext = u < NTAP;                        // (tap 26 requests nothing: the next tile is complete only at the step's last barrier)
-            constexpr bool a1 = WEMU == 0;                          // (emulation: one A tile per tap)
+            constexpr bool anext = u < 27;                          // (tap 26 requests nothing: the next tile is complete only at the step's last barrier)
             const unsigned vau = va;
             constexpr bool bnext = t < 8;                           // the next tap's weights are in this group's buffer
             constexpr int BN = (t + 1) * 256 * 16;
@@ -2785,27 +2675,25 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 #define NM_MFMA2L(ACC, B, A) ACC = nm_mfma_lo<SINGLE>(B, A, ACC); __builtin_amdgcn_sched_barrier(0)
             NM_MFMA2(acc[0][0], bh0[i], ah0[i]);  if constexpr (anext) ah0[j] = lds_read16_untracked<AO>(vau);
             NM_MFMA2(acc[0][1], bh1[i], ah0[i]);  if constexpr (anext) al0[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO>(vau);
-            NM_MFMA2L(accl[0][0], bl0[i], ah0[i]); if constexpr (anext && a1) ah1[j] = lds_read16_untracked<AO + YO>(vau); else if constexpr (bnext && !a1) bh0[j] = lds_read16_untracked<BN>(vb);
-            NM_MFMA2L(accl[0][1], bl1[i], ah0[i]); if constexpr (anext && a1) al1[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO + YO>(vau); else if constexpr (bnext && !a1) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb);
-            NM_MFMA2L(accl[0][0], bh0[i], al0[i]); if constexpr (bnext && a1) bh0[j] = lds_read16_untracked<BN>(vb); else if constexpr (bnext && !a1) bl0[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 128 * 16>(vb);
-            NM_MFMA2L(accl[0][1], bh1[i], al0[i]); if constexpr (bnext && a1) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb); else if constexpr (bnext && !a1) bl1[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 160 * 16>(vb);
-            if constexpr (a1) {
+            NM_MFMA2L(accl[0][0], bl0[i], ah0[i]); if constexpr (anext) ah1[j] = lds_read16_untracked<AO + YO>(vau);
+            NM_MFMA2L(accl[0][1], bl1[i], ah0[i]); if constexpr (anext) al1[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO + YO>(vau);
+            NM_MFMA2L(accl[0][0], bh0[i], al0[i]); if constexpr (bnext) bh0[j] = lds_read16_untracked<BN>(vb);
+            NM_MFMA2L(accl[0][1], bh1[i], al0[i]); if constexpr (bnext) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb);
             NM_MFMA2(acc[1][0], bh0[i], ah1[i]);  if constexpr (bnext) bl0[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 128 * 16>(vb);
             NM_MFMA2(acc[1][1], bh1[i], ah1[i]);  if constexpr (bnext) bl1[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 160 * 16>(vb);
             NM_MFMA2L(accl[1][0], bl0[i], ah1[i]);
             NM_MFMA2L(accl[1][1], bl1[i], ah1[i]);
             NM_MFMA2L(accl[1][0], bh0[i], al1[i]);
             NM_MFMA2L(accl[1][1], bh1[i], al1[i]);
-            }
             if constexpr (t == 8) {
                 // tap-group end: the producers publish the next group's weights (and, at the second barrier, the next tile)
-                NM_PSTAMP(1 + 2 * (g % 3));
+                NM_PSTAMP(1 + 2 * g);
                 asm volatile("s_barrier" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-                NM_PSTAMP(2 + 2 * (g % 3));
+                NM_PSTAMP(2 + 2 * g);
             }
         });
-        if constexpr (WEMU == 0) gpar ^= 1;                         // three groups per step
+        gpar ^= 1;                                                  // three groups per step
         // the next step's tile is complete since the barrier that ended tap group 2: request its first tap's A operands now (slot 0;
         // the step's first wait covers them)
         if (has_next) {
@@ -3641,7 +3529,6 @@ Tiling choose_tiling(const ConvGeom& g, int Cin) {
 // (records live in the context: NmLaunchState, nm_common.h).  By default only launches on the profiled context's main stream are
 // timed - a side-stream launch overlaps the main stream, so its event-to-event time is not its own; prof_all records those too
 // (bench.py lists them separately)
-typedef NmProfRec ProfRec;
 #define NM_PROF_ON(s) (nm_ls().prof_on && (nm_ls().prof_all || (s) == nm_ls().prof_stream))
 
 hipEvent_t prof_event() {
@@ -3652,25 +3539,15 @@ hipEvent_t prof_event() {
     return e;
 }
 
+// algorithmic work of a conv launch: real channels and taps, no padding
+double conv_flops(const ConvParams& p, double taps) { return 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * taps; }
+
 template <int MT, int NT>
 int launch_t(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) {
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<MT, NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv)");
-        attr_set.mark();
-    }
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * p.ks * p.ks * p.ks;
-        // algorithmic work: real channels and taps, no padding
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = (MT - 1) * 2 + (NT - 1);
-        (void)hipEventRecord(rec.a, s);
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv)", &conv_mfma_kernel<MT, NT>)) return rc;
+    NmProfScope prof(s, conv_flops(p, (double)p.ks * p.ks * p.ks), (MT - 1) * 2 + (NT - 1));
     hipLaunchKernelGGL((conv_mfma_kernel<MT, NT>), grid, dim3(256), t.lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
     return nm_check_hip(hipGetLastError(), "conv_mfma launch");
 }
 
@@ -3701,23 +3578,11 @@ template <int MT, int NT, int KS, bool UP2, bool SINGLE, int IO = 0>
 int launch_f16s_impl(const ConvParams& p_in, const Tiling& t, dim3 grid, hipStream_t s) {
     ConvParams p = p_in;
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_f16s)");
-        attr_set.mark();
-    }
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * p.ks * p.ks * p.ks;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = UP2 ? 10 + (NT - 1) : 5 + (NT - 1);      // the fused-upsample layers are families of their own
-        (void)hipEventRecord(rec.a, s);
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_f16s)", &conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>)) return rc;
     dim3 pgrid(min(grid.x, 512u), grid.y);                          // persistent: ~2 resident workgroups per CU
     choose_super_tile(p, (int)pgrid.x, p.nbz, p.nby, p.nbx);
+    NmProfScope prof(s, conv_flops(p, (double)p.ks * p.ks * p.ks), UP2 ? 10 + (NT - 1) : 5 + (NT - 1));      // the fused-upsample layers are families of their own
     hipLaunchKernelGGL((conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>), pgrid, dim3(256), t.lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
     return nm_check_hip(hipGetLastError(), "conv_f16s launch");
 }
 // 16-bit storage (p.in_h / p.out_h): the instantiations the training path of conv mode 4 needs - k1 layers at >= 32^3 (both tensors
@@ -3740,27 +3605,21 @@ int launch_f16s(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) 
 
 template <int NT, bool SINGLE>
 int launch_pool_f16s_impl(const ConvParams& p, dim3 grid, hipStream_t s) {
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * 8.0;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 8;
-        (void)hipEventRecord(rec.a, s);
-    }
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    if (io) {                                                       // 16-bit storage: the pool convs of the training path (input always bfloat16)
+    // 16-bit storage: the pool convs of the training path (one-product modes, input always bfloat16)
+    if (io && (!SINGLE || p.Cin > 128 || p.in2 || p.in_map || !(io & 1))) return io16_unsupported("conv_pool_f16q", p);
+    NmProfScope prof(s, conv_flops(p, 8.0), 8);
+    if (io) {
         if constexpr (SINGLE) {
-            if (p.Cin > 128 || p.in2 || p.in_map || !(io & 1)) return io16_unsupported("conv_pool_f16q", p);
             if (io == 3) hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, true, false, 3>), grid, dim3(256), 0, s, p);
             else hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, true, false, 1>), grid, dim3(256), 0, s, p);
-        } else return io16_unsupported("conv_pool_f16q", p);
+        }
     } else
     if (nm_ls().pool_q && p.Cin <= 128) {                           // (the affine table holds 128 channels)
         if (p.in2) hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, SINGLE, true>), grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, SINGLE, false>), grid, dim3(256), 0, s, p);
     } else
     hipLaunchKernelGGL((conv_pool_f16s_kernel<NT, SINGLE>), grid, dim3(256), 0, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
     return nm_check_hip(hipGetLastError(), "conv_pool_f16s launch");
 }
 template <int NT>
@@ -3768,171 +3627,78 @@ int launch_pool_f16s(const ConvParams& p, dim3 grid, hipStream_t s) {
     return nm_ls().single ? launch_pool_f16s_impl<NT, true>(p, grid, s) : launch_pool_f16s_impl<NT, false>(p, grid, s);
 }
 
-int g_num_cus = 0;
-
-template <bool UP2, bool SINGLE, int IO = 0, int LATE = 1>
-int launch_f16p_impl(const ConvParams& p_in, size_t lds_bytes, int work_items, hipStream_t s) {
-    ConvParams p = p_in;
+// The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks, 512 threads): one
+// workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues), the bricks in XCD
+// super-tile order where a brick is one work item
+template <auto KERNEL>
+int launch_persistent(const char* what_attr, const char* what_launch, int variant, bool super_tile, const ConvParams& p_in,
+                      size_t lds_bytes, int work_items, hipStream_t s) {
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16p_kernel<UP2, SINGLE, IO, LATE>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_f16p)");
-        attr_set.mark();
-    }
-    if (g_num_cus == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return nm_check_hip(hipErrorUnknown, "device query");
-        g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * 27.0;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 7;
-        (void)hipEventRecord(rec.a, s);
-    }
-    // persistent: one workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues)
-    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, g_num_cus) : g_num_cus));
-    if (p.Cout == 32) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);   // (one cout group per brick)
-    hipLaunchKernelGGL((conv_f16p_kernel<UP2, SINGLE, IO, LATE>), grid, dim3(512), lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
-    return nm_check_hip(hipGetLastError(), "conv_f16p launch");
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, what_attr, KERNEL)) return rc;
+    const int cus = nm_num_cus();
+    if (!cus) return NM_ERR_HIP;
+    ConvParams p = p_in;
+    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, cus) : cus));
+    if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);
+    NmProfScope prof(s, conv_flops(p, 27.0), variant);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds_bytes, s, p);
+    return nm_check_hip(hipGetLastError(), what_launch);
 }
-template <bool UP2>
-int launch_f16p(const ConvParams& p, size_t lds_bytes, int work_items, hipStream_t s) {
+
+template <bool SINGLE, int IO = 0>
+int launch_f16p_impl(const ConvParams& p, int work_items, hipStream_t s) {
+    const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)3 * 9 * 4 * 32 * 16 + (size_t)(256 + p.Cout) * sizeof(float);
+    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, lds_bytes, work_items, s);
+}
+int launch_f16p(const ConvParams& p, int work_items, hipStream_t s) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
     if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
         if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p", p);
-        return launch_f16p_impl<UP2, true, 3>(p, lds_bytes, work_items, s);
+        return launch_f16p_impl<true, 3>(p, work_items, s);
     }
-    if (nm_ls().f16p_late == 2) return launch_f16p_impl<UP2, false, 0, 2>(p, lds_bytes, work_items, s);
-    if (!nm_ls().f16p_late)      // (A/B: the round-2 producer schedule)
-        return nm_ls().single ? launch_f16p_impl<UP2, true, 0, 0>(p, lds_bytes, work_items, s) : launch_f16p_impl<UP2, false, 0, 0>(p, lds_bytes, work_items, s);
-    return nm_ls().single ? launch_f16p_impl<UP2, true>(p, lds_bytes, work_items, s) : launch_f16p_impl<UP2, false>(p, lds_bytes, work_items, s);
+    return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s) : launch_f16p_impl<false>(p, work_items, s);
 }
 
-template <bool UP2, bool SINGLE, int IO = 0, int WEMU = 0, bool DEFER = false>
-int launch_f16p2_impl(const ConvParams& p_in, size_t lds_bytes, int work_items, hipStream_t s) {
-    ConvParams p = p_in;
-#ifdef NM_Q2_DIAG
-    if constexpr (WEMU == 0 && !UP2 && !SINGLE && IO == 0) {       // diagnostic build: the Winograd resource-profile emulation (wrong results)
-        static const int wemu = getenv("NM355_P2_WEMU") ? atoi(getenv("NM355_P2_WEMU")) : 0;
-        if (wemu == 1) return launch_f16p2_impl<UP2, SINGLE, IO, 1>(p_in, lds_bytes, work_items, s);
-        if (wemu == 3) return launch_f16p2_impl<UP2, SINGLE, IO, 3>(p_in, lds_bytes, work_items, s);
-    }
-#endif
-    static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16p2_kernel<UP2, SINGLE, IO, WEMU, DEFER>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_f16p2)");
-        attr_set.mark();
-    }
-    if (g_num_cus == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return nm_check_hip(hipErrorUnknown, "device query");
-        g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * 27.0;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 9;
-        (void)hipEventRecord(rec.a, s);
-    }
-    // persistent: one workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues)
-    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, g_num_cus) : g_num_cus));
-    if (p.Cout == 64) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);   // (one cout group per brick)
-    hipLaunchKernelGGL((conv_f16p2_kernel<UP2, SINGLE, IO, WEMU, DEFER>), grid, dim3(512), lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
-    return nm_check_hip(hipGetLastError(), "conv_f16p2 launch");
+template <bool SINGLE, int IO = 0, bool DEFER = false>
+int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s) {
+    const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
+    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO, DEFER>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s);
 }
 // the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
 template <int IO, int DBG = 0>
-int launch_f16q2_impl(const ConvParams& p_in, int work_items, hipStream_t s) {
-    ConvParams p = p_in;
-    static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16q2_kernel<IO, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_f16q2)");
-        attr_set.mark();
-    }
-    if (g_num_cus == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return nm_check_hip(hipErrorUnknown, "device query");
-        g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s) {
     const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)2 * 27 * 2 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
     if (lds_bytes > 160 * 1024) { nm_set_error("conv_f16q2: %d output channels exceed the LDS budget", p.Cout); return NM_ERR_UNSUPPORTED; }
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * 27.0;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 14;
-        (void)hipEventRecord(rec.a, s);
-    }
-    // persistent: one workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues)
-    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, g_num_cus) : g_num_cus));
-    if (p.Cout == 64) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);   // (one cout group per brick)
-    hipLaunchKernelGGL((conv_f16q2_kernel<IO, DBG>), grid, dim3(512), lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
-    return nm_check_hip(hipGetLastError(), "conv_f16q2 launch");
+    return launch_persistent<&conv_f16q2_kernel<IO, DBG>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s);
 }
 // the one-product modes' kernel for the 32-output-channel layers (conv_f16r_kernel: resident weights); Cin = 16 C16T
 template <int IO, int C16T>
-int launch_f16r_impl(const ConvParams& p_in, int work_items, hipStream_t s) {
-    ConvParams p = p_in;
-    static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f16r_kernel<IO, C16T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_f16r)");
-        attr_set.mark();
-    }
-    if (g_num_cus == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return nm_check_hip(hipErrorUnknown, "device query");
-        g_num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s) {
     const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)27 * C16T * 64 * 16 + (size_t)(512 + 32) * sizeof(float) + 2048 + 256 + 1024;      // (+ the store slots of the lanes that hold no total)
-    ProfRec rec;
-    rec.flops = 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * 27.0;
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 15;
-        (void)hipEventRecord(rec.a, s);
-    }
-    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, g_num_cus) : g_num_cus));
-    choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);
-    hipLaunchKernelGGL((conv_f16r_kernel<IO, C16T>), grid, dim3(512), lds_bytes, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
-    return nm_check_hip(hipGetLastError(), "conv_f16r launch");
+    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, lds_bytes, work_items, s);
 }
-template <bool UP2>
-int launch_f16p2(const ConvParams& p, size_t lds_bytes, int work_items, hipStream_t s) {
+int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    if constexpr (!UP2) {
-        if (nm_ls().single && nm_ls().f16q2 && (io == 0 || io == 3) && p.Cout <= 1024) {
+    if (nm_ls().single && nm_ls().f16q2 && (io == 0 || io == 3) && p.Cout <= 1024) {
 #ifdef NM_Q2_DIAG
-            static const int dbg = getenv("NM355_Q2_DBG") ? atoi(getenv("NM355_Q2_DBG")) : 0;      // ablations of tools/diag_f16q2.py (diagnostic build only)
-            if (io == 3) switch (dbg) {
-                case 1: return launch_f16q2_impl<3, 1>(p, work_items, s); case 2: return launch_f16q2_impl<3, 2>(p, work_items, s);
-                case 3: return launch_f16q2_impl<3, 3>(p, work_items, s); case 4: return launch_f16q2_impl<3, 4>(p, work_items, s);
-                case 5: return launch_f16q2_impl<3, 5>(p, work_items, s); case 6: return launch_f16q2_impl<3, 6>(p, work_items, s);
-                case 7: return launch_f16q2_impl<3, 7>(p, work_items, s); case 8: return launch_f16q2_impl<3, 8>(p, work_items, s);
-                case 9: return launch_f16q2_impl<3, 9>(p, work_items, s); default: break;
-            }
-#endif
-            return io ? launch_f16q2_impl<3>(p, work_items, s) : launch_f16q2_impl<0>(p, work_items, s);
+        static const int dbg = getenv("NM355_Q2_DBG") ? atoi(getenv("NM355_Q2_DBG")) : 0;      // ablations of tools/diag_f16q2.py (diagnostic build only)
+        if (io == 3) switch (dbg) {
+            case 1: return launch_f16q2_impl<3, 1>(p, work_items, s); case 2: return launch_f16q2_impl<3, 2>(p, work_items, s);
+            case 3: return launch_f16q2_impl<3, 3>(p, work_items, s); case 4: return launch_f16q2_impl<3, 4>(p, work_items, s);
+            case 5: return launch_f16q2_impl<3, 5>(p, work_items, s); case 6: return launch_f16q2_impl<3, 6>(p, work_items, s);
+            case 7: return launch_f16q2_impl<3, 7>(p, work_items, s); case 8: return launch_f16q2_impl<3, 8>(p, work_items, s);
+            case 9: return launch_f16q2_impl<3, 9>(p, work_items, s); default: break;
         }
+#endif
+        return io ? launch_f16q2_impl<3>(p, work_items, s) : launch_f16q2_impl<0>(p, work_items, s);
     }
     if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
         if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p2", p);
-        return launch_f16p2_impl<UP2, true, 3>(p, lds_bytes, work_items, s);
+        return launch_f16p2_impl<true, 3>(p, work_items, s);
     }
-    if (nm_ls().single) return launch_f16p2_impl<UP2, true>(p, lds_bytes, work_items, s);
-    if (nm_ls().p2_defer) return launch_f16p2_impl<UP2, false, 0, 0, true>(p, lds_bytes, work_items, s);      // (A/B: the deferred epilogue, slower)
-    return launch_f16p2_impl<UP2, false>(p, lds_bytes, work_items, s);
+    if (nm_ls().single) return launch_f16p2_impl<true>(p, work_items, s);
+    if (nm_ls().p2_defer) return launch_f16p2_impl<false, 0, true>(p, work_items, s);      // (A/B: the deferred epilogue, slower)
+    return launch_f16p2_impl<false>(p, work_items, s);
 }
 
 #ifdef NM_DIAG
@@ -4024,11 +3790,14 @@ static bool use_up2c(const ConvGeom& g, int Cin) {
     return g.up2 && g.up2c && nm_ls().conv_mode == 1 && nm_up2c_eligible(g.OD / 2, g.OH / 2, g.OW / 2, Cin, g.Cout, g.ks, g.stride, g.pad);
 }
 
+// a k2 s2 p0 conv with tiling t goes to the pool kernels: split-fp16 weights, whole 16-channel chunks, 4 x 8 x 8 output bricks
+static bool pool16_case(const Tiling& t, int Cin, bool have_w16) {
+    return nm_ls().conv_mode == 1 && nm_ls().pool16 && have_w16 && Cin % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2;
+}
+
 bool nm_conv_pool16_eligible(int Cin, int OD, int OH, int OW, bool have_w16) {
-    if (!(nm_ls().conv_mode == 1 && nm_ls().pool16 && have_w16 && Cin % 16 == 0)) return false;
     ConvGeom g; g.ks = 2; g.stride = 2; g.pad = 0; g.OD = OD; g.OH = OH; g.OW = OW; g.Cout = Cin; g.Co_pad = (Cin + 31) & ~31;
-    const Tiling t = choose_tiling(g, Cin);
-    return t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2;
+    return pool16_case(choose_tiling(g, Cin), Cin, have_w16);
 }
 
 int nm_conv_blocks_per_frame(const ConvGeom& g, int Cin) {
@@ -4047,7 +3816,7 @@ void nm_conv_prof_enable(int on, hipStream_t stream) {
 // variant: see nm_prof_kernel_name.  Synchronises on the recorded events.
 int nm_conv_prof_collect(int variant, double* ms_total, double* flops_total, long long* launches) {
     double ms = 0.0, fl = 0.0; long long n = 0;
-    for (const ProfRec& r : nm_ls().prof) {
+    for (const NmProfRec& r : nm_ls().prof) {
         if (r.variant != variant) continue;
         if (hipEventSynchronize(r.b) != hipSuccess) return NM_ERR_HIP;
         float t = 0.f;
@@ -4070,9 +3839,19 @@ NmProfScope::~NmProfScope() {
     nm_ls().prof.push_back(rec);
 }
 
+int nm_num_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { (void)nm_check_hip(hipErrorUnknown, "device query"); return 0; }
+        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return cus;
+}
+
 void nm_conv_prof_reset() {
     NmLaunchState& l = nm_ls();
-    for (const ProfRec& r : l.prof) { l.event_pool.push_back(r.a); l.event_pool.push_back(r.b); }
+    for (const NmProfRec& r : l.prof) { l.event_pool.push_back(r.a); l.event_pool.push_back(r.b); }
     l.prof.clear();
 }
 
@@ -4093,17 +3872,10 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
     if ((in.brickmap || in.p2) && g.up2) { nm_set_error("conv: a brick-sparse input tensor can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG; }
     if (use_up2c(g, in.C)) {
         // the fused-upsample layers on the coarse grid with composite weights (nm_up2c.hip): main + shell launch, timed together
-        ProfRec rec;
-        rec.flops = 2.0 * in.N * (double)g.OD * g.OH * g.OW * g.Cout * (double)(cin_real > 0 ? cin_real : in.C) * 27.0;
-        if (nm_up2y_active()) rec.flops *= 0.5;      // the products conv_up2y_kernel PERFORMS: 4 x 27 per coarse voxel instead of the fine conv's 8 x 27 (halo rows not counted)
-        const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-        if (prof_rec) {
-            rec.a = prof_event(); rec.b = prof_event(); rec.variant = 12;
-            (void)hipEventRecord(rec.a, s);
-        }
-        const int rc = nm_launch_conv_up2c(in, g.up2c, bias, out, g.Cout, g.Co_pad, part, s, out_h);
-        if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
-        return rc;
+        double flops = 2.0 * in.N * (double)g.OD * g.OH * g.OW * g.Cout * (double)(cin_real > 0 ? cin_real : in.C) * 27.0;
+        if (nm_up2y_active()) flops *= 0.5;          // the products conv_up2y_kernel PERFORMS: 4 x 27 per coarse voxel instead of the fine conv's 8 x 27 (halo rows not counted)
+        NmProfScope prof(s, flops, 12);
+        return nm_launch_conv_up2c(in, g.up2c, bias, out, g.Cout, g.Co_pad, part, s, out_h);
     }
     Tiling t = choose_tiling(g, in.C);
     if (t.lds_bytes > 160 * 1024) { nm_set_error("conv: LDS tile %zu B too large", t.lds_bytes); return NM_ERR_UNSUPPORTED; }
@@ -4143,32 +3915,30 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
 #endif
     p.KC = t.KC; p.HZ = t.HZ; p.HY = t.HY; p.HX = t.HX; p.HV = t.HV; p.HVp = t.HVp; p.CVp = t.CVp; p.ZP = t.HY * t.HX;
     dim3 grid((unsigned)(in.N * t.nbz * t.nby * t.nbx), (unsigned)(g.Co_pad / (t.NT * 32)));
-    if (nm_ls().conv_mode == 1 && nm_ls().pool16 && w_packed16 && in.C % 16 == 0 && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2 &&
-        t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2) {
+    if (pool16_case(t, in.C, w_packed16 != nullptr) && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2) {
         p.w = static_cast<const float*>(w_packed16);
         return t.NT == 2 ? launch_pool_f16s<2>(p, grid, s) : launch_pool_f16s<1>(p, grid, s);
     }
-    if (nm_ls().conv_mode == 1 && nm_ls().f16p2 && w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
-        g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16 && g.Cout % 64 == 0) {
+    // the persistent producer / consumer kernels take k3 s1 p1 layers of whole 4 x 8 x 8 bricks, at least four of them along z
+    const bool k3_bricks = w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
+                           g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16;
+    if (nm_ls().conv_mode == 1 && nm_ls().f16p2 && k3_bricks && g.Cout % 64 == 0) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 64);
         p.w = static_cast<const float*>(w_packed16);
-        const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + g.Cout) * sizeof(float);
-        return launch_f16p2<false>(p, lds_bytes, work, s);
+        return launch_f16p2(p, work, s);
     }
-    if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && nm_ls().f16p && w_packed16 && (in.C == 32 || in.C == 64) && g.ks == 3 && g.stride == 1 &&
-        g.pad == 1 && !g.up2 && g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16 && g.Cout == 32 && (p.in_h != 0) == (p.out_h != 0)) {
+    if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && nm_ls().f16p && k3_bricks && (in.C == 32 || in.C == 64) && g.Cout == 32 &&
+        (p.in_h != 0) == (p.out_h != 0)) {
         // one-product modes, 32 output channels: the layer's weights stay in LDS (conv_f16r_kernel)
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8);
         p.w = static_cast<const float*>(w_packed16);
         if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s) : launch_f16r_impl<0, 2>(p, work, s);
         return p.in_h ? launch_f16r_impl<3, 4>(p, work, s) : launch_f16r_impl<0, 4>(p, work, s);
     }
-    if (nm_ls().conv_mode == 1 && nm_ls().f16p && w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
-        g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16 && g.Cout % 32 == 0 && (nm_ls().f16p == 1 || nm_ls().f16p_all || g.Cout == 32)) {
+    if (nm_ls().conv_mode == 1 && nm_ls().f16p && k3_bricks && g.Cout % 32 == 0 && (nm_ls().f16p == 1 || nm_ls().f16p_all || g.Cout == 32)) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 32);
         p.w = static_cast<const float*>(w_packed16);
-        const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)3 * 9 * 4 * 32 * 16 + (size_t)(256 + g.Cout) * sizeof(float);
-        return launch_f16p<false>(p, lds_bytes, work, s);
+        return launch_f16p(p, work, s);
     }
     if (nm_ls().conv_mode == 1 && w_packed16 && in.C % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2 &&
         g.stride == 1 && (g.ks == 1 || g.ks == 3) && t.HZ == g.ks + 3 && t.HY * t.HX * 2 <= 256) {
@@ -4226,17 +3996,12 @@ int nm_launch_conv_k5occ(const float* occ, int N, int G, const float* w_packed, 
     const int NT = (Co_pad % 64 == 0) ? 2 : 1;
     dim3 grid((unsigned)(N * nm_occ_blocks_per_frame(G)), (unsigned)(Co_pad / (NT * 32)));
     if (p.row_walk) grid.x /= (unsigned)(G >> 3);         // one workgroup per x-row of bricks (conv_k5occ_f16_kernel)
-    ProfRec rec;
-    rec.flops = 2.0 * N * (double)G * G * G * Cout * 4.0 * 125.0;   // the reference's dense k5 layer over 4 input channels
-    const bool prof_rec = NM_PROF_ON(s) && rec.flops >= nm_ls().prof_min_flops;
-    if (prof_rec) {
-        rec.a = prof_event(); rec.b = prof_event(); rec.variant = 4;
-        (void)hipEventRecord(rec.a, s);
+    // 16-bit storage: the dense training form on the f16 MFMA kernel only
+    if (out_h && (!(nm_ls().conv_mode == 1 && nm_ls().occ16 && nm_ls().single) || brickmap || Cout % 4)) {
+        nm_set_error("conv_k5occ: bfloat16 output needs conv mode 4, the dense (training) form and Cout %% 4 == 0"); return NM_ERR_UNSUPPORTED;
     }
-    if (out_h) {                                                    // 16-bit storage: the dense training form on the f16 MFMA kernel only
-        if (!(nm_ls().conv_mode == 1 && nm_ls().occ16 && nm_ls().single) || brickmap || Cout % 4) {
-            nm_set_error("conv_k5occ: bfloat16 output needs conv mode 4, the dense (training) form and Cout %% 4 == 0"); return NM_ERR_UNSUPPORTED;
-        }
+    NmProfScope prof(s, 2.0 * N * (double)G * G * G * Cout * 4.0 * 125.0, 4);   // the reference's dense k5 layer over 4 input channels
+    if (out_h) {
         if (NT == 2) hipLaunchKernelGGL((conv_k5occ_f16_kernel<2, true, false, true>), grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, true, false, true>), grid, dim3(256), 0, s, p);
     } else
@@ -4248,6 +4013,5 @@ int nm_launch_conv_k5occ(const float* occ, int N, int G, const float* w_packed, 
         else { if (nm_ls().single) hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, true>), grid, dim3(256), 0, s, p); else hipLaunchKernelGGL((conv_k5occ_f16_kernel<1>), grid, dim3(256), 0, s, p); }
     } else if (NT == 2) hipLaunchKernelGGL((conv_k5occ_kernel<2>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv_k5occ_kernel<1>), grid, dim3(256), 0, s, p);
-    if (prof_rec) { (void)hipEventRecord(rec.b, s); nm_ls().prof.push_back(rec); }
     return nm_check_hip(hipGetLastError(), "conv_k5occ launch");
 }

@@ -744,11 +744,7 @@ template <bool SINGLE, bool OH16, bool IH16>
 static int launch_convT2_f16(const TensorRef& in, const float* w, const float* bias, float* out, int Cout, int tpf, int tiles, size_t ldsb,
                              hipStream_t s, const float* out_mul) {
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convT2_f16_kernel<SINGLE, OH16, IH16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(convT2_f16)");
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(convT2_f16)", &convT2_f16_kernel<SINGLE, OH16, IH16>)) return rc;
     // persistent workgroups (each converts the weights into its LDS once): as many as fit the chip, at most one per four tiles
     const int per_cu = ldsb <= 40 * 1024 ? 3 : (ldsb <= 76 * 1024 ? 2 : 1);
     const dim3 g((unsigned)min((tiles + 3) / 4, 256 * per_cu));
@@ -781,14 +777,8 @@ int nm_launch_convT2(const TensorRef& in, const float* w, const float* bias, flo
     if (OD == 2 * in.D && OH == 2 * in.H && OW == 2 * in.W && Cout % 32 == 0 && in.C <= 128 && in.C % 8 == 0 && fvox % 32 == 0 && cvox >= 4096 &&
         fvox * 8 * Cout < ((size_t)1 << 31)) {
         static NmDeviceOnce attr_set;
-        if (!attr_set.done()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convT2_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convT2_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convT2_mfma_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&convT2_mfma_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(convT2_mfma)");
-            attr_set.mark();
-        }
+        if (int rc = nm_raise_lds_limit(attr_set, 96 * 1024, "hipFuncSetAttribute(convT2_mfma)", &convT2_mfma_kernel<false>, &convT2_mfma_kernel<true>,
+                                        &convT2_mfma_kernel<true, true>, &convT2_mfma_kernel<false, true>)) return rc;
         const int tpf = (int)(fvox / 32), tiles = (int)(cvox / 32);
         const size_t ldsb = (size_t)4 * 32 * (in.C + 4) * sizeof(float);
         const dim3 gm((unsigned)min((tiles + 3) / 4, 2048));

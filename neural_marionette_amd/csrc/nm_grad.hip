@@ -2465,12 +2465,7 @@ int launch_wgrad_t(const WgradPlan& q, hipStream_t s) {
         }
     }
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<MODE, NTW, HX, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            nm_set_error("wgrad: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-        }
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad: cannot raise the dynamic LDS limit", &wgrad_kernel<MODE, NTW, HX, HD>)) return rc;
     hipLaunchKernelGGL((wgrad_kernel<MODE, NTW, HX, HD>), dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
     return nm_check_hip(hipGetLastError(), "wgrad launch");
 }
@@ -2478,17 +2473,8 @@ int launch_wgrad_t(const WgradPlan& q, hipStream_t s) {
 
 int w16z_set_attr() {
     static NmDeviceOnce attr_z;
-    if (!attr_z.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16z_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            nm_set_error("wgrad16z: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-        }
-        attr_z.mark();
-    }
-    return NM_OK;
+    return nm_raise_lds_limit(attr_z, 160 * 1024, "wgrad16z: cannot raise the dynamic LDS limit", &wgrad16z_kernel<0>, &wgrad16z_kernel<1>,
+                              &wgrad16z_kernel<2>, &wgrad16z_kernel<0, true>, &wgrad16z_kernel<0, true, true>);
 }
 
 // q.slots: the partial-sum slots the launch filled (the fixed-order reduce of run_wgrad walks them all)
@@ -2528,22 +2514,9 @@ int launch_wgrad16(WgradPlan& q, hipStream_t s) {
     }
     if (nm_ls().wgrad_tr && q.p.in.N <= W16_TAB_FRAMES) {                       // (the per-frame scale / shift table of wgrad16t_kernel lives in LDS: 256 B per frame)
         static NmDeviceOnce attr_t;
-        if (!attr_t.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16t_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16t_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16t_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16t_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16u_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                nm_set_error("wgrad16t: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-            }
-            attr_t.mark();
-        }
+        if (int rc = nm_raise_lds_limit(attr_t, 160 * 1024, "wgrad16t: cannot raise the dynamic LDS limit", &wgrad16t_kernel<0>, &wgrad16t_kernel<1>,
+                &wgrad16t_kernel<2>, &wgrad16t_kernel<0, true>, &wgrad16u_kernel<0>, &wgrad16u_kernel<1>, &wgrad16u_kernel<2>, &wgrad16u_kernel<3>,
+                &wgrad16u_kernel<4>, &wgrad16u_kernel<5>, &wgrad16u_kernel<0, true>)) return rc;
         const size_t ldsb = WT_LDS + (size_t)q.p.in.N * 64 * sizeof(float) + 64;
         const dim3 grid(q.p.S, q.m_tiles * q.p.n_tiles);
         if (nm_ls().wgrad_z && q.p.nbz >= 2) {
@@ -2575,13 +2548,7 @@ int launch_wgrad16(WgradPlan& q, hipStream_t s) {
         return nm_check_hip(hipGetLastError(), "wgrad16t launch");
     }
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            nm_set_error("wgrad16: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-        }
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16: cannot raise the dynamic LDS limit", &wgrad16_kernel<false>, &wgrad16_kernel<true>)) return rc;
     if (nm_conv_single()) hipLaunchKernelGGL(wgrad16_kernel<true>, dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
     else hipLaunchKernelGGL(wgrad16_kernel<false>, dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
     return nm_check_hip(hipGetLastError(), "wgrad16 launch");
@@ -2632,12 +2599,7 @@ template <int MT, bool SINGLE, bool HX, bool HD>
 static int launch_k2f16_t(const WgradParams& p, dim3 grid, hipStream_t s) {
     static NmDeviceOnce attr_set;
     const size_t ldsb = w2_lds_bytes(MT, SINGLE);
-    if (!attr_set.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad16k2_kernel<MT, SINGLE, HX, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            nm_set_error("wgrad16k2: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-        }
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16k2: cannot raise the dynamic LDS limit", &wgrad16k2_kernel<MT, SINGLE, HX, HD>)) return rc;
     hipLaunchKernelGGL((wgrad16k2_kernel<MT, SINGLE, HX, HD>), grid, dim3(256), ldsb, s, p);
     return nm_check_hip(hipGetLastError(), "wgrad16k2 launch");
 }
@@ -2667,17 +2629,8 @@ int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride
         const int bricks = in.N * (dy.D * dy.H * dy.W / 64), S = min(bricks, K1_WGS);
         const size_t ldsb = (size_t)64 * (m_tiles * 32 + 4 + n_tiles * 32 + 4) * sizeof(float);
         static NmDeviceOnce attr_set;
-        if (!attr_set.done()) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k1_kernel<6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                nm_set_error("wgrad_k1: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-            }
-            attr_set.mark();
-        }
+        if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad_k1: cannot raise the dynamic LDS limit", &wgrad_k1_kernel<1>,
+                &wgrad_k1_kernel<2>, &wgrad_k1_kernel<6>, &wgrad_k1_kernel<1, true>, &wgrad_k1_kernel<2, true>, &wgrad_k1_kernel<6, true>)) return rc;
         if (in.h != dy.h) { nm_set_error("wgrad_k1: the two tensors must have the same element type (in %d, dy %d)", in.h, dy.h); return NM_ERR_UNSUPPORTED; }
         if (in.h) {
             if (T <= 4) hipLaunchKernelGGL((wgrad_k1_kernel<1, true>), dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
@@ -2761,12 +2714,7 @@ int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, f
     // occupancy channel: matrix cores over the non-empty bricks (sparse_occ 1, grids that are whole 4x8x8 bricks), else the gather
     if (sparse_occ == 1 && G % 8 == 0) {
         static NmDeviceOnce attr_set;
-        if (!attr_set.done()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k5occ_mfma_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_k5occ_mfma_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(wgrad_k5occ_mfma)");
-            attr_set.mark();
-        }
+        if (int rc = nm_raise_lds_limit(attr_set, 96 * 1024, "hipFuncSetAttribute(wgrad_k5occ_mfma)", &wgrad_k5occ_mfma_kernel<64>, &wgrad_k5occ_mfma_kernel<64, true>)) return rc;
         // eight workgroups per CU when the clip allows: a workgroup's bricks are a serial chain (halo test, dY brick through LDS, 128
         // MFMA steps, no double buffering) - 512 / 1024 / 2048 workgroups: 915 / 794 / 637 us (+ 24 / 46 / 92 us of reduce)
         const int blocks = min(2048, N * chunks);                  // (the partial buffer is sized for N * chunks blocks)

@@ -664,12 +664,7 @@ __global__ void affinity_kernel(const float* __restrict__ params, int N, int K, 
 // runtime that refuses it reports NM_ERR_HIP here, not a failed launch later.
 static int heat_plane_lds_limit(const void* kernel, int which) {
     static NmDeviceOnce attr_set[2];
-    if (attr_set[which].done()) return NM_OK;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 32 * 32 * (int)sizeof(float)) != hipSuccess) {
-        nm_set_error("heatmap: cannot raise the dynamic LDS limit to 128 KB"); return NM_ERR_HIP;
-    }
-    attr_set[which].mark();
-    return NM_OK;
+    return nm_raise_lds_limit(attr_set[which], 32 * 32 * 32 * (int)sizeof(float), "heatmap: cannot raise the dynamic LDS limit to 128 KB", kernel);
 }
 
 int nm_launch_heatmap(const float* head, const float* clip_head, const float* prop, int F, int T, int K, int Kc, int g,

@@ -934,12 +934,7 @@ int nm_launch_clip_loss_bwd(const float* keypoints, const float* affinity, const
     const size_t lds = ((size_t)4 * T * K * 3 + K * 3 + 4 * K * K + (graph_ver != 1 ? (size_t)4 * T * K : 0)) * sizeof(float);
     if (lds > 150 * 1024) { nm_set_error("clip_loss_bwd: T*K too large (%d x %d)", T, K); return NM_ERR_UNSUPPORTED; }
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(clip_loss_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-            nm_set_error("clip_loss_bwd: cannot raise the dynamic LDS limit"); return NM_ERR_HIP;
-        }
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 150 * 1024, "clip_loss_bwd: cannot raise the dynamic LDS limit", clip_loss_bwd_kernel)) return rc;
     hipLaunchKernelGGL(clip_loss_bwd_kernel, dim3(B), dim3(256), lds, s, keypoints, affinity, dloss, B, T, K, N, sep_sigma, use_traj,
                        graph_ver, graph_flags, dkp, affinity ? dinfl : nullptr);
     return nm_check_hip(hipGetLastError(), "clip_loss_bwd launch");

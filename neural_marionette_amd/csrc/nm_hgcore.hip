@@ -350,11 +350,7 @@ int nm_launch_hg_core(const NmHgCoreParams& p, hipStream_t s) {
         nm_set_error("hg_core: %zu bytes of LDS per frame / scratch items %d (expected %d)", lds, p.scratch_items, nm_hg_core_scratch_items(p)); return NM_ERR_UNSUPPORTED;
     }
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hg_core_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(hg_core)");
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(hg_core)", &hg_core_kernel)) return rc;
     static int diag_set[64];                // per device (the symbol is per-device state), stored + 1 so that 0 = never written
     const char* e = getenv("NM355_HG_DIAG");
     const int diag = e ? atoi(e) : 0;

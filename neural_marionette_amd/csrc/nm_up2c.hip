@@ -1578,8 +1578,6 @@ __global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, 
     }
 }
 
-int g_cus = 0;
-
 }  // namespace
 
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad) {
@@ -1613,33 +1611,18 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     if (!nm_up2c_eligible(in.D, in.H, in.W, in.C, Cout, 3, 1, 1) || !packed) { nm_set_error("conv_up2c: shape not eligible"); return NM_ERR_ARG; }
     if ((in.scale == nullptr) != (in.shift == nullptr)) { nm_set_error("conv_up2c: scale/shift must come together"); return NM_ERR_ARG; }
     static NmDeviceOnce attr_set;
-    if (!attr_set.done()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_kernel<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_x16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2y_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_face_r_kernel<2, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_up2c_face_r_kernel<4, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return nm_check_hip(e, "hipFuncSetAttribute(conv_up2c)");
-        attr_set.mark();
-    }
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_up2c)", &conv_up2c_kernel<false>, &conv_up2c_kernel<true>,
+                                    &conv_up2c_kernel<true, 3>, &conv_up2c_kernel<true, 2>, &conv_up2c_kernel<true, 1>, &conv_up2c_kernel<false, 0, true>,
+                                    &conv_up2c_x16_kernel<false>, &conv_up2c_x16_kernel<true>, &conv_up2y_kernel<false>, &conv_up2y_kernel<true>,
+                                    &conv_up2c_face_r_kernel<2, 9>, &conv_up2c_face_r_kernel<4, 6>)) return rc;
     const bool single = nm_conv_single() != 0;
     const bool io16 = in.h || out_h;
     if (io16 && !single) {
         nm_set_error("conv_up2c: 16-bit storage (input %d / output %d) needs conv mode 4", in.h, out_h); return NM_ERR_UNSUPPORTED;
     }
     const int io = (in.h ? 1 : 0) | (out_h ? 2 : 0);
-    if (g_cus == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return nm_check_hip(hipErrorUnknown, "device query");
-        g_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    const int cus = nm_num_cus();
+    if (!cus) return NM_ERR_HIP;
     Up2cParams p;
     p.in = in.p; p.in_scale = in.scale; p.in_shift = in.shift; p.in_slope = in.slope;
     p.N = in.N; p.ID = in.D; p.IH = in.H; p.IW = in.W; p.Cin = in.C;
@@ -1654,21 +1637,21 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     const bool y_main = io == 0 && !single && nm_ls().up2y;
     const int columns = p.N * p.nbz * p.nbx;
     // row tiles of the busiest workgroup: 10 per brick, or 10 + 8 (nby - 1) per column
-    const long long tiles_bricks = (long long)((total + g_cus - 1) / g_cus) * YT, tiles_columns = (long long)((columns + g_cus - 1) / g_cus) * (YT + (YT - 2) * (p.nby - 1));
-    p.march = y_main && p.nby > 1 && (nm_ls().up2y_march >= 2 || (nm_ls().up2y_march == 1 && columns >= g_cus && tiles_columns < tiles_bricks));
+    const long long tiles_bricks = (long long)((total + cus - 1) / cus) * YT, tiles_columns = (long long)((columns + cus - 1) / cus) * (YT + (YT - 2) * (p.nby - 1));
+    p.march = y_main && p.nby > 1 && (nm_ls().up2y_march >= 2 || (nm_ls().up2y_march == 1 && columns >= cus && tiles_columns < tiles_bricks));
     p.ypad = y_main && nm_ls().up2y_ypad != 0;
-    if (io == 3) hipLaunchKernelGGL((conv_up2c_kernel<true, 3>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (io == 2) hipLaunchKernelGGL((conv_up2c_kernel<true, 2>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (io == 1) hipLaunchKernelGGL((conv_up2c_kernel<true, 1>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
+    if (io == 3) hipLaunchKernelGGL((conv_up2c_kernel<true, 3>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (io == 2) hipLaunchKernelGGL((conv_up2c_kernel<true, 2>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (io == 1) hipLaunchKernelGGL((conv_up2c_kernel<true, 1>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
     // (the one-product modes keep the 32x32x16 kernel in fp32 storage too: their bfloat16-storage instantiations are bit-compared with
     //  it, tests/test_storage16_gpu.py; NM355_UP2C_X16=2 forces the 16x16x32 form there as well - A/B)
-    else if (y_main && p.march) hipLaunchKernelGGL(conv_up2y_kernel<true>, dim3((unsigned)min(columns, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (y_main) hipLaunchKernelGGL(conv_up2y_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_x16 >= 2 && single) hipLaunchKernelGGL(conv_up2c_x16_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_x16 && !single) hipLaunchKernelGGL(conv_up2c_x16_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (single) hipLaunchKernelGGL(conv_up2c_kernel<true>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_diag & 64) hipLaunchKernelGGL((conv_up2c_kernel<false, 0, true>), dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
-    else hipLaunchKernelGGL(conv_up2c_kernel<false>, dim3((unsigned)min(total, g_cus)), dim3(512), LDS_BYTES, s, p);
+    else if (y_main && p.march) hipLaunchKernelGGL(conv_up2y_kernel<true>, dim3((unsigned)min(columns, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (y_main) hipLaunchKernelGGL(conv_up2y_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (nm_ls().up2c_x16 >= 2 && single) hipLaunchKernelGGL(conv_up2c_x16_kernel<true>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (nm_ls().up2c_x16 && !single) hipLaunchKernelGGL(conv_up2c_x16_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (single) hipLaunchKernelGGL(conv_up2c_kernel<true>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else if (nm_ls().up2c_diag & 64) hipLaunchKernelGGL((conv_up2c_kernel<false, 0, true>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    else hipLaunchKernelGGL(conv_up2c_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
     int rc = nm_check_hip(hipGetLastError(), "conv_up2c launch");
     if (rc) return rc;
     if (nm_ls().up2c_diag & 4) return NM_OK;

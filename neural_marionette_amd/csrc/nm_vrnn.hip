@@ -2468,10 +2468,7 @@ static bool post_chain_fits(nm_ctx* c, int B, int S, int nstat, int& rc) {
     if (!(nm_ls().vrnn_chain && S >= 1 && S <= 16 && (size_t)S * B <= 96 && B <= 16 && K >= 2 && K <= 32 && Z == 128 && H == 512 && c->nf_flag)) return false;
     if (nm_ls().post_chain_fits < 0) {
         static NmDeviceOnce attr_set;
-        if (!attr_set.done()) {
-            if ((rc = nm_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&vrnn_post_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "hipFuncSetAttribute(vrnn_post_chain)"))) return false;
-            attr_set.mark();
-        }
+        if ((rc = nm_raise_lds_limit(attr_set, 150 * 1024, "hipFuncSetAttribute(vrnn_post_chain)", &vrnn_post_chain_kernel))) return false;
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&vrnn_post_chain_kernel), NM_CHAIN_T, (size_t)(3 + 7 * 32) * 128 * sizeof(float)) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
@@ -2870,11 +2867,7 @@ static int rollout_steps(nm_ctx* c, RolloutBufs& r, int kind, int B, int Tcond, 
         // bounded spins are for: the time-out is reported by the next call and switches the chain off for this context (nm_nf_poll).
         if (nm_ls().chain_fits < 0) {
             static NmDeviceOnce attr_set;
-            if (!attr_set.done()) {
-                if ((rc = nm_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&vrnn_prior_chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024), "hipFuncSetAttribute(vrnn_prior_chain)"))) return rc;
-                if ((rc = nm_check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&vrnn_prior_chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024), "hipFuncSetAttribute(vrnn_prior_chain one-XCD)"))) return rc;
-                attr_set.mark();
-            }
+            if ((rc = nm_raise_lds_limit(attr_set, 140 * 1024, "hipFuncSetAttribute(vrnn_prior_chain)", &vrnn_prior_chain_kernel<false>, &vrnn_prior_chain_kernel<true>))) return rc;
             int per_cu = 0, cus = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&vrnn_prior_chain_kernel<false>), NM_CHAIN_T, (size_t)(3 + 7 * 32) * 128 * sizeof(float)) != hipSuccess ||
                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }

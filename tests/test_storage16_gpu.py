@@ -47,6 +47,8 @@ FWD_CASES = [
     (32, 64, 3, 1, 1, 16, 3, 0, 1, 1, "conv_f16p2 (two channel chunks, several bricks per workgroup)"),
     (32, 32, 3, 1, 1, 32, 2, 0, 1, 1, "conv_f16r (one-product modes, 32 output channels: resident weights)"),
     (64, 32, 3, 1, 1, 16, 5, 0, 1, 1, "conv_f16r (four chunks)"),
+    (16, 32, 3, 1, 1, 16, 20, 0, 1, 1, "conv_f16p (conv_f16r takes Cin 32 / 64 only): 320 bricks, some workgroups walk two"),
+    (48, 32, 3, 1, 1, 16, 2, 0, 1, 1, "conv_f16p, three channel chunks (an odd count)"),
     (32, 64, 1, 1, 0, 32, 2, 0, 1, 1, "conv_f16s k1, two N tiles"),
     (64, 32, 1, 1, 0, 32, 2, 0, 1, 1, "conv_f16s k1, one N tile"),
     (128, 64, 3, 1, 1, 8, 2, 1, 0, 1, "conv_f16s fused upsample, fp32 in / bf16 out"),
@@ -160,9 +162,9 @@ def test_elementwise_storage16(ctx):
 
 BWD_CASES = [
     # Cin, Cout, ks, stride, pad, size, N, up2, dgrad_channels, in16, out16
-    (32, 32, 3, 1, 1, 32, 2, 0, 32, 1, 1),      # wgrad16z, conv_f16p data gradient
+    (32, 32, 3, 1, 1, 32, 2, 0, 32, 1, 1),      # wgrad16z, conv_f16r data gradient
     (64, 64, 3, 1, 1, 16, 3, 0, 64, 1, 1),      # wgrad16z 4 tile pairs, conv_f16p2
-    (32, 64, 3, 1, 1, 16, 2, 0, 32, 1, 1),      # ragged tile pairs, data gradient 64 -> 32 on conv_f16p
+    (32, 64, 3, 1, 1, 16, 2, 0, 32, 1, 1),      # ragged tile pairs, data gradient 64 -> 32 on conv_f16r
     (32, 64, 1, 1, 0, 16, 2, 0, 32, 1, 1),      # k1: wgrad_k1, conv_f16s k1 data gradient
     (32, 32, 2, 2, 0, 32, 2, 0, 32, 1, 1),      # pool: wgrad_kernel<0, 2>, transposed conv on the matrix cores with packed bf16 stores
     (64, 64, 2, 2, 0, 16, 8, 0, 64, 1, 0),      # pool across the storage threshold: bf16 input, fp32 dy

@@ -53,8 +53,6 @@ bash tools/ab_mfma_shape.sh 7 > $E/${R}_mfma_shape_ab.txt 2>&1
 if [ -f neural_marionette_amd/libnm355_x4.so ]; then bash tools/ab_granule_loads.sh 2>&1 | grep -v amdgpu.ids > $E/${R}_granule_loads_ab.txt; fi
 # conv_f16p2's deferred epilogue (built, slower, opt-in) against the shipped exposed one; in-kernel stamps of both (libnm355_stamps.so: make stamps)
 { bash tools/ab_p2_defer.sh; if [ -f neural_marionette_amd/libnm355_stamps.so ]; then for D in 0 1; do echo "in-kernel stamps, NM355_P2_DEFER=$D (tools/diag_f16p2_steps.py):"; NM355_P2_DEFER=$D python3 tools/diag_f16p2_steps.py 2>&1 | grep -v amdgpu.ids | head -5; done; fi; } > $E/${R}_p2_defer_ab.txt 2>&1
-# the measured upper bound of a Winograd F(2,3) form of conv_f16p2 (needs libnm355_diag.so: make -C neural_marionette_amd/csrc diag)
-if [ -f neural_marionette_amd/libnm355_diag.so ]; then python3 tools/diag_winograd_emu.py 2>&1 | grep -v amdgpu.ids > $E/${R}_winograd_emu.txt; fi
 {
   echo "config-5 rollout (tools/time_rollout.py: generate, Tcond = 5 posterior + 64 prior steps), alternating, one call:"
   for i in 1 2; do
@@ -72,7 +70,6 @@ python3 tools/time_encode_ab.py 2>&1 | grep -v amdgpu.ids > $E/${R}_encode_ab.tx
   bash tools/ab_forward_env.sh "NM355_UP2C_X16=0" "NM355_UP2C_X16=1" 3
   bash tools/ab_forward_env.sh "NM355_VRNN_POST_CHAIN=1" "NM355_VRNN_POST_CHAIN=2" 3
   bash tools/ab_forward_env.sh "NM355_UP2C_ALL=0" "NM355_UP2C_ALL=1" 2
-  bash tools/ab_forward_env.sh "NM355_F16P_LATE=0" "NM355_F16P_LATE=1" 3
   bash tools/ab_forward_env.sh "NM355_FAST_DECODE=0" "NM355_FAST_DECODE=1" 3
 } > $E/${R}_forward_ab.txt 2>&1
 {
