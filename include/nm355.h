@@ -218,6 +218,53 @@ typedef struct nm_clip_desc {
 int nm_voxelize_batch(nm_ctx* ctx, const nm_clip_desc* clips_dev, int32_t B, int32_t T, int64_t N, int32_t J, int32_t points_f64,
                       int32_t joints_f64, float* vox, void* joints_out, int32_t* idx_out, double* bbox_out, int32_t* bad_rows);
 
+/* ---- mesh sampling: point sequences from mesh sequences - what the reference's offline preparation computed per frame with
+ * trimesh.sample.sample_surface(mesh, 20000) and mesh.face_normals (dataset/dfaust/write_sequence_to_obj.py:20-23, :107-115,
+ * dataset/aistpp/prepare_aistpp.py:13-16, :75-83) before it wrote the (frames, 20000, 3) arrays the input path reads ----
+ * This is trimesh's algorithm - a face by area, a point in it by two uniforms folded into the triangle - with three changes that make
+ * the result independent of the order a parallel machine sums in; it is NOT trimesh's or numpy's random stream and not its bits.  The
+ * result is defined by this text alone, in float64, unfused, in exactly this operation order (tests/sample_ref.py restates it in numpy).
+ *
+ * vertices (T,V,3) float32 (widened exactly) or float64 on the device, triangles (F,3) int32 or int64 on the device, shared by all T
+ * frames; count samples per frame.  1 <= F <= 2^21, T, V, count >= 1.
+ *   1. face records, per frame and face   a = v1 - v0, b = v2 - v0;  c = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x);
+ *      n2 = (c_x c_x + c_y c_y) + c_z c_z;  r = sqrt(n2);  area = 0.5 * r;  normal = float(c / r) per component, (0, 0, 0) where n2 is 0 or
+ *      not finite.  A face with a vertex index outside [0, V) reads nothing and has area 0 and normal 0 in every frame; `bad_faces`
+ *      counts such rows of `triangles` (once a row, not once a frame).
+ *   2. integer weights   amax = the frame's largest finite area, e = the exponent frexp(amax) returns (amax = m 2^e, 0.5 <= m < 1; 0 for
+ *      amax = 0);  w_i = (uint64) floor(ldexp(area_i, 32 - e)) < 2^32, 0 for an area that is not finite;  Cum = the inclusive prefix sum
+ *      of w over the frame's faces, W = Cum[F - 1] < 2^53.  Integer sums do not depend on their order: any scan gives this table.  A face
+ *      whose area is below amax 2^-32 has weight 0.  A frame with W = 0 has no surface: all its points are v0 of face 0 ((0, 0, 0) if that
+ *      index lies outside [0, V)), its normals 0, its face indices 0, and `empty_frames` counts it.
+ *   3. picks   sample s of frame t has uniforms (u0, u1, u2) in [0, 1):  p = min((uint64) floor(u0 * (double) W), W - 1) (a u0 that is
+ *      negative or NaN gives p = 0);  face = the smallest i with Cum[i] > p - a face of weight 0 is never picked;  if u1 + u2 > 1.0
+ *      (strictly), u1 = fabs(u1 - 1.0) and u2 = fabs(u2 - 1.0);  point = v0 + (a * u1 + b * u2) per component with the face's a, b of 1.
+ *      points (T,count,3) float32 = float(point), normals (T,count,3) float32 = the face's normal, face_index (T,count) int32.
+ *   4. uniforms   u (T,count,3) float64 on the device, or with u NULL Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments
+ *      9E3779B9 / BB67AE85) under key (seed & 0xffffffff, seed >> 32) at counter (s & 0xffffffff, s >> 32, t, call): call 0's words
+ *      (x0, x1, x2, x3) give u0 from (x0, x1) and u1 from (x2, x3), call 1's give u2 from (x0, x1); a pair (hi, lo) becomes
+ *      ((hi >> 5) * 67108864.0 + (lo >> 6)) * 2^-53.  Known answers (counter / key -> words): 0 0 0 0 / 0 0 -> 6627e8d5 e169c58d bc57ac4c
+ *      9b00dbd8; all ffffffff -> 408f276d 41c83b0e a20bc7c6 6d5451fd; 243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 ->
+ *      d16cfe09 94fdcceb 5001e420 24126ea1.  uniforms_out (T,count,3) float64, if given, receives what was used.
+ * nm_sample_surface_workspace - bytes of `scratch` for T frames of F faces (0 for a shape nm_sample_surface refuses): areas, Cum,
+ *   face normals, the coarse table (every 64th entry of Cum), chunk sums, the frames' maxima.
+ * nm_sample_surface - three passes on the context's stream: face records and the frame maximum (a wave reduction, then an atomic
+ *   maximum of the bit pattern of a non-negative double - exact and order-free); weights and their scan (one workgroup per frame up to
+ *   16384 faces; above that per 4096-face chunk: chunk sums, their scan, the chunks); the draw (a lane per sample; the frame's coarse
+ *   table staged in LDS up to 2048 entries = 131072 faces and searched in global memory above, then the 64-entry segment of Cum).
+ *   counters (2) int32 on the device: bad_faces, empty_frames, written by every call.  scratch must be 256-byte aligned.
+ * nm_sample_tables - copies areas (T,F) float64 and / or cum (T,F) int64 out of the scratch of a nm_sample_surface call with the same
+ *   T and F (either may be NULL).
+ * All stream-ordered; nothing synchronises and nothing is allocated.  The only atomics are the integer maximum and the two counters:
+ * results are bit-identical from run to run.  Arguments are judged before any launch.  NM_ERR_ARG: null ctx / vertices / triangles /
+ * scratch / points / normals / face_index / counters, T, V, F, count < 1, F > 2^21, scratch_bytes below the workspace query, a scratch
+ * that is not 256-byte aligned; NM_ERR_UNSUPPORTED: count >= 2^31 - 1024, T * ceil(count / 1024) or T * ceil(F / 256) >= 2^31. */
+size_t nm_sample_surface_workspace(int32_t T, int32_t F);
+int nm_sample_surface(nm_ctx* ctx, const void* vertices, int32_t vertices_f64, const void* triangles, int32_t triangles_i64, int32_t T,
+                      int32_t V, int32_t F, int64_t count, uint64_t seed, const double* u, void* scratch, size_t scratch_bytes,
+                      float* points, float* normals, int32_t* face_index, double* uniforms_out, int32_t* counters);
+int nm_sample_tables(nm_ctx* ctx, const void* scratch, int32_t T, int32_t F, double* areas, int64_t* cum);
+
 /* Device output path: thresholded voxels to ordered point sets - the host lines every consumer of the decoder's voxels starts with
  * (vis_generation.py:137-170, vis_interpolation.py:141-177, vis/visualize.py:58-59, :130-137): binarise, np.where / torch.where per
  * frame, divide into [-1, 1] coordinates, min_z / max_z of the last coordinate over a clip and the per-point (z - min_z) / z_len.

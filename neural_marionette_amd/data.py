@@ -4,7 +4,8 @@ The reference's dataset classes (dataset/dataset.py) load a sequence, pick a cro
 item.  Here the sequences stay on the device (ClipBank), the host only picks the crops (ClipSampler: the start-index rules of
 dataset.py:51-68, on the reference's own random stream) and one library call builds the (B,T,1,G,G,G) batch
 (NeuralMarionette.voxelize_batch -> nm_voxelize_batch).  DeviceClipLoader ties the three together for the trainers.
-File I/O is the caller's: ``bank.add(np.load(path)[..., :3])``.
+File I/O is the caller's: ``bank.add(np.load(path)[..., :3])`` for a prepared point sequence, or ``bank.add_mesh(net, vertices,
+triangles)`` for a mesh sequence, which is sampled on the device (NeuralMarionette.sample_surface -> nm_sample_surface).
 """
 from __future__ import annotations
 
@@ -47,6 +48,12 @@ class ClipBank:
         self.points.append(p.to(self.device).contiguous())
         self.joints.append(j)
         return len(self.points) - 1
+
+    def add_mesh(self, net, vertices, triangles, count: int = 20000, seed: int = 0, joints=None) -> int:
+        """Samples ``count`` surface points per frame of the mesh sequence ``vertices`` (frames,V,3) / ``triangles`` (F,3) on the
+        device (NeuralMarionette.sample_surface) and stores the float32 points - what the reference's prepared ``.npy[..., :3]``
+        holds - as a new sequence; returns its id."""
+        return self.add(net.sample_surface(vertices, triangles, count=count, seed=seed)["points"], joints)
 
     def __len__(self) -> int:
         return len(self.points)

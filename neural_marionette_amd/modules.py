@@ -819,6 +819,75 @@ class NeuralMarionette(nn.Module):
                                    return_joints=return_joints, return_indices=return_indices, check=check, pad=pad)
 
     @torch.no_grad()
+    def sample_surface(self, vertices, triangles, count: int = 20000, seed: int = 0, u=None, check: bool = False, return_tables: bool = False):
+        """Device version of the reference's offline preparation (dataset/dfaust/write_sequence_to_obj.py:20-23, :107-115,
+        dataset/aistpp/prepare_aistpp.py:13-16, :75-83: trimesh.sample.sample_surface(mesh, 20000) and mesh.face_normals per frame):
+        ``count`` points on the surface of every frame of a mesh sequence, a face picked in proportion to its area and a point
+        uniformly inside it, in one stream-ordered call (nm_sample_surface, csrc/nm_sample.hip).  **Not trimesh's random stream and
+        not its bits**: the result is defined by the contract of include/nm355.h alone (tests/sample_ref.py restates it).  It is
+        trimesh's algorithm with integer face weights - the areas scaled by the power of two above the frame's largest and floored, so
+        the cumulative table does not depend on the order of a parallel sum - and uniforms from Philox4x32-10 keyed by ``seed`` and
+        counted by (sample, frame).  A face below 2^-32 of the frame's largest area is never picked.
+        vertices: (T,V,3) float32 or float64, triangles: (F,3) int32 or int64 shared by all frames, F <= 2^21, both contiguous on the
+        network's device.  u: (T,count,3) float64 uniforms in [0, 1) of the caller's instead of the generator's (face, then the two
+        barycentric draws).
+        Returns a dict: points (T,count,3) float32 - what ClipBank.add takes; normals (T,count,3) float32, the picked faces' unit
+        normals (zero for a degenerate face); face_index (T,count) int32; bad_faces, empty_frames: 0-d int32 device tensors - rows of
+        ``triangles`` with an index outside the vertices (they have no area and are never read through), and frames whose faces all
+        have weight 0 (their points are vertex 0 of face 0, their normals zero).  check=True reads the two (the call's one
+        synchronisation) and raises ValueError if either is not 0.  return_tables=True adds areas (T,F) float64, cum (T,F) int64 -
+        the inclusive sums of the integer weights - and uniforms (T,count,3) float64 as used."""
+        who = "sample_surface"
+        for name, t in (("vertices", vertices), ("triangles", triangles)) + ((("u", u),) if u is not None else ()):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if vertices.dtype not in (torch.float32, torch.float64) or vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[0] < 1 or vertices.shape[1] < 1:
+            raise ValueError(f"{who}: vertices must be (T,V,3) float32 or float64 with T, V >= 1, got {tuple(vertices.shape)} {vertices.dtype}")
+        if triangles.dtype not in (torch.int32, torch.int64) or triangles.dim() != 2 or triangles.shape[1] != 3:
+            raise ValueError(f"{who}: triangles must be (F,3) int32 or int64, got {tuple(triangles.shape)} {triangles.dtype}")
+        T, V, F = int(vertices.shape[0]), int(vertices.shape[1]), int(triangles.shape[0])
+        if not 1 <= F <= 2 ** 21:
+            raise ValueError(f"{who}: {F} faces, a call takes 1 .. 2^21 (a frame's integer weights sum below 2^53)")
+        if isinstance(count, bool) or not isinstance(count, int) or count < 1:
+            raise ValueError(f"{who}: count must be an integer >= 1, got {count!r}")
+        if count >= 2 ** 31 - 1024 or T * ((count + 1023) // 1024) >= 2 ** 31 or T >= 2 ** 31 or V >= 2 ** 31:
+            raise ValueError(f"{who}: {T} frames of {count} samples, one call launches fewer than 2^31 workgroups")
+        if u is not None and (u.dtype != torch.float64 or tuple(u.shape) != (T, count, 3)):
+            raise ValueError(f"{who}: u must be ({T},{count},3) float64, got {tuple(u.shape)} {u.dtype}")
+        tensors = [("vertices", vertices), ("triangles", triangles)] + ([("u", u)] if u is not None else [])
+        for name, t in tensors:
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous on the network's device, got {t.device}")
+        eng = self._engine
+        dev = eng._device()
+        for name, t in tensors:
+            if t.device != dev:
+                raise ValueError(f"{who}: {name} must be on the network's device ({dev}), got {t.device}")
+        ctx = eng.ready()
+        nbytes = int(ctx.lib.nm_sample_surface_workspace(T, F))
+        if nbytes == 0:
+            raise _lib.NmError(f"{who}: no workspace size for {T} frames of {F} faces")
+        scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        out = dict(points=torch.empty(T, count, 3, device=dev), normals=torch.empty(T, count, 3, device=dev),
+                   face_index=torch.empty(T, count, device=dev, dtype=torch.int32))
+        counters = torch.empty(2, device=dev, dtype=torch.int32)
+        used = torch.empty(T, count, 3, device=dev, dtype=torch.float64) if return_tables and u is None else None
+        eng.call("nm_sample_surface", vertices.data_ptr(), int(vertices.dtype == torch.float64), triangles.data_ptr(),
+                 int(triangles.dtype == torch.int64), T, V, F, count, int(seed) & (2 ** 64 - 1), _lib.ptr(u), scratch.data_ptr(), nbytes,
+                 _lib.ptr(out["points"]), _lib.ptr(out["normals"]), _lib.ptr(out["face_index"]), _lib.ptr(used), _lib.ptr(counters))
+        out["bad_faces"], out["empty_frames"] = counters[0], counters[1]
+        if return_tables:
+            out["areas"] = torch.empty(T, F, device=dev, dtype=torch.float64)
+            out["cum"] = torch.empty(T, F, device=dev, dtype=torch.int64)
+            eng.call("nm_sample_tables", scratch.data_ptr(), T, F, _lib.ptr(out["areas"]), out["cum"].data_ptr())
+            out["uniforms"] = used if u is None else u
+        if check:
+            bad, empty = (int(x) for x in counters.tolist())          # (the one synchronisation)
+            if bad or empty:
+                raise ValueError(f"{who}: {bad} faces with a vertex index outside [0, {V}), {empty} frames without surface")
+        return out
+
+    @torch.no_grad()
     def occupied_points(self, vox, threshold=0.5, dtype=torch.float64, capacity=None, return_indices: bool = False,
                         return_depth: bool = False, return_bits: bool = False):
         """Device version of the host lines every consumer of the decoder's voxels starts with (vis_generation.py:137-170,
