@@ -34,10 +34,8 @@ NmLaunchState::NmLaunchState()
       defer_sums(env_int("NM355_DEFER_SUMS", 1)),      // 0: the per-layer gamma / beta / bias gradient sums are launched inside each GroupNorm backward (A/B)
       wgrad_async(env_int("NM355_WGRAD_ASYNC", 1)),    // 0: the weight gradients of the training backward stay in the main stream's chain (A/B)
       wgrad_wgs(env_int("NM355_WGRAD_WGS", 0)),       // workgroups of a split-fp16 weight-gradient launch (0: 224 beside the main stream's walk, else 256; plan_wgrad)
-      wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: wgrad16_kernel (VALU transposition) instead of wgrad16t_kernel
-      wgrad_u(env_int("NM355_WGRAD_U", 1)),         // 0: wgrad16t_kernel (conditional staging loads) instead of wgrad16u_kernel
+      wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: every split-fp16 k3 weight gradient on wgrad16_kernel (VALU transposition) instead of wgrad16z_kernel: the one A/B of the family (w16z_takes)
       tail_rank1(env_int("NM355_TAIL_RANK1", 1)),   // 0: the decoder tail's backward materialises its [F][G^3][32] gradient (A/B)
-      wgrad_z(env_int("NM355_WGRAD_Z", 1)),         // 0: bricks in any order with their full halo (wgrad16u_kernel) instead of z-columns with a plane ring
       up2c(env_int("NM355_UP2C", 1)),               // 0: fused-upsample layers stay on conv_f16s (diagnostic / A-B)
       up2c_diag(env_int("NM355_UP2C_DIAG", 0)),
       vrnn_mid(env_int("NM355_VRNN_MID", 1)),          // 0: prior steps as six launches instead of three (A/B)

@@ -48,7 +48,6 @@ struct WgradParams {
     int M, Nc;               // dy channels / input channels that take part
     int BZ, BY, BX, nbz, nby, nbx, HZ, HY, HX;
     int S, n_tiles, groups;  // split count, column tiles, tap groups per tile
-    int dbg;                 // diagnostics (NM355_W16_DBG): 1 no MFMA phase, 2 no global loads, 3 no loads / LDS stores, 4 LDS stores only
 };
 
 // MODE 0: taps dealt to the waves (NTW per wave);  MODE 1: ks = 1, the waves split the voxels;
@@ -453,15 +452,12 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(WgradParams p) {
     const char* bh_base = A_hi + l31 * W16_PA; const char* bl_base = A_lo + l31 * W16_PA;
     for (; b < total; b += p.S) {
         __syncthreads();
-        if (!(p.dbg == 3 && b != (int)blockIdx.x)) {
-            w16_store<10>(ta, va, A_hi, A_lo, W16_PA, qa, rowa * 32);
-            if (w == 0) w16_store<10>(tb, vb, A_hi, A_lo, W16_PA, qa, rowb * 32);
-            else if (w < 3) w16_store<8>(tb, vb, D_hi, D_lo, W16_PD, qa, rowb * 16);
-        }
+        w16_store<10>(ta, va, A_hi, A_lo, W16_PA, qa, rowa * 32);
+        if (w == 0) w16_store<10>(tb, vb, A_hi, A_lo, W16_PA, qa, rowb * 32);
+        else if (w < 3) w16_store<8>(tb, vb, D_hi, D_lo, W16_PD, qa, rowb * 16);
         __syncthreads();
         const bool has_next = b + p.S < total;
-        if (has_next && p.dbg < 2) { setup(b + p.S); w16_fetch(ta, va); if (w < 3) w16_fetch(tb, vb); }
-        if (p.dbg == 1 || p.dbg == 4) continue;
+        if (has_next) { setup(b + p.S); w16_fetch(ta, va); if (w < 3) w16_fetch(tb, vb); }
         // k-steps of 16 voxels (two brick rows).  LDS reads run one row group ahead of the MFMAs that consume them: group 1 is
         // requested before the 9 MFMAs of group 0, group 2 / the next step's dY operand / the next step's group 0 before those of
         // group 1 (a wave is alone on its SIMD: nothing else covers the LDS latency).
@@ -691,552 +687,21 @@ __global__ __launch_bounds__(256) void wgrad16k2_kernel(WgradParams p) {
         }
 }
 
-// ---- wgrad16t: the same weight gradient through transposing LDS reads (gfx950 ds_read_b64_tr_b16) -------------------------------
+// ---- wgrad16z: the same weight gradient through transposing LDS reads (gfx950 ds_read_b64_tr_b16), walking its bricks along z ----
 // wgrad16_kernel spends ~35-45 % of its time turning the channels-last tiles into [channel][voxel] planes with VALU before the first
 // MFMA, because v_mfma_f32_32x32x16_f16 wants 8 consecutive K (= voxels) of one channel per lane.  ds_read_b64_tr_b16 delivers a
 // 4 (rows = voxels) x 16 (columns = channels) block of 16-bit elements column-major: lane i of a 16-lane group receives column i of
 // the 4 rows.  So LDS keeps the natural channels-last fp16 tiles - [voxel][32 channels], 64 B per voxel, filled by plain 16-byte
-// stores - and an operand is two transposed reads (x = 0..3, 4..7 of a brick row).  A tap is just a row offset into the halo tile
-// (no register shifting for dx), the four reads of a 32-lane half cover 256 contiguous bytes (conflict-free), the staging is the
-// forward convs' activate + split, and a buffer is 66 KB: two of them, so the next brick is loaded (registers) and written (other
-// buffer) while the MFMAs of the current one run.  512 threads: the 27 taps are dealt to 8 waves (4, 4, 4, 3, 3, 3, 3, 3 - two
-// waves per SIMD), each holding its taps' accumulator pairs; per k-step of 16 voxels a wave reads the dY operand (4 transposed
-// reads) and its taps' X operands (4 each) and issues 3 MFMAs per tap.  Partials and the reduce are wgrad16_kernel's.
-#define WT_HV 400
-#define WT_BV 128
-#define WT_XB (WT_HV * 64)
-#define WT_DB (WT_BV * 64)
-#define WT_BUF (2 * WT_XB + 2 * WT_DB)
-#define WT_LDS (2 * WT_BUF)
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short short4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x2 tr_read(const char* lds_ptr) {
-    // (take the 64-bit result as a whole: element-wise extraction of the builtin's vector is miscompiled by this hipcc)
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)lds_ptr));
-}
-__device__ __forceinline__ half8 tr_operand(const char* p) {
-    const u32x2 a = tr_read(p), b = tr_read(p + 4 * 64);
-    return __builtin_bit_cast(half8, u32x4{a[0], a[1], b[0], b[1]});
-}
-
-template <int DBG, bool SINGLE = false>      // DBG 0: product; 1: no MFMA loop, 2: no staging after the first brick (timing experiments, NM355_W16_DBG)
-__global__ __launch_bounds__(512, 1) void wgrad16t_kernel(WgradParams p) {
-    extern __shared__ char lds8[];
-    // per-frame GroupNorm scale / shift of this column tile's 32 input channels: [N][2][32] floats behind the two tile buffers, loaded
-    // once (a commit inside the k-loop must not wait for global memory)
-    float* xtab = reinterpret_cast<float*>(lds8 + WT_LDS);
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tp = blockIdx.y, mt = tp / p.n_tiles, nt = tp % p.n_tiles, m0 = mt * 32, n0 = nt * 32;
-    // taps: wave w owns the tap line (dz, dy) = (w / 3, w % 3) - taps 3 w + dx, whose three X operands come out of ONE halo row read
-    // (10 voxels, shifted in registers) - and waves 0..2 also tap 24 + w of the ninth line
-    const int ntaps = w < 3 ? 4 : 3;
-    f32x16 acc[4], accl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; accl[j][r] = 0.f; }
-    // transposed-read addresses: lane 4q + pp of a 16-lane group supplies row q, columns 4pp .. 4pp + 3 of the group's block;
-    // group = (column block cb = (lane >> 4) & 1, lane half lh)
-    const int i16 = lane & 15, q = i16 >> 2, pp = i16 & 3, cb = (lane >> 4) & 1;
-    const int a_lane = ((lh * 8 + q) * 32 + 16 * cb + 4 * pp) * 2;          // dY tile: brick row 2s + lh, voxel x0 + q
-    const int b_lane = ((lh * 10 + q) * 32 + 16 * cb + 4 * pp) * 2;         // X tile: halo row (z + tz, 2(s & 3) + lh + ty), voxel x0 + q + tx
-    const int lineoff = (((w / 3) * 10 + w % 3) * 10) * 64;                 // halo row (dz, dy) of the wave's line, x = -1
-    const int extraoff = ((2 * 10 + 2) * 10 + min(w, 2)) * 64;              // tap 24 + w = (2, 2, w)
-
-    const int per_frame = p.nbz * p.nby * p.nbx, total = p.in.N * per_frame;
-    // staging roles: three (four for 64 threads) X items (halo voxel, channel octet) and one dY item per thread; octet = tid & 3
-    const int oct = tid & 3;
-    for (int i = tid; i < p.in.N * 64; i += 512) {        // (identity when the input carries no pending GroupNorm: the commit is branch-free)
-        const int n = i >> 6, which = (i >> 5) & 1, c = n0 + (i & 31);
-        xtab[i] = p.in.scale ? (c < p.Nc ? (which ? p.in.shift : p.in.scale)[(size_t)n * p.in.C + c] : 0.f) : (which ? 0.f : 1.f);
-    }
-    // (the table is read by other threads than those that wrote it, first in the prologue below: without this barrier a wave that ran
-    //  ahead converted its first items with whatever the previous workgroup left in LDS - a run-to-run difference of ~1e-4 in the
-    //  weight gradient of one layer, one run in ~80 when the kernel ran alone and one in ~5 beside the main stream's kernels; round 4)
-    __syncthreads();
-    char* dummy = lds8 + WT_LDS + (size_t)p.in.N * 256;   // 32 B written by the threads without a fourth X item
-    f32x4 xa[4], xb[4], da, db, dsa, dsb, dha, dhb;
-    dsa = dsb = f32x4{1.f, 1.f, 1.f, 1.f}; dha = dhb = f32x4{0.f, 0.f, 0.f, 0.f};
-    int xn = 0, xoz = 0, xoy = 0, xox = 0;                // brick being fetched
-    // the next brick arrives in two instalments (registers): dY item + X items 0, 1 at the start of a brick, X items 2, 3 mid-brick
-    auto locate = [&](int b) __attribute__((always_inline)) {
-        xn = b / per_frame; int r = b % per_frame;
-        const int bx = r % p.nbx; r /= p.nbx;
-        xoz = (r / p.nby) * 2; xoy = (r % p.nby) * 8; xox = bx * 8;
-    };
-    // per X item: the thread's halo voxel as packed (hx, hy, hz) and as an element offset from the brick's first halo voxel; the
-    // brick part of every address is wave-uniform (scalar registers)
-    int hpack[4], hoffs[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int hv = min((tid >> 2) + 128 * k, WT_HV - 1), hx = hv % 10, hy = (hv / 10) % 10, hz = hv / 100;
-        hpack[k] = hx | (hy << 8) | (hz << 16);
-        hoffs[k] = ((hz * p.in.H + hy) * p.in.W + hx) * p.in.C + n0 + 8 * oct;
-    }
-    unsigned inmask = 0;                                  // bit k: X item k of the brick being fetched lies inside the tensor
-    auto fetch = [&](int k0, int k1, bool with_dy) __attribute__((always_inline)) {
-        const int c = n0 + 8 * oct;
-        const long long base = ((((long long)xn * p.in.D + (xoz - 1)) * p.in.H + (xoy - 1)) * p.in.W + (xox - 1)) * (long long)p.in.C;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < k0 || k >= k1) continue;
-            xa[k] = xb[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int gx = xox - 1 + (hpack[k] & 255), gy = xoy - 1 + ((hpack[k] >> 8) & 255), gz = xoz - 1 + (hpack[k] >> 16);
-            const bool in = (unsigned)gz < (unsigned)p.in.D && (unsigned)gy < (unsigned)p.in.H && (unsigned)gx < (unsigned)p.in.W &&
-                            (tid >> 2) + 128 * k < WT_HV;
-            inmask = (inmask & ~(1u << k)) | ((in ? 1u : 0u) << k);
-            if (in) {
-                const float* src = p.in.p + base + hoffs[k];
-                if (c < p.Nc) xa[k] = *reinterpret_cast<const f32x4*>(src);
-                if (c + 4 < p.Nc) xb[k] = *reinterpret_cast<const f32x4*>(src + 4);
-            }
-        }
-        if (with_dy) {
-            const int bv = tid >> 2, z = bv >> 6, y = (bv >> 3) & 7, x = bv & 7, m = m0 + 8 * oct;
-            const float* src = p.dy.p + ((((size_t)xn * p.dy.D + xoz + z) * p.dy.H + xoy + y) * p.dy.W + xox + x) * p.dy.C + m;
-            da = db = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (m < p.M) da = *reinterpret_cast<const f32x4*>(src);
-            if (m + 4 < p.M) db = *reinterpret_cast<const f32x4*>(src + 4);
-            if (p.dy.scale) {                             // (else they stay 1 / 0)
-                const float* ps = p.dy.scale + (size_t)xn * p.dy.C + m; const float* ph = p.dy.shift + (size_t)xn * p.dy.C + m;
-                if (m < p.M) { dsa = *reinterpret_cast<const f32x4*>(ps); dha = *reinterpret_cast<const f32x4*>(ph); }
-                if (m + 4 < p.M) { dsb = *reinterpret_cast<const f32x4*>(ps + 4); dhb = *reinterpret_cast<const f32x4*>(ph + 4); }
-            }
-        }
-    };
-    // (no branches from here to the store: the conversion of an item has to sit in the same basic block as the k-step's MFMAs for
-    //  the scheduler to interleave the two; slope 1 makes the leaky ReLU an identity, the tables hold 1 / 0 without a GroupNorm)
-    auto act_x = [&](int n, f32x4& a, f32x4& b) __attribute__((always_inline)) {
-        const float* t = xtab + n * 64 + 8 * oct;
-        const f32x4 sa = *reinterpret_cast<const f32x4*>(t), sb = *reinterpret_cast<const f32x4*>(t + 4);
-        const f32x4 ha = *reinterpret_cast<const f32x4*>(t + 32), hb = *reinterpret_cast<const f32x4*>(t + 36);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = fmaf(a[j], sa[j], ha[j]); b[j] = fmaf(b[j], sb[j], hb[j]);
-            a[j] = fmaxf(a[j], a[j] * p.in.slope); b[j] = fmaxf(b[j], b[j] * p.in.slope);
-        }
-    };
-    auto act_d = [&](f32x4& a, f32x4& b) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = fmaf(a[j], dsa[j], dha[j]); b[j] = fmaf(b[j], dsb[j], dhb[j]);
-            a[j] = fmaxf(a[j], a[j] * p.dy.slope); b[j] = fmaxf(b[j], b[j] * p.dy.slope);
-        }
-    };
-    auto split_store = [&](const f32x4& a, const f32x4& b, char* hi, char* lo) __attribute__((always_inline)) {
-        unsigned h[4], l[4];
-        h[0] = pack_split(a[0], a[1], l[0]); h[1] = pack_split(a[2], a[3], l[1]);
-        h[2] = pack_split(b[0], b[1], l[2]); h[3] = pack_split(b[2], b[3], l[3]);
-        *reinterpret_cast<u32x4*>(hi) = u32x4{h[0], h[1], h[2], h[3]};
-        if constexpr (!SINGLE) *reinterpret_cast<u32x4*>(lo) = u32x4{l[0], l[1], l[2], l[3]};      // (conv mode 3 never reads the lo tiles)
-    };
-    // slot 0..3: X items, slot 4: the dY item.  Unconditional: without a next brick the stale registers go to the idle buffer.
-    const float xa_on = n0 + 8 * oct < p.Nc ? 1.f : 0.f, xb_on = n0 + 8 * oct + 4 < p.Nc ? 1.f : 0.f;
-    const float da_on = m0 + 8 * oct < p.M ? 1.f : 0.f, db_on = m0 + 8 * oct + 4 < p.M ? 1.f : 0.f;
-    auto commit = [&](char* buf, int slot) __attribute__((always_inline)) {
-        if (slot < 4) {
-            const int hv = (tid >> 2) + 128 * slot;
-            f32x4 a = xa[slot], b = xb[slot];
-            act_x(xn, a, b);
-            // zero padding, not act(0); as a multiplication (the item's registers are zero, act(0) is finite): a select would be
-            // turned into a branch around the conversion
-            const float in = (float)((inmask >> slot) & 1), ka = in * xa_on, kb = in * xb_on;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a[j] *= ka; b[j] *= kb; }
-            char* hi = buf + hv * 64 + oct * 16; char* lo = hi + WT_XB;
-            if (slot == 3) { const bool item = hv < WT_HV; hi = item ? hi : dummy; lo = item ? lo : dummy + 16; }
-            split_store(a, b, hi, lo);
-        } else {
-            const int bv = tid >> 2;
-            f32x4 a = da, b = db;
-            act_d(a, b);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a[j] *= da_on; b[j] *= db_on; }
-            split_store(a, b, buf + 2 * WT_XB + bv * 64 + oct * 16, buf + 2 * WT_XB + WT_DB + bv * 64 + oct * 16);
-        }
-    };
-
-    int b = blockIdx.x, cur = 0;
-    if (b < total) {
-        locate(b); fetch(0, 4, true);
-#pragma unroll
-        for (int sl = 0; sl < 5; ++sl) commit(lds8, sl);
-    }
-    __syncthreads();
-    for (; b < total; b += p.S) {
-        const bool has_next = b + p.S < total && DBG != 2;
-        const char* buf = lds8 + cur * WT_BUF;
-        char* nbuf = lds8 + (cur ^ 1) * WT_BUF;
-        // the next brick comes through registers one item at a time (dY item, then the four X items), each written to the other
-        // buffer two or three k-steps (5000+ cycles) after its loads were issued: at most two items are live at once - with all
-        // five in flight the kernel spills, and a scratch reload queues behind the outstanding global loads (vmcnt is in order)
-        if (has_next) { locate(b + p.S); fetch(0, 1, true); }
-#pragma unroll
-        for (int s8 = 0; s8 < 8; ++s8) {
-            if (has_next) {
-                if (s8 == 2) fetch(1, 2, false);
-                if (s8 == 3) fetch(2, 3, false);
-                if (s8 == 4) fetch(3, 4, false);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // the item conversion (branch-free) ahead of the k-step's operand reads
-            constexpr int slot_of[8] = {-1, -1, 4, 0, 1, -1, 2, 3};
-            if (DBG != 2 && slot_of[s8] >= 0) commit(nbuf, slot_of[s8]);
-            if (DBG == 1) continue;
-            const char* ap = buf + 2 * WT_XB + a_lane + s8 * 1024;
-            const half8 ah = tr_operand(ap), al = tr_operand(ap + WT_DB);
-            const char* xp = buf + b_lane + (((s8 >> 2) * 10 + 2 * (s8 & 3)) * 10) * 64;
-            {
-                // halo row of the line: voxels x = -1 .. 10 as three transposed reads (x = 9, 10 of the third are never used), hi and lo;
-                // dx = 0 is registers 0..3, dx = 2 registers 1..4, dx = 1 four v_alignbit - 6 LDS reads for three taps instead of 12
-                const char* lp = xp + lineoff;
-                const u32x2 h0 = tr_read(lp), h1 = tr_read(lp + 4 * 64), h2 = tr_read(lp + 8 * 64);
-                const u32x2 l0 = tr_read(lp + WT_XB), l1 = tr_read(lp + WT_XB + 4 * 64), l2 = tr_read(lp + WT_XB + 8 * 64);
-                half8 bh[3], bl[3];
-                bh[0] = __builtin_bit_cast(half8, u32x4{h0[0], h0[1], h1[0], h1[1]});
-                bh[2] = __builtin_bit_cast(half8, u32x4{h0[1], h1[0], h1[1], h2[0]});
-                bh[1] = __builtin_bit_cast(half8, u32x4{__builtin_amdgcn_alignbit(h0[1], h0[0], 16), __builtin_amdgcn_alignbit(h1[0], h0[1], 16),
-                                                        __builtin_amdgcn_alignbit(h1[1], h1[0], 16), __builtin_amdgcn_alignbit(h2[0], h1[1], 16)});
-                bl[0] = __builtin_bit_cast(half8, u32x4{l0[0], l0[1], l1[0], l1[1]});
-                bl[2] = __builtin_bit_cast(half8, u32x4{l0[1], l1[0], l1[1], l2[0]});
-                bl[1] = __builtin_bit_cast(half8, u32x4{__builtin_amdgcn_alignbit(l0[1], l0[0], 16), __builtin_amdgcn_alignbit(l1[0], l0[1], 16),
-                                                        __builtin_amdgcn_alignbit(l1[1], l1[0], 16), __builtin_amdgcn_alignbit(l2[0], l1[1], 16)});
-#pragma unroll
-                for (int u = 0; u < 3; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[u], acc[u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 3; ++u) accl[u] = nm_mfma_lo<SINGLE>(ah, bl[u], accl[u]);
-#pragma unroll
-                for (int u = 0; u < 3; ++u) accl[u] = nm_mfma_lo<SINGLE>(al, bh[u], accl[u]);
-            }
-            if (ntaps == 4) {                             // waves 0..2
-                const half8 bh = tr_operand(xp + extraoff), bl = tr_operand(xp + WT_XB + extraoff);
-                acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[3], 0, 0, 0);
-                accl[3] = nm_mfma_lo<SINGLE>(ah, bl, accl[3]);
-                accl[3] = nm_mfma_lo<SINGLE>(al, bh, accl[3]);
-            }
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (j >= ntaps) continue;
-        const int t = j < 3 ? 3 * w + j : 24 + w;
-        float* dst = p.part + (((size_t)blockIdx.x * gridDim.y + tp) * 27 + t) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[((r >> 2) * 8 + lh * 4 + (r & 3)) * 32 + l31] = acc[j][r] + accl[j][r] * (1.0f / W16_SPLIT);
-    }
-}
-
-// ---- wgrad16u: wgrad16t_kernel with a statically countable memory pipeline (round 3) -------------------------------------------
-// What held wgrad16t_kernel at 2.5-3x its MFMA time (6.8-8.2 us per 128-voxel brick against 2.7 us of matrix work) shows in its
-// ISA: (1) every staging load sat under a condition (halo voxel inside the volume, channel tail, "is there a next brick"), so the
-// compiler could not count the loads in flight and drained them - s_waitcnt vmcnt(0) - in front of every item's conversion,
-// i.e. right behind the loads it had just issued for the NEXT item: five exposed memory round trips per brick; (2) a k-step's
-// transposing LDS reads were issued in front of the MFMAs that consume them (their latency exposed once per k-step and wave),
-// and the fourth tap of waves 0..2 sat in a branch of its own (four reads, a full wait, three MFMAs).  Here: every load is
-// unconditional - the address of an item that does not exist is replaced by the tensor's first element and its value multiplied
-// by zero - and "no next brick" fetches the current one again; the dY tensor's affine comes from an identity table when it has
-// none; the body is instantiated for 4 and 3 taps and the wave picks its copy once, outside the brick loop; a k-step requests the
-// NEXT k-step's operands before its own MFMAs.  Nothing inside the brick loop branches, so every wait is a counted one.
-__device__ float w16u_ident[16] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-struct W16uHi { u32x2 a[2]; u32x2 x[3]; };       // hi halves of a k-step's operands: dY (2 transposing reads), halo row (3) - requested one k-step ahead
-struct W16uLo { u32x2 a[2]; u32x2 x[3]; };       // lo halves, requested at the top of their own k-step (first used behind the hi x hi MFMAs)
-struct W16uExt { u32x2 h[2], l[2]; };            // the fourth tap's X operand
-
-#define W16U_PIN4(v) asm volatile("" : "+v"(v))
-template <typename F, int... I>
-__device__ __forceinline__ void w16u_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void w16u_static_for(F&& f) { w16u_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
-template <int V> using ic_ = std::integral_constant<int, V>;
-template <int NT, int DBG, bool SINGLE>
-__device__ __forceinline__ void wgrad16u_run(const WgradParams& p, const int w) {
-    extern __shared__ char lds8[];
-    float* xtab = reinterpret_cast<float*>(lds8 + WT_LDS);
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-    const int tp = blockIdx.y, mt = tp / p.n_tiles, nt = tp % p.n_tiles, m0 = mt * 32, n0 = nt * 32;
-    f32x16 acc[NT], accl[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; accl[j][r] = 0.f; }
-    const int i16 = lane & 15, q = i16 >> 2, pp = i16 & 3, cb = (lane >> 4) & 1;
-    // per-lane LDS byte offsets of the three operand streams (buffer base and the k-step's row are added per use: immediates)
-    const int a_off = 2 * WT_XB + ((lh * 8 + q) * 32 + 16 * cb + 4 * pp) * 2;
-    const int b_lane = ((lh * 10 + q) * 32 + 16 * cb + 4 * pp) * 2;
-    const int x_off = b_lane + (((w / 3) * 10 + w % 3) * 10) * 64;
-    const int e_off = b_lane + ((2 * 10 + 2) * 10 + min(w, 2)) * 64;
-    const int per_frame = p.nbz * p.nby * p.nbx, total = p.in.N * per_frame;
-    const int oct = tid & 3;
-    for (int i = tid; i < p.in.N * 64; i += 512) {
-        const int n = i >> 6, which = (i >> 5) & 1, c = n0 + (i & 31);
-        xtab[i] = p.in.scale ? (c < p.Nc ? (which ? p.in.shift : p.in.scale)[(size_t)n * p.in.C + c] : 0.f) : (which ? 0.f : 1.f);
-    }
-    // (the table is read by other threads than those that wrote it, first in the prologue below: without this barrier a wave that ran
-    //  ahead converted its first items with whatever the previous workgroup left in LDS - a run-to-run difference of ~1e-4 in the
-    //  weight gradient of one layer, one run in ~80 when the kernel ran alone and one in ~5 beside the main stream's kernels; round 4)
-    __syncthreads();
-    const int dummy_off = WT_LDS + p.in.N * 256;      // 32 B written by the threads without a fourth X item
-    int xn = 0, xoz = 0, xoy = 0, xox = 0;
-    auto locate = [&](int b) __attribute__((always_inline)) {
-        xn = b / per_frame; int r = b % per_frame;
-        const int bx = r % p.nbx; r /= p.nbx;
-        xoz = (r / p.nby) * 2; xoy = (r % p.nby) * 8; xox = bx * 8;
-    };
-    const bool ca_ok = n0 + 8 * oct < p.Nc, cb_ok = n0 + 8 * oct + 4 < p.Nc;
-    const bool ma_ok = m0 + 8 * oct < p.M, mb_ok = m0 + 8 * oct + 4 < p.M;
-    // X item k: halo voxel (tid >> 2) + 128 k as packed (hx, hy, hz, exists), channel octet oct
-    int hpack[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int hv0 = (tid >> 2) + 128 * k, hv = min(hv0, WT_HV - 1), hx = hv % 10, hy = (hv / 10) % 10, hz = hv / 100;
-        hpack[k] = hx | (hy << 8) | (hz << 16) | ((hv0 < WT_HV ? 1 : 0) << 24);
-    }
-    // two unconditional 16-byte loads; an item outside the volume (or the tile's channels) reads the tensor's first element and is
-    // multiplied by zero at its conversion.  (The unpacking goes through an opaque copy: as a loop invariant the compiler keeps the
-    // twelve coordinates in registers of their own, spills them, and a scratch reload queues behind the loads in flight.)
-    auto x_inside = [&](int hp, int& gx, int& gy, int& gz) __attribute__((always_inline)) {
-        gx = xox - 1 + (hp & 255); gy = xoy - 1 + ((hp >> 8) & 255); gz = xoz - 1 + ((hp >> 16) & 255);
-        return (unsigned)gz < (unsigned)p.in.D && (unsigned)gy < (unsigned)p.in.H && (unsigned)gx < (unsigned)p.in.W && (hp >> 24) != 0;
-    };
-    auto x_issue = [&](int k, f32x4& a, f32x4& b) __attribute__((always_inline)) {
-        int hp = hpack[k], gx, gy, gz;
-        asm volatile("" : "+v"(hp));
-        const bool in = x_inside(hp, gx, gy, gz);
-        const long long off = ((((long long)xn * p.in.D + gz) * p.in.H + gy) * p.in.W + gx) * (long long)p.in.C + n0 + 8 * oct;
-        const float* src = p.in.p + off;
-        const float* sa = in && ca_ok ? src : p.in.p;
-        const float* sb = in && cb_ok ? src + 4 : p.in.p;
-        a = *reinterpret_cast<const f32x4*>(sa); b = *reinterpret_cast<const f32x4*>(sb);
-    };
-    // the dY item: brick voxel tid >> 2, channel octet; values now, the tensor's pending affine (identity table without one) one
-    // k-step ahead of the conversion
-    auto d_issue = [&](f32x4& a, f32x4& b) __attribute__((always_inline)) {
-        int t = tid;
-        asm volatile("" : "+v"(t));
-        const int bv = t >> 2, z = bv >> 6, y = (bv >> 3) & 7, x = bv & 7, m = m0 + 8 * (t & 3);
-        const float* src = p.dy.p + ((((size_t)xn * p.dy.D + xoz + z) * p.dy.H + xoy + y) * p.dy.W + xox + x) * p.dy.C + m;
-        a = *reinterpret_cast<const f32x4*>(ma_ok ? src : p.dy.p); b = *reinterpret_cast<const f32x4*>(mb_ok ? src + 4 : p.dy.p);
-    };
-    auto d_affine = [&](f32x4& sa, f32x4& sb, f32x4& ha, f32x4& hb) __attribute__((always_inline)) {
-        int t = tid;
-        asm volatile("" : "+v"(t));
-        const bool has = p.dy.scale != nullptr;
-        const size_t so = (size_t)xn * p.dy.C + m0 + 8 * (t & 3);
-        const float* ps = has ? p.dy.scale + so : w16u_ident; const float* ph = has ? p.dy.shift + so : w16u_ident + 8;
-        sa = *reinterpret_cast<const f32x4*>(ma_ok ? ps : w16u_ident); ha = *reinterpret_cast<const f32x4*>(ma_ok ? ph : w16u_ident + 8);
-        sb = *reinterpret_cast<const f32x4*>(mb_ok ? ps + 4 : w16u_ident); hb = *reinterpret_cast<const f32x4*>(mb_ok ? ph + 4 : w16u_ident + 8);
-    };
-    auto split_store = [&](const f32x4& a, const f32x4& b, char* hi, char* lo) __attribute__((always_inline)) {
-        unsigned h[4], l[4];
-        h[0] = pack_split(a[0], a[1], l[0]); h[1] = pack_split(a[2], a[3], l[1]);
-        h[2] = pack_split(b[0], b[1], l[2]); h[3] = pack_split(b[2], b[3], l[3]);
-        *reinterpret_cast<u32x4*>(hi) = u32x4{h[0], h[1], h[2], h[3]};
-        if constexpr (!SINGLE) *reinterpret_cast<u32x4*>(lo) = u32x4{l[0], l[1], l[2], l[3]};
-    };
-    // conversions: the item's registers pass through an opaque statement first - otherwise the compiler starts the arithmetic right
-    // behind the loads (it frees registers) and waits for them there
-    auto x_commit = [&](char* cbase, int k, int n, f32x4 a, f32x4 b) __attribute__((always_inline)) {
-        W16U_PIN4(a); W16U_PIN4(b);
-        int hp = hpack[k], gx, gy, gz;
-        asm volatile("" : "+v"(hp));
-        const bool in = x_inside(hp, gx, gy, gz);        // (recomputed: cheaper than a register carried from the request)
-        const float* t = xtab + n * 64 + 8 * oct;
-        const f32x4 sa = *reinterpret_cast<const f32x4*>(t), sb = *reinterpret_cast<const f32x4*>(t + 4);
-        const f32x4 ha = *reinterpret_cast<const f32x4*>(t + 32), hb = *reinterpret_cast<const f32x4*>(t + 36);
-        const float ka = in && ca_ok ? 1.f : 0.f, kb = in && cb_ok ? 1.f : 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = fmaf(a[j], sa[j], ha[j]); b[j] = fmaf(b[j], sb[j], hb[j]);
-            a[j] = fmaxf(a[j], a[j] * p.in.slope) * ka; b[j] = fmaxf(b[j], b[j] * p.in.slope) * kb;
-        }
-        char* hi = cbase + 8192 * k; char* lo = hi + WT_XB;                 // (voxel (tid >> 2) + 128 k, octet) = byte 16 tid + 8192 k
-        if (k == 3) { const bool item = tid < 64; hi = item ? hi : lds8 + dummy_off; lo = item ? lo : lds8 + dummy_off + 16; }
-        split_store(a, b, hi, lo);
-    };
-    auto d_commit = [&](char* cbase, f32x4 a, f32x4 b, f32x4 sa, f32x4 sb, f32x4 ha, f32x4 hb) __attribute__((always_inline)) {
-        W16U_PIN4(a); W16U_PIN4(b); W16U_PIN4(sa); W16U_PIN4(sb); W16U_PIN4(ha); W16U_PIN4(hb);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a[j] = fmaf(a[j], sa[j], ha[j]); b[j] = fmaf(b[j], sb[j], hb[j]);
-            a[j] = fmaxf(a[j], a[j] * p.dy.slope) * (ma_ok ? 1.f : 0.f); b[j] = fmaxf(b[j], b[j] * p.dy.slope) * (mb_ok ? 1.f : 0.f);
-        }
-        split_store(a, b, cbase + 2 * WT_XB, cbase + 2 * WT_XB + WT_DB);
-    };
-    auto read_hi = [&](const char* buf, int s8, W16uHi& o) __attribute__((always_inline)) {
-        const char* ap = buf + a_off + s8 * 1024;
-        const char* lp = buf + x_off + (((s8 >> 2) * 10 + 2 * (s8 & 3)) * 10) * 64;
-        o.a[0] = tr_read(ap); o.a[1] = tr_read(ap + 4 * 64);
-        o.x[0] = tr_read(lp); o.x[1] = tr_read(lp + 4 * 64); o.x[2] = tr_read(lp + 8 * 64);
-    };
-    auto read_lo = [&](const char* buf, int s8, W16uLo& o) __attribute__((always_inline)) {
-        const char* ap = buf + a_off + s8 * 1024 + WT_DB;
-        const char* lp = buf + x_off + (((s8 >> 2) * 10 + 2 * (s8 & 3)) * 10) * 64 + WT_XB;
-        o.x[0] = tr_read(lp); o.x[1] = tr_read(lp + 4 * 64); o.x[2] = tr_read(lp + 8 * 64);
-        o.a[0] = tr_read(ap); o.a[1] = tr_read(ap + 4 * 64);
-    };
-    auto read_ext = [&](const char* buf, int s8, W16uExt& e) __attribute__((always_inline)) {
-        const char* xp = buf + e_off + (((s8 >> 2) * 10 + 2 * (s8 & 3)) * 10) * 64;
-        e.h[0] = tr_read(xp); e.h[1] = tr_read(xp + 4 * 64);
-        if constexpr (!SINGLE) { e.l[0] = tr_read(xp + WT_XB); e.l[1] = tr_read(xp + WT_XB + 4 * 64); }
-    };
-    auto shifted = [&](const u32x2& r0, const u32x2& r1, const u32x2& r2, half8 (&o)[3]) __attribute__((always_inline)) {
-        o[0] = __builtin_bit_cast(half8, u32x4{r0[0], r0[1], r1[0], r1[1]});
-        o[2] = __builtin_bit_cast(half8, u32x4{r0[1], r1[0], r1[1], r2[0]});
-        o[1] = __builtin_bit_cast(half8, u32x4{__builtin_amdgcn_alignbit(r0[1], r0[0], 16), __builtin_amdgcn_alignbit(r1[0], r0[1], 16),
-                                               __builtin_amdgcn_alignbit(r1[1], r1[0], 16), __builtin_amdgcn_alignbit(r2[0], r1[1], 16)});
-    };
-    int b = blockIdx.x, cur = 0;
-    if (b < total) {                                  // the first brick: plain fetch + convert (once per workgroup)
-        locate(b);
-        f32x4 a, c, sa, sb, ha, hb;
-        char* cbase = lds8 + tid * 16;
-        d_issue(a, c); d_affine(sa, sb, ha, hb); d_commit(cbase, a, c, sa, sb, ha, hb);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { x_issue(k, a, c); x_commit(cbase, k, xn, a, c); }
-    }
-    __syncthreads();
-    for (; b < total; b += p.S) {
-        const bool has_next = b + p.S < total;
-        const char* buf = lds8 + cur * WT_BUF;
-        char* cbase = lds8 + (cur ^ 1) * WT_BUF + tid * 16;
-        locate(has_next ? b + p.S : b);               // (no next brick: this one again, into the idle buffer)
-        // staging of the next brick, two items in flight: requested at the end of a k-step, converted at the end of the second (dY,
-        // X0, X1) or third (X2, X3) k-step after it
-        f32x4 da, db, dsa, dsb, dha, dhb, xa[4], xb[4];
-        constexpr bool STAGE = DBG != 2 && DBG != 3 && DBG != 4;
-        if (STAGE) d_issue(da, db);
-        W16uHi h0, h1;
-        W16uLo lo;
-        W16uExt e0;
-        if (DBG != 1) read_hi(buf, 0, h0);
-        // An item's conversion as six pieces (+ the request of a later item, + the dY affine's loads), placed by hand between the
-        // k-step's MFMAs: left to itself the scheduler issues the MFMAs back to back and the ~130 vector instructions as one block
-        // behind them, through which the matrix pipe idles (sched_group_barrier spreads some k-steps and not others).
-        f32x4 ca, cb, csa, csb, cha, chb;
-        float cka = 0.f, ckb = 0.f, cslope = 1.f;
-        unsigned ch[4], cl[4];
-        w16u_static_for<8>([&](auto S8) __attribute__((always_inline)) {
-            constexpr int s8 = decltype(S8)::value;
-            constexpr int CI = s8 >= 2 && s8 <= 6 ? s8 - 2 : -1;          // item converted in this k-step: 0 = dY, 1..4 = X item CI - 1
-            constexpr int RI = s8 <= 3 ? s8 : -1;                          // X item requested in this k-step
-            auto piece = [&](auto P) __attribute__((always_inline)) {
-                constexpr int pc = decltype(P)::value;
-                if constexpr (!STAGE) return;
-                if constexpr (CI >= 0 && pc == 0) {
-                    if constexpr (CI == 0) {
-                        ca = da; cb = db; csa = dsa; csb = dsb; cha = dha; chb = dhb;
-                        W16U_PIN4(ca); W16U_PIN4(cb); W16U_PIN4(csa); W16U_PIN4(csb); W16U_PIN4(cha); W16U_PIN4(chb);
-                        cka = ma_ok ? 1.f : 0.f; ckb = mb_ok ? 1.f : 0.f; cslope = p.dy.slope;
-                    } else {
-                        ca = xa[CI - 1]; cb = xb[CI - 1];
-                        W16U_PIN4(ca); W16U_PIN4(cb);
-                        int hp = hpack[CI - 1], gx, gy, gz;
-                        asm volatile("" : "+v"(hp));
-                        const bool in = x_inside(hp, gx, gy, gz);
-                        cka = in && ca_ok ? 1.f : 0.f; ckb = in && cb_ok ? 1.f : 0.f; cslope = p.in.slope;
-                        const float* t = xtab + xn * 64 + 8 * oct;
-                        csa = *reinterpret_cast<const f32x4*>(t); csb = *reinterpret_cast<const f32x4*>(t + 4);
-                        cha = *reinterpret_cast<const f32x4*>(t + 32); chb = *reinterpret_cast<const f32x4*>(t + 36);
-                    }
-                }
-                if constexpr (CI >= 0 && pc >= 1 && pc <= 4) {
-                    constexpr int j = (pc - 1) & 1;
-                    float v0, v1;
-                    if constexpr (pc <= 2) {
-                        v0 = fmaf(ca[2 * j], csa[2 * j], cha[2 * j]); v1 = fmaf(ca[2 * j + 1], csa[2 * j + 1], cha[2 * j + 1]);
-                        v0 = fmaxf(v0, v0 * cslope) * cka; v1 = fmaxf(v1, v1 * cslope) * cka;
-                    } else {
-                        v0 = fmaf(cb[2 * j], csb[2 * j], chb[2 * j]); v1 = fmaf(cb[2 * j + 1], csb[2 * j + 1], chb[2 * j + 1]);
-                        v0 = fmaxf(v0, v0 * cslope) * ckb; v1 = fmaxf(v1, v1 * cslope) * ckb;
-                    }
-                    ch[pc - 1] = pack_split(v0, v1, cl[pc - 1]);
-                }
-                if constexpr (CI >= 0 && pc == 5) {
-                    char* hi; char* lo_;
-                    if constexpr (CI == 0) { hi = cbase + 2 * WT_XB; lo_ = hi + WT_DB; }
-                    else {
-                        hi = cbase + 8192 * (CI - 1); lo_ = hi + WT_XB;
-                        if constexpr (CI == 4) { const bool item = tid < 64; hi = item ? hi : lds8 + dummy_off; lo_ = item ? lo_ : lds8 + dummy_off + 16; }
-                    }
-                    *reinterpret_cast<u32x4*>(hi) = u32x4{ch[0], ch[1], ch[2], ch[3]};
-                    if constexpr (!SINGLE) *reinterpret_cast<u32x4*>(lo_) = u32x4{cl[0], cl[1], cl[2], cl[3]};
-                }
-                if constexpr (RI >= 0 && pc == 6) x_issue(RI, xa[RI], xb[RI]);
-                if constexpr (s8 == 1 && pc == 7) d_affine(dsa, dsb, dha, dhb);
-            };
-            if constexpr (DBG == 1) {
-                w16u_static_for<8>([&](auto P) __attribute__((always_inline)) { piece(P); });
-            } else {
-                W16uHi& hc = (s8 & 1) ? h1 : h0;
-                W16uHi& hn = (s8 & 1) ? h0 : h1;
-                if (DBG == 3) { if (s8 == 0) { if (NT == 4) read_ext(buf, 0, e0); read_lo(buf, 0, lo); h1 = h0; } }
-                else {
-                    if (NT == 4) read_ext(buf, s8, e0);
-                    if (!SINGLE) read_lo(buf, s8, lo);
-                    if (s8 < 7) read_hi(buf, s8 + 1, hn);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const W16uHi& o = DBG == 3 ? h0 : hc;
-                // the MFMAs in order, each followed by the piece of its position (DBG 5: all pieces behind the last MFMA instead)
-                auto slot = [&](auto P) __attribute__((always_inline)) {
-                    if constexpr (DBG != 5) { __builtin_amdgcn_sched_barrier(0); piece(P); __builtin_amdgcn_sched_barrier(0); }
-                };
-                const half8 ah = __builtin_bit_cast(half8, u32x4{o.a[0][0], o.a[0][1], o.a[1][0], o.a[1][1]});
-                half8 bh[3], eh;
-                shifted(o.x[0], o.x[1], o.x[2], bh);
-                if constexpr (NT == 4) eh = __builtin_bit_cast(half8, u32x4{e0.h[0][0], e0.h[0][1], e0.h[1][0], e0.h[1][1]});
-                constexpr int Q = NT == 4 ? 1 : 0;        // position shift behind each group's fourth MFMA
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[0], acc[0], 0, 0, 0); slot(ic_<0>{});
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[1], acc[1], 0, 0, 0); slot(ic_<1>{});
-                acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[2], acc[2], 0, 0, 0); slot(ic_<2>{});
-                if constexpr (NT == 4) { acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, eh, acc[3], 0, 0, 0); slot(ic_<3>{}); }
-                if constexpr (!SINGLE) {
-                    half8 bl[3];
-                    shifted(lo.x[0], lo.x[1], lo.x[2], bl);
-                    accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], accl[0], 0, 0, 0); slot(ic_<3 + Q>{});
-                    accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[1], accl[1], 0, 0, 0); slot(ic_<4 + Q>{});
-                    accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[2], accl[2], 0, 0, 0); slot(ic_<5 + Q>{});
-                    if constexpr (NT == 4) {
-                        accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(half8, u32x4{e0.l[0][0], e0.l[0][1], e0.l[1][0], e0.l[1][1]}), accl[3], 0, 0, 0);
-                        slot(ic_<7>{});
-                    }
-                    const half8 al = __builtin_bit_cast(half8, u32x4{lo.a[0][0], lo.a[0][1], lo.a[1][0], lo.a[1][1]});
-                    accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], accl[0], 0, 0, 0); slot(ic_<6 + 2 * Q>{});
-                    accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], accl[1], 0, 0, 0); slot(ic_<7 + 2 * Q>{});
-                    accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[2], accl[2], 0, 0, 0);
-                    if constexpr (NT == 4) accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, eh, accl[3], 0, 0, 0);
-                    if constexpr (DBG == 5) w16u_static_for<8>([&](auto P) __attribute__((always_inline)) { piece(P); });
-                    // (positions 8 .. 10 of the four-tap waves carry no piece: 8 pieces in all)
-                } else {
-                    // one product: the pieces beyond the three / four MFMAs follow the last one
-                    w16u_static_for<8 - 3 - Q>([&](auto P) __attribute__((always_inline)) { piece(ic_<decltype(P)::value + 3 + Q>{}); });
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        });
-        if (DBG != 4) __syncthreads();                    // (4: timing experiment without the brick barrier, no staging)
-        cur ^= 1;
-    }
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int t = j < 3 ? 3 * w + j : 24 + w;
-        float* dst = p.part + (((size_t)blockIdx.x * gridDim.y + tp) * 27 + t) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[((r >> 2) * 8 + lh * 4 + (r & 3)) * 32 + l31] = acc[j][r] + accl[j][r] * (1.0f / W16_SPLIT);
-    }
-}
-
-template <int DBG, bool SINGLE = false>
-__global__ __launch_bounds__(512, 1) void wgrad16u_kernel(WgradParams p) {
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (w < 3) wgrad16u_run<4, DBG, SINGLE>(p, w);
-    else wgrad16u_run<3, DBG, SINGLE>(p, w);
-}
-
-// ---- wgrad16z: wgrad16u walking its bricks along z with the shared halo planes kept in LDS -------------------------------------
+// stores - and an operand is two transposed reads (x = 0..3, 4..7 of a brick row); the four reads of a 32-lane half cover 256
+// contiguous bytes (conflict-free).  512 threads, one workgroup per CU: wave w owns the tap line (dz, dy) = (w / 3, w % 3) - taps
+// 3 w + dx, whose three X operands come out of ONE halo row read (x = -1 .. 10 as three transposed reads: dx = 0 is registers 0..3,
+// dx = 2 registers 1..4, dx = 1 four v_alignbit) - and waves 0..2 also tap 24 + w of the ninth line: the body is instantiated for
+// 4 and 3 taps and a wave picks its copy once.  Partials and the reduce are wgrad16_kernel's.
+// The memory pipeline is statically countable: every staging load is unconditional - the address of an item that does not exist
+// (halo voxel outside the volume, channel tail, no next brick) is replaced by the tensor's first element and its value multiplied
+// by zero at the conversion - and the dY tensor's affine comes from an identity table when it has none.  Nothing inside the brick
+// loop branches, so the compiler counts the loads in flight (no s_waitcnt vmcnt(0) in front of every conversion), and a k-step
+// requests the NEXT k-step's operands behind its own MFMAs.  (DESIGN_HISTORY.md: the two kernels this one grew out of.)
 // A 2 x 8 x 8 brick needs the 4 x 10 x 10 halo of its input: 3.1 staged voxels per brick voxel, and the staging (activate, split,
 // 9-10 vector instructions per element at 4 issue cycles each) costs the SIMDs about as many cycles as the MFMAs - the kernel is
 // bound by vector issue, not by the matrix pipe.  Consecutive bricks of one (frame, y, x) column share two of their four halo
@@ -1246,12 +711,31 @@ __global__ __launch_bounds__(512, 1) void wgrad16u_kernel(WgradParams p) {
 #define WZ_PL (100 * 64)                  // one plane of one ring: 100 halo voxels x 32 fp16 channels
 #define WZ_XR (6 * WZ_PL)                 // hi ring; the lo ring follows
 #define WZ_D0 (2 * WZ_XR)                 // two dY buffers (hi 8 KB + lo 8 KB each)
-#define WZ_DBUF (2 * WT_DB)
+#define WZ_DB (128 * 64)                  // one dY tile: 128 brick voxels x 32 fp16 channels
+#define WZ_DBUF (2 * WZ_DB)
 #define WZ_LDS (WZ_D0 + 2 * WZ_DBUF)
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef short short4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x2 tr_read(const char* lds_ptr) {
+    // (take the 64-bit result as a whole: element-wise extraction of the builtin's vector is miscompiled by this hipcc)
+    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)lds_ptr));
+}
+__device__ float w16z_ident[16] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // scale 1 x 8, shift 0 x 8
+
+struct W16zHi { u32x2 a[2]; u32x2 x[3]; };       // hi halves of a k-step's operands: dY (2 transposing reads), halo row (3) - requested one k-step ahead
+struct W16zLo { u32x2 a[2]; u32x2 x[3]; };       // lo halves, requested inside their own k-step (first used behind the hi x hi MFMAs)
+struct W16zExt { u32x2 h[2], l[2]; };            // the fourth tap's X operand
+
+#define W16Z_PIN4(v) asm volatile("" : "+v"(v))
+template <typename F, int... I>
+__device__ __forceinline__ void w16z_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void w16z_static_for(F&& f) { w16z_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
+template <int V> using ic_ = std::integral_constant<int, V>;
 
 // H16: both operand tensors are stored as bfloat16 (16-bit storage mode): an item's eight channels are ONE 16-byte load, kept raw in
 // the `a` register quad and widened (shift / mask) inside the conversion pieces - two more vector instructions per affine piece
-template <int NT, int DBG, bool SINGLE, bool H16>
+template <int NT, bool SINGLE, bool H16>
 __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) {
     extern __shared__ char lds8[];
     float* xtab = reinterpret_cast<float*>(lds8 + WZ_LDS);
@@ -1281,7 +765,8 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
     const bool ca_ok = n0 + 8 * oct < p.Nc, cb_ok = n0 + 8 * oct + 4 < p.Nc;
     const bool ma_ok = m0 + 8 * oct < p.M, mb_ok = m0 + 8 * oct + 4 < p.M;
     int xn = 0, xoy = 0, xox = 0;
-    // one 16-byte-pair item of the input: halo voxel (gz, xoy - 1 + hy, xox - 1 + hx); unconditional loads (wgrad16u)
+    // one 16-byte-pair item of the input: halo voxel (gz, xoy - 1 + hy, xox - 1 + hx).  The loads are unconditional: an item outside
+    // the volume or the tile's channels reads the tensor's first element and is multiplied by zero at its conversion (`in`)
     auto x_load = [&](int gz, int hy, int hx, bool exists, f32x4& a, f32x4& b, bool& in) __attribute__((always_inline)) {
         const int gy = xoy - 1 + hy, gx = xox - 1 + hx;
         in = (unsigned)gz < (unsigned)p.in.D && (unsigned)gy < (unsigned)p.in.H && (unsigned)gx < (unsigned)p.in.W && exists;
@@ -1308,9 +793,9 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
         asm volatile("" : "+v"(t));
         const bool has = p.dy.scale != nullptr;
         const size_t so = (size_t)xn * p.dy.C + m0 + 8 * (t & 3);
-        const float* ps = has ? p.dy.scale + so : w16u_ident; const float* ph = has ? p.dy.shift + so : w16u_ident + 8;
-        sa = *reinterpret_cast<const f32x4*>(ma_ok ? ps : w16u_ident); ha = *reinterpret_cast<const f32x4*>(ma_ok ? ph : w16u_ident + 8);
-        sb = *reinterpret_cast<const f32x4*>(mb_ok ? ps + 4 : w16u_ident); hb = *reinterpret_cast<const f32x4*>(mb_ok ? ph + 4 : w16u_ident + 8);
+        const float* ps = has ? p.dy.scale + so : w16z_ident; const float* ph = has ? p.dy.shift + so : w16z_ident + 8;
+        sa = *reinterpret_cast<const f32x4*>(ma_ok ? ps : w16z_ident); ha = *reinterpret_cast<const f32x4*>(ma_ok ? ph : w16z_ident + 8);
+        sb = *reinterpret_cast<const f32x4*>(mb_ok ? ps + 4 : w16z_ident); hb = *reinterpret_cast<const f32x4*>(mb_ok ? ph + 4 : w16z_ident + 8);
     };
     // conversion of one item in the open (column starts): affine, leaky ReLU, zero mask, split, two 16-byte stores
     auto convert_store = [&](f32x4 a, f32x4 b, const f32x4& sa, const f32x4& sb, const f32x4& ha, const f32x4& hb, float slope, float ka, float kb,
@@ -1340,7 +825,7 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
     }
     // (xb / db / eb: the lane's byte address of the stream in this brick's ring slot / dY buffer, one opaque register each - as an
     //  expression of bz the compiler forms one address register per read)
-    auto read_hi = [&](int xb, int db, int s8, W16uHi& o) __attribute__((always_inline)) {
+    auto read_hi = [&](int xb, int db, int s8, W16zHi& o) __attribute__((always_inline)) {
         const char* ap = lds8 + db + s8 * 1024;
         const char* lp = lds8 + xb + (2 * (s8 & 3) * 10) * 64;
         o.a[0] = tr_read(ap); o.a[1] = tr_read(ap + 4 * 64);
@@ -1352,8 +837,10 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
         o[1] = __builtin_bit_cast(half8, u32x4{__builtin_amdgcn_alignbit(r0[1], r0[0], 16), __builtin_amdgcn_alignbit(r1[0], r0[1], 16),
                                                __builtin_amdgcn_alignbit(r1[1], r1[0], 16), __builtin_amdgcn_alignbit(r2[0], r1[1], 16)});
     };
-    constexpr bool STAGE = DBG != 2;
-    float* dtab = reinterpret_cast<float*>(lds8 + WZ_LDS + p.in.N * 256 + 64);      // the dY tensor's pending affine of the column's frame: [scale 32][shift 32]
+    // pieces of a brick's staging (below).  A local the piece lambda names, not a literal there: hipcc makes it the lambda's first capture,
+    // and without that member the <false, false> instantiation comes out with 2 spilled VGPRs and 12 B of scratch (disassembly A/B)
+    constexpr int NPIECE = 60;
+    float* dtab = reinterpret_cast<float*>(lds8 + WZ_LDS + p.in.N * 256 + 64);     // the dY tensor's pending affine of the column's frame: [scale 32][shift 32]
     const long long xstep = 2LL * p.in.H * p.in.W * p.in.C, dstep = 2LL * p.dy.H * p.dy.W * p.dy.C;    // one brick further along z
 
     int cur = 0;
@@ -1380,7 +867,7 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
                 f32x4 da, db, dsa, dsb, dha, dhb;
                 d_issue(0, da, db); d_affine(dsa, dsb, dha, dhb);
                 convert_store(da, db, dsa, dsb, dha, dhb, p.dy.slope, ma_ok ? 1.f : 0.f, mb_ok ? 1.f : 0.f,
-                              lds8 + WZ_D0 + cur * WZ_DBUF + tid * 16, lds8 + WZ_D0 + cur * WZ_DBUF + WT_DB + tid * 16);
+                              lds8 + WZ_D0 + cur * WZ_DBUF + tid * 16, lds8 + WZ_D0 + cur * WZ_DBUF + WZ_DB + tid * 16);
             }
 #pragma unroll 1
             for (int k = 0; k < 4; ++k) {
@@ -1407,10 +894,10 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
             const int ns0 = slot_off(4), ns1 = slot_off(5);                    // slots of the next brick's two new planes
             const int bzn = min(bz + 1, p.nbz - 1);        // (behind the column's last brick: its dY tile again, into the idle buffer)
             f32x4 da, db, xa[2], xb[2];
-            W16uHi h0, h1;
-            W16uLo lo;
-            W16uExt e0;
-            if (DBG != 1) read_hi(xb0, dbs, 0, h0);
+            W16zHi h0, h1;
+            W16zLo lo;
+            W16zExt e0;
+            read_hi(xb0, dbs, 0, h0);
             // The next brick's staging as 60 pieces of 4-6 vector instructions, one behind each MFMA (position g = 9 k-step + MFMA;
             // the one-product instantiation runs three per MFMA): a wave hides about five single-issue instructions in the 32 cycles
             // of a 32x32x16 MFMA, and blocks of 20+ (a whole element pair per gap) measured no better than the conversion as one
@@ -1423,7 +910,7 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
             const float* xsrc = nullptr; bool xin = false;
             auto piece = [&](auto GG) __attribute__((always_inline)) {
                 constexpr int g = decltype(GG)::value;
-                if constexpr (!STAGE || g < 0 || g >= 60) return;
+                if constexpr (g < 0 || g >= NPIECE) return;
                 if constexpr (g == 0) {
                     if constexpr (H16) da = *reinterpret_cast<const f32x4*>(ma_ok ? nm_eptr(p.dy.p, (size_t)(doff + bzn * dstep), 1) : p.dy.p);
                     else {
@@ -1459,7 +946,7 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
                             cka = in && ca_ok ? 1.f : 0.f; ckb = in && cb_ok ? 1.f : 0.f; cslope = p.in.slope;
                             t = xtab + xn * 64 + 8 * oct;
                         }
-                        W16U_PIN4(ca); if constexpr (!H16) W16U_PIN4(cb_);
+                        W16Z_PIN4(ca); if constexpr (!H16) W16Z_PIN4(cb_);
                         csa = *reinterpret_cast<const f32x4*>(t); cha = *reinterpret_cast<const f32x4*>(t + 32);
                     } else if constexpr (c <= 12) {
                         constexpr int j = (c - 1) / 3, part = (c - 1) % 3, e = 2 * (j & 1);
@@ -1483,7 +970,7 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
                         } else ch[j] = pack_split(tt[0], tt[1], cl[j]);
                     } else {
                         char* hi; char* lo_;
-                        if constexpr (item == 0) { hi = lds8 + WZ_D0 + ndbuf + tid * 16; lo_ = hi + WT_DB; }
+                        if constexpr (item == 0) { hi = lds8 + WZ_D0 + ndbuf + tid * 16; lo_ = hi + WZ_DB; }
                         else {
                             int np = npack[item - 1];
                             asm volatile("" : "+v"(np));
@@ -1496,71 +983,67 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
                     }
                 }
             };
-            w16u_static_for<8>([&](auto S8) __attribute__((always_inline)) {
+            w16z_static_for<8>([&](auto S8) __attribute__((always_inline)) {
                 constexpr int s8 = decltype(S8)::value;
-                if constexpr (DBG == 1) {
-                    w16u_static_for<9>([&](auto P) __attribute__((always_inline)) { piece(ic_<9 * s8 + decltype(P)::value>{}); });
-                } else {
-                    W16uHi& hc = (s8 & 1) ? h1 : h0;
-                    W16uHi& hn = (s8 & 1) ? h0 : h1;
-                    const int xbc = s8 < 4 ? xb0 : xb1, xbn = s8 + 1 < 4 ? xb0 : xb1, ebc = s8 < 4 ? eb0 : eb1;
-                    const char* lpc = lds8 + xbc + (2 * (s8 & 3) * 10) * 64 + WZ_XR;                 // this k-step's lo halo row
-                    const char* apc = lds8 + dbs + s8 * 1024 + WT_DB;                               //              lo dY operand
-                    const char* lpn = lds8 + xbn + (2 * ((s8 + 1) & 3) * 10) * 64;                   // the next k-step's hi halo row
-                    const char* apn = lds8 + dbs + (s8 + 1) * 1024;
-                    const char* epc = lds8 + ebc + (2 * (s8 & 3) * 10) * 64;
-                    // behind MFMA number `pos`: this k-step's lo operands (first used by MFMA 3 / 6), the fourth tap's operand (its
-                    // MFMAs close the k-step), the next k-step's hi operands one read per gap - no block of 10-14 LDS reads in front of a
-                    // k-step's first MFMA - and the staging piece of the position
-                    auto slot = [&](auto P) __attribute__((always_inline)) {
-                        constexpr int pos = decltype(P)::value;
-                        __builtin_amdgcn_sched_barrier(0);
-                        if constexpr (!SINGLE) {
-                            if constexpr (pos == 0) { lo.a[0] = tr_read(apc); lo.a[1] = tr_read(apc + 4 * 64); }
-                            if constexpr (pos == 1) { lo.x[0] = tr_read(lpc); lo.x[1] = tr_read(lpc + 4 * 64); lo.x[2] = tr_read(lpc + 8 * 64); }
-                            if constexpr (NT == 4 && pos == 2) { e0.h[0] = tr_read(epc); e0.h[1] = tr_read(epc + 4 * 64); }
-                            if constexpr (NT == 4 && pos == 3) { e0.l[0] = tr_read(epc + WZ_XR); e0.l[1] = tr_read(epc + WZ_XR + 4 * 64); }
-                            if constexpr (s8 < 7) {
-                                if constexpr (pos == 4) hn.a[0] = tr_read(apn);
-                                if constexpr (pos == 5) hn.a[1] = tr_read(apn + 4 * 64);
-                                if constexpr (pos == 6) hn.x[0] = tr_read(lpn);
-                                if constexpr (pos == 7) hn.x[1] = tr_read(lpn + 4 * 64);
-                                if constexpr (pos == 8) hn.x[2] = tr_read(lpn + 8 * 64);
-                            }
-                            if constexpr (pos < 9) piece(ic_<9 * s8 + pos>{});
-                        } else {
-                            if constexpr (NT == 4 && pos == 0) { e0.h[0] = tr_read(epc); e0.h[1] = tr_read(epc + 4 * 64); }
-                            if constexpr (s8 < 7 && pos == 1) { hn.a[0] = tr_read(apn); hn.a[1] = tr_read(apn + 4 * 64); }
-                            if constexpr (s8 < 7 && pos == 2) { hn.x[0] = tr_read(lpn); hn.x[1] = tr_read(lpn + 4 * 64); hn.x[2] = tr_read(lpn + 8 * 64); }
-                            piece(ic_<9 * s8 + 3 * pos>{}); piece(ic_<9 * s8 + 3 * pos + 1>{}); piece(ic_<9 * s8 + 3 * pos + 2>{});
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    };
-                    const half8 ah = __builtin_bit_cast(half8, u32x4{hc.a[0][0], hc.a[0][1], hc.a[1][0], hc.a[1][1]});
-                    half8 bh[3];
-                    shifted(hc.x[0], hc.x[1], hc.x[2], bh);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[0], acc[0], 0, 0, 0); slot(ic_<0>{});
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[1], acc[1], 0, 0, 0); slot(ic_<1>{});
-                    acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[2], acc[2], 0, 0, 0); slot(ic_<2>{});
+                W16zHi& hc = (s8 & 1) ? h1 : h0;
+                W16zHi& hn = (s8 & 1) ? h0 : h1;
+                const int xbc = s8 < 4 ? xb0 : xb1, xbn = s8 + 1 < 4 ? xb0 : xb1, ebc = s8 < 4 ? eb0 : eb1;
+                const char* lpc = lds8 + xbc + (2 * (s8 & 3) * 10) * 64 + WZ_XR;                 // this k-step's lo halo row
+                const char* apc = lds8 + dbs + s8 * 1024 + WZ_DB;                               //              lo dY operand
+                const char* lpn = lds8 + xbn + (2 * ((s8 + 1) & 3) * 10) * 64;                   // the next k-step's hi halo row
+                const char* apn = lds8 + dbs + (s8 + 1) * 1024;
+                const char* epc = lds8 + ebc + (2 * (s8 & 3) * 10) * 64;
+                // behind MFMA number `pos`: this k-step's lo operands (first used by MFMA 3 / 6), the fourth tap's operand (its
+                // MFMAs close the k-step), the next k-step's hi operands one read per gap - no block of 10-14 LDS reads in front of a
+                // k-step's first MFMA - and the staging piece of the position
+                auto slot = [&](auto P) __attribute__((always_inline)) {
+                    constexpr int pos = decltype(P)::value;
+                    __builtin_amdgcn_sched_barrier(0);
                     if constexpr (!SINGLE) {
-                        const half8 al = __builtin_bit_cast(half8, u32x4{lo.a[0][0], lo.a[0][1], lo.a[1][0], lo.a[1][1]});
-                        accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], accl[0], 0, 0, 0); slot(ic_<3>{});
-                        accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], accl[1], 0, 0, 0); slot(ic_<4>{});
-                        accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[2], accl[2], 0, 0, 0); slot(ic_<5>{});
-                        half8 bl[3];
-                        shifted(lo.x[0], lo.x[1], lo.x[2], bl);
-                        accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], accl[0], 0, 0, 0); slot(ic_<6>{});
-                        accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[1], accl[1], 0, 0, 0); slot(ic_<7>{});
-                        accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[2], accl[2], 0, 0, 0); slot(ic_<8>{});
-                        if constexpr (NT == 4) {
-                            const half8 eh = __builtin_bit_cast(half8, u32x4{e0.h[0][0], e0.h[0][1], e0.h[1][0], e0.h[1][1]});
-                            acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, eh, acc[3], 0, 0, 0);
-                            accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, eh, accl[3], 0, 0, 0);
-                            accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(half8, u32x4{e0.l[0][0], e0.l[0][1], e0.l[1][0], e0.l[1][1]}), accl[3], 0, 0, 0);
+                        if constexpr (pos == 0) { lo.a[0] = tr_read(apc); lo.a[1] = tr_read(apc + 4 * 64); }
+                        if constexpr (pos == 1) { lo.x[0] = tr_read(lpc); lo.x[1] = tr_read(lpc + 4 * 64); lo.x[2] = tr_read(lpc + 8 * 64); }
+                        if constexpr (NT == 4 && pos == 2) { e0.h[0] = tr_read(epc); e0.h[1] = tr_read(epc + 4 * 64); }
+                        if constexpr (NT == 4 && pos == 3) { e0.l[0] = tr_read(epc + WZ_XR); e0.l[1] = tr_read(epc + WZ_XR + 4 * 64); }
+                        if constexpr (s8 < 7) {
+                            if constexpr (pos == 4) hn.a[0] = tr_read(apn);
+                            if constexpr (pos == 5) hn.a[1] = tr_read(apn + 4 * 64);
+                            if constexpr (pos == 6) hn.x[0] = tr_read(lpn);
+                            if constexpr (pos == 7) hn.x[1] = tr_read(lpn + 4 * 64);
+                            if constexpr (pos == 8) hn.x[2] = tr_read(lpn + 8 * 64);
                         }
-                    } else if constexpr (NT == 4) {
-                        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(half8, u32x4{e0.h[0][0], e0.h[0][1], e0.h[1][0], e0.h[1][1]}), acc[3], 0, 0, 0);
+                        if constexpr (pos < 9) piece(ic_<9 * s8 + pos>{});
+                    } else {
+                        if constexpr (NT == 4 && pos == 0) { e0.h[0] = tr_read(epc); e0.h[1] = tr_read(epc + 4 * 64); }
+                        if constexpr (s8 < 7 && pos == 1) { hn.a[0] = tr_read(apn); hn.a[1] = tr_read(apn + 4 * 64); }
+                        if constexpr (s8 < 7 && pos == 2) { hn.x[0] = tr_read(lpn); hn.x[1] = tr_read(lpn + 4 * 64); hn.x[2] = tr_read(lpn + 8 * 64); }
+                        piece(ic_<9 * s8 + 3 * pos>{}); piece(ic_<9 * s8 + 3 * pos + 1>{}); piece(ic_<9 * s8 + 3 * pos + 2>{});
                     }
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                const half8 ah = __builtin_bit_cast(half8, u32x4{hc.a[0][0], hc.a[0][1], hc.a[1][0], hc.a[1][1]});
+                half8 bh[3];
+                shifted(hc.x[0], hc.x[1], hc.x[2], bh);
+                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[0], acc[0], 0, 0, 0); slot(ic_<0>{});
+                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[1], acc[1], 0, 0, 0); slot(ic_<1>{});
+                acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[2], acc[2], 0, 0, 0); slot(ic_<2>{});
+                if constexpr (!SINGLE) {
+                    const half8 al = __builtin_bit_cast(half8, u32x4{lo.a[0][0], lo.a[0][1], lo.a[1][0], lo.a[1][1]});
+                    accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], accl[0], 0, 0, 0); slot(ic_<3>{});
+                    accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], accl[1], 0, 0, 0); slot(ic_<4>{});
+                    accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[2], accl[2], 0, 0, 0); slot(ic_<5>{});
+                    half8 bl[3];
+                    shifted(lo.x[0], lo.x[1], lo.x[2], bl);
+                    accl[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], accl[0], 0, 0, 0); slot(ic_<6>{});
+                    accl[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[1], accl[1], 0, 0, 0); slot(ic_<7>{});
+                    accl[2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[2], accl[2], 0, 0, 0); slot(ic_<8>{});
+                    if constexpr (NT == 4) {
+                        const half8 eh = __builtin_bit_cast(half8, u32x4{e0.h[0][0], e0.h[0][1], e0.h[1][0], e0.h[1][1]});
+                        acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, eh, acc[3], 0, 0, 0);
+                        accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, eh, accl[3], 0, 0, 0);
+                        accl[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(half8, u32x4{e0.l[0][0], e0.l[0][1], e0.l[1][0], e0.l[1][1]}), accl[3], 0, 0, 0);
+                    }
+                } else if constexpr (NT == 4) {
+                    acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(half8, u32x4{e0.h[0][0], e0.h[0][1], e0.h[1][0], e0.h[1][1]}), acc[3], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -1577,11 +1060,11 @@ __device__ __forceinline__ void wgrad16z_run(const WgradParams& p, const int w) 
     }
 }
 
-template <int DBG, bool SINGLE = false, bool H16 = false>
+template <bool SINGLE, bool H16>
 __global__ __launch_bounds__(512, 1) void wgrad16z_kernel(WgradParams p) {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (w < 3) wgrad16z_run<4, DBG, SINGLE, H16>(p, w);
-    else wgrad16z_run<3, DBG, SINGLE, H16>(p, w);
+    if (w < 3) wgrad16z_run<4, SINGLE, H16>(p, w);
+    else wgrad16z_run<3, SINGLE, H16>(p, w);
 }
 
 // ---- first layer, sparse form ----------------------------------------------------------------------------------------------------
@@ -1770,6 +1253,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
         const float s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
         dW[((size_t)m * Cin + c) * taps + tap] = s * mm;
     }
+}
+int launch_wgrad_reduce(const float* part, int slots, int tiles, int n_tiles, int groups, int M, int Cin, int taps, int k5occ,
+                        const float* mul, float* dW, hipStream_t s) {
+    const int total = M * Cin * taps;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min((total + 255) / 256, 4096)), dim3(256), 0, s, part, slots, tiles, n_tiles, groups,
+                       M, Cin, taps, k5occ, mul, dW);
+    return nm_check_hip(hipGetLastError(), "wgrad reduce launch");
 }
 
 // voxels per block of the partial-sum pass: 512, or 2048 for the large volumes (a 512-voxel block of a 32-channel layer lives ~4 us:
@@ -2399,10 +1889,19 @@ bool wgrad16_eligible(int OD, int OH, int OW, int ks, int stride) {
     return ks == 3 && stride == 1 && OD % 2 == 0 && OH % 8 == 0 && OW % 8 == 0;
 }
 
-// wgrad16t/u/z_kernel keep the per-frame scale / shift rows of their input in LDS (256 B per frame): at 96 frames wgrad16t/u ask for
-// 159808 of the 163840 B.  Bfloat16 operands exist on wgrad16z_kernel only, so above that count launch_wgrad16 runs it once per group
-// of at most W16_TAB_FRAMES frames (equal groups: 97 frames are 49 + 48, not 96 + 1), every group on its own range of partial-sum slots.
+// wgrad16z_kernel keeps the per-frame scale / shift rows of its input in LDS (256 B per frame) behind its tiles.  The bound of 96
+// frames is the one its predecessors' larger tiles left room for in the 163840 B (DESIGN_HISTORY.md); at 96 frames wgrad16z asks
+// for 134464 B.  Bfloat16 operands exist on wgrad16z_kernel only, so above that count launch_wgrad16 runs it once per group of at
+// most W16_TAB_FRAMES frames (equal groups: 97 frames are 49 + 48, not 96 + 1), every group on its own range of partial-sum slots.
 #define W16_TAB_FRAMES 96
+// Does wgrad16z_kernel take the call?  The one place that says so: plan_wgrad sizes the partial sums by it and launch_wgrad16 fills
+// them.  It needs a column of at least two bricks (nbz >= 2: the ring of z-planes) and a frame table that fits - or, above
+// W16_TAB_FRAMES frames, bfloat16 operands in the 16-bit storage mode, which run as frame groups.  Everything else is
+// wgrad16_kernel: more than 96 frames of fp32 operands, NM355_WGRAD_TR=0, and a volume one brick deep (2 x 8k x 8k voxels) - no layer
+// of the network has one (cubes whose y and x extents are multiples of 8 have nbz >= 4), only the op-level entry point reaches it.
+bool w16z_takes(int N, int nbz, bool h16) {
+    return nm_ls().wgrad_tr && nbz >= 2 && (N <= W16_TAB_FRAMES || (h16 && nm_ls().store16));
+}
 int w16_group_frames(int N) { const int groups = (N + W16_TAB_FRAMES - 1) / W16_TAB_FRAMES; return (N + groups - 1) / groups; }
 // slots of all groups together: a group has no more workgroups per tile pair than (frame, y, x) columns
 int w16_group_slots(int N, int S, int cols_per_frame) {
@@ -2430,12 +1929,13 @@ WgradPlan plan_wgrad(int N, int OD, int OH, int OW, int M, int Nc, int ks, int s
         const int wgs = nm_ls().wgrad_wgs > 0 ? nm_ls().wgrad_wgs : (nm_ls().wgrad_async == 1 && !nm_ls().single ? 224 : 256);
         p.S = max(1, min(total, max(tiles, wgs) / tiles));
         // wgrad16z_kernel hands out whole (frame, y, x) columns: no more workgroups per tile pair than columns
-        if (nm_ls().wgrad_tr && nm_ls().wgrad_z && p.nbz >= 2 && N <= W16_TAB_FRAMES) p.S = max(1, min(p.S, N * p.nby * p.nbx));
+        const bool z = w16z_takes(N, p.nbz, false);
+        if (z) p.S = max(1, min(p.S, N * p.nby * p.nbx));
         q.slots = p.S; q.lds = W16_LDS;
-        // 16-bit storage above W16_TAB_FRAMES frames: one wgrad16z launch per frame group, each with its own slots (launch_wgrad16)
+        // more frames than that, should the operands turn out bfloat16 (the plan does not see them): one wgrad16z launch per frame
+        // group, each with its own slots (launch_wgrad16)
         int ws_slots = q.slots;
-        if (nm_ls().store16 && nm_ls().wgrad_tr && nm_ls().wgrad_z && p.nbz >= 2 && N > W16_TAB_FRAMES)
-            ws_slots = max(ws_slots, w16_group_slots(N, p.S, p.nby * p.nbx));
+        if (!z && w16z_takes(N, p.nbz, true)) ws_slots = max(ws_slots, w16_group_slots(N, p.S, p.nby * p.nbx));
         q.ws_floats = (size_t)ws_slots * tiles * 27 * 1024;
         return q;
     }
@@ -2471,28 +1971,33 @@ int launch_wgrad_t(const WgradPlan& q, hipStream_t s) {
 }
 
 
-int w16z_set_attr() {
+// one wgrad16z launch of p.S workgroups per tile pair; LDS: tiles, X affine table (256 B per frame), dummy item, dY affine table
+int launch_w16z(const WgradParams& p, int tiles, hipStream_t s) {
     static NmDeviceOnce attr_z;
-    return nm_raise_lds_limit(attr_z, 160 * 1024, "wgrad16z: cannot raise the dynamic LDS limit", &wgrad16z_kernel<0>, &wgrad16z_kernel<1>,
-                              &wgrad16z_kernel<2>, &wgrad16z_kernel<0, true>, &wgrad16z_kernel<0, true, true>);
+    if (int rc = nm_raise_lds_limit(attr_z, 160 * 1024, "wgrad16z: cannot raise the dynamic LDS limit", &wgrad16z_kernel<false, false>,
+                                    &wgrad16z_kernel<true, false>, &wgrad16z_kernel<true, true>)) return rc;
+    const size_t ldsz = WZ_LDS + (size_t)p.in.N * 64 * sizeof(float) + 64 + 256;
+    const dim3 grid(p.S, tiles);
+    if (p.in.h) hipLaunchKernelGGL((wgrad16z_kernel<true, true>), grid, dim3(512), ldsz, s, p);
+    else if (nm_conv_single()) hipLaunchKernelGGL((wgrad16z_kernel<true, false>), grid, dim3(512), ldsz, s, p);
+    else hipLaunchKernelGGL((wgrad16z_kernel<false, false>), grid, dim3(512), ldsz, s, p);
+    return nm_check_hip(hipGetLastError(), "wgrad16z launch");
 }
 
 // q.slots: the partial-sum slots the launch filled (the fixed-order reduce of run_wgrad walks them all)
 int launch_wgrad16(WgradPlan& q, hipStream_t s) {
+    const int N = q.p.in.N, tiles = q.m_tiles * q.p.n_tiles;
+    const bool h16 = q.p.in.h || q.p.dy.h, z = w16z_takes(N, q.p.nbz, h16);
     // 16-bit storage: both operands bfloat16, on the z-walking kernel only (every layer of >= 32^3 voxels has nbz >= 16)
-    const bool h16 = q.p.in.h || q.p.dy.h;
-    // (above W16_TAB_FRAMES frames plan_wgrad sized the partial sums for the frame groups in the storage mode only)
-    if (h16 && !(q.p.in.h && q.p.dy.h && nm_conv_single() && nm_ls().wgrad_tr && nm_ls().wgrad_z && q.p.nbz >= 2 &&
-                 (q.p.in.N <= W16_TAB_FRAMES || nm_ls().store16))) {
+    if (h16 && !(q.p.in.h && q.p.dy.h && nm_conv_single() && z)) {
         nm_set_error("wgrad16: bfloat16 operands (in %d, dy %d) need conv mode 4, both tensors bfloat16 and the wgrad16z kernel", q.p.in.h, q.p.dy.h);
         return NM_ERR_UNSUPPORTED;
     }
-    if (h16 && q.p.in.N > W16_TAB_FRAMES) {
+    if (z && N > W16_TAB_FRAMES) {
         // more frames than table rows: one launch per frame group - the group's frames as a tensor of their own (data and scale / shift
         // rows offset by its first frame), its partials behind those of the groups before it.  Groups and slots in a fixed order, one
         // reduce over all of them: deterministic, no atomics.
-        if (int rc = w16z_set_attr()) return rc;
-        const int N = q.p.in.N, gf = w16_group_frames(N), tiles = q.m_tiles * q.p.n_tiles;
+        const int gf = w16_group_frames(N);
         const size_t xframe = (size_t)q.p.in.D * q.p.in.H * q.p.in.W * q.p.in.C, dframe = (size_t)q.p.dy.D * q.p.dy.H * q.p.dy.W * q.p.dy.C;
         int slot0 = 0;
         for (int f0 = 0; f0 < N; f0 += gf) {
@@ -2504,53 +2009,17 @@ int launch_wgrad16(WgradPlan& q, hipStream_t s) {
             if (pz.dy.scale) { pz.dy.scale += (size_t)f0 * pz.dy.C; pz.dy.shift += (size_t)f0 * pz.dy.C; }
             pz.S = max(1, min(q.p.S, n * pz.nby * pz.nbx));
             pz.part = q.p.part + (size_t)slot0 * tiles * 27 * 1024;
-            const size_t ldsz = WZ_LDS + (size_t)n * 64 * sizeof(float) + 64 + 256;
-            hipLaunchKernelGGL((wgrad16z_kernel<0, true, true>), dim3(pz.S, tiles), dim3(512), ldsz, s, pz);
-            if (int rc = nm_check_hip(hipGetLastError(), "wgrad16z launch")) return rc;
+            if (int rc = launch_w16z(pz, tiles, s)) return rc;
             slot0 += pz.S;
         }
         q.slots = slot0;
         return NM_OK;
     }
-    if (nm_ls().wgrad_tr && q.p.in.N <= W16_TAB_FRAMES) {                       // (the per-frame scale / shift table of wgrad16t_kernel lives in LDS: 256 B per frame)
-        static NmDeviceOnce attr_t;
-        if (int rc = nm_raise_lds_limit(attr_t, 160 * 1024, "wgrad16t: cannot raise the dynamic LDS limit", &wgrad16t_kernel<0>, &wgrad16t_kernel<1>,
-                &wgrad16t_kernel<2>, &wgrad16t_kernel<0, true>, &wgrad16u_kernel<0>, &wgrad16u_kernel<1>, &wgrad16u_kernel<2>, &wgrad16u_kernel<3>,
-                &wgrad16u_kernel<4>, &wgrad16u_kernel<5>, &wgrad16u_kernel<0, true>)) return rc;
-        const size_t ldsb = WT_LDS + (size_t)q.p.in.N * 64 * sizeof(float) + 64;
-        const dim3 grid(q.p.S, q.m_tiles * q.p.n_tiles);
-        if (nm_ls().wgrad_z && q.p.nbz >= 2) {
-            if (int rc = w16z_set_attr()) return rc;
-            const WgradParams& pz = q.p;                  // (plan_wgrad bounded S by the column count)
-            const size_t ldsz = WZ_LDS + (size_t)q.p.in.N * 64 * sizeof(float) + 64 + 256;   // tiles, X affine table, dummy item, dY affine table
-            const dim3 gz(pz.S, q.m_tiles * q.p.n_tiles);
-            if (h16) hipLaunchKernelGGL((wgrad16z_kernel<0, true, true>), gz, dim3(512), ldsz, s, pz);
-            else if (q.p.dbg == 1) hipLaunchKernelGGL(wgrad16z_kernel<1>, gz, dim3(512), ldsz, s, pz);
-            else if (q.p.dbg == 2) hipLaunchKernelGGL(wgrad16z_kernel<2>, gz, dim3(512), ldsz, s, pz);
-            else if (nm_conv_single()) hipLaunchKernelGGL((wgrad16z_kernel<0, true>), gz, dim3(512), ldsz, s, pz);
-            else hipLaunchKernelGGL(wgrad16z_kernel<0>, gz, dim3(512), ldsz, s, pz);
-            return nm_check_hip(hipGetLastError(), "wgrad16z launch");
-        }
-        if (nm_ls().wgrad_u) {
-            if (q.p.dbg == 1) hipLaunchKernelGGL(wgrad16u_kernel<1>, grid, dim3(512), ldsb, s, q.p);
-            else if (q.p.dbg == 2) hipLaunchKernelGGL(wgrad16u_kernel<2>, grid, dim3(512), ldsb, s, q.p);
-            else if (q.p.dbg == 3) hipLaunchKernelGGL(wgrad16u_kernel<3>, grid, dim3(512), ldsb, s, q.p);
-            else if (q.p.dbg == 4) hipLaunchKernelGGL(wgrad16u_kernel<4>, grid, dim3(512), ldsb, s, q.p);
-            else if (q.p.dbg == 5) hipLaunchKernelGGL(wgrad16u_kernel<5>, grid, dim3(512), ldsb, s, q.p);
-            else if (nm_conv_single()) hipLaunchKernelGGL((wgrad16u_kernel<0, true>), grid, dim3(512), ldsb, s, q.p);
-            else hipLaunchKernelGGL(wgrad16u_kernel<0>, grid, dim3(512), ldsb, s, q.p);
-            return nm_check_hip(hipGetLastError(), "wgrad16u launch");
-        }
-        if (q.p.dbg == 1) hipLaunchKernelGGL(wgrad16t_kernel<1>, grid, dim3(512), ldsb, s, q.p);
-        else if (q.p.dbg == 2) hipLaunchKernelGGL(wgrad16t_kernel<2>, grid, dim3(512), ldsb, s, q.p);
-        else if (nm_conv_single()) hipLaunchKernelGGL((wgrad16t_kernel<0, true>), grid, dim3(512), ldsb, s, q.p);
-        else hipLaunchKernelGGL(wgrad16t_kernel<0>, grid, dim3(512), ldsb, s, q.p);
-        return nm_check_hip(hipGetLastError(), "wgrad16t launch");
-    }
+    if (z) return launch_w16z(q.p, tiles, s);             // (plan_wgrad bounded S by the column count)
     static NmDeviceOnce attr_set;
     if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16: cannot raise the dynamic LDS limit", &wgrad16_kernel<false>, &wgrad16_kernel<true>)) return rc;
-    if (nm_conv_single()) hipLaunchKernelGGL(wgrad16_kernel<true>, dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
-    else hipLaunchKernelGGL(wgrad16_kernel<false>, dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
+    if (nm_conv_single()) hipLaunchKernelGGL(wgrad16_kernel<true>, dim3(q.p.S, tiles), dim3(256), q.lds, s, q.p);
+    else hipLaunchKernelGGL(wgrad16_kernel<false>, dim3(q.p.S, tiles), dim3(256), q.lds, s, q.p);
     return nm_check_hip(hipGetLastError(), "wgrad16 launch");
 }
 
@@ -2572,11 +2041,7 @@ int run_wgrad(WgradPlan& q, float* ws, float* dW, int cin_real, int taps, hipStr
     else if (q.p.ks == 3) rc = launch_wgrad_t<0, 7>(q, s);
     else { nm_set_error("wgrad: ks=%d unsupported", q.p.ks); return NM_ERR_UNSUPPORTED; }
     if (rc) return rc;
-    const int tiles = q.m_tiles * q.p.n_tiles;
-    const int total = q.p.M * cin_real * taps;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min((total + 255) / 256, 4096)), dim3(256), 0, s, ws, q.slots, tiles, q.p.n_tiles,
-                       q.p.groups, q.p.M, cin_real, taps, q.mode == 2 ? 1 : 0, mul, dW);
-    return nm_check_hip(hipGetLastError(), "wgrad reduce launch");
+    return launch_wgrad_reduce(ws, q.slots, q.m_tiles * q.p.n_tiles, q.p.n_tiles, q.p.groups, q.p.M, cin_real, taps, q.mode == 2 ? 1 : 0, mul, dW, s);
 }
 
 }  // namespace
@@ -2602,6 +2067,14 @@ static int launch_k2f16_t(const WgradParams& p, dim3 grid, hipStream_t s) {
     if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16k2: cannot raise the dynamic LDS limit", &wgrad16k2_kernel<MT, SINGLE, HX, HD>)) return rc;
     hipLaunchKernelGGL((wgrad16k2_kernel<MT, SINGLE, HX, HD>), grid, dim3(256), ldsb, s, p);
     return nm_check_hip(hipGetLastError(), "wgrad16k2 launch");
+}
+// the product form and the operands' storage pick the instantiation (bfloat16 dY comes with bfloat16 X only: nm_launch_wgrad)
+template <int MT>
+static int launch_k2f16_mt(const WgradParams& p, dim3 grid, hipStream_t s) {
+    if (!nm_conv_single()) return launch_k2f16_t<MT, false, false, false>(p, grid, s);
+    if (p.dy.h) return launch_k2f16_t<MT, true, true, true>(p, grid, s);
+    if (p.in.h) return launch_k2f16_t<MT, true, true, false>(p, grid, s);
+    return launch_k2f16_t<MT, true, false, false>(p, grid, s);
 }
 
 size_t nm_wgrad_ws_floats(int N, int OD, int OH, int OW, int M, int Nc, int ks, int stride) {
@@ -2642,39 +2115,20 @@ int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride
         else hipLaunchKernelGGL(wgrad_k1_kernel<6>, dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
         int rc = nm_check_hip(hipGetLastError(), "wgrad_k1 launch");
         if (rc) return rc;
-        const int totalw = dy.C * cin_real;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min((totalw + 255) / 256, 4096)), dim3(256), 0, s, ws, S, T, n_tiles, 1, dy.C, cin_real, 1, 0, mul, dW);
-        return nm_check_hip(hipGetLastError(), "wgrad reduce launch");
+        return launch_wgrad_reduce(ws, S, T, n_tiles, 1, dy.C, cin_real, 1, 0, mul, dW, s);
     }
     if (allow_f16 && pad == 0 && k2f16_shape_eligible(dy.D, dy.H, dy.W, dy.C, ks, stride) && in.D == 2 * dy.D && in.H == 2 * dy.H && in.W == 2 * dy.W &&
         (!in.h || in.C % 8 == 0) && (!dy.h || (dy.C % 8 == 0 && in.h)) && (!(in.h || dy.h) || nm_conv_single())) {
-        WgradParams p; p.in = in; p.dy = dy; p.part = ws; p.ks = 2; p.stride = 2; p.pad = 0; p.M = dy.C; p.Nc = in.C; p.dbg = 0;
+        WgradParams p; p.in = in; p.dy = dy; p.part = ws; p.ks = 2; p.stride = 2; p.pad = 0; p.M = dy.C; p.Nc = in.C;
         const int m_tiles = (dy.C + 31) / 32, n_tiles = (in.C + 31) / 32;
         p.n_tiles = n_tiles; p.groups = 8;
         p.S = k2f16_slots(in.N, dy.D, dy.H, dy.W, in.C);
         const dim3 grid(p.S, n_tiles);
-        const bool single = nm_conv_single();
-        int rc;
-        if (m_tiles <= 2) {
-            if (!single) rc = launch_k2f16_t<2, false, false, false>(p, grid, s);
-            else if (dy.h) rc = launch_k2f16_t<2, true, true, true>(p, grid, s);
-            else if (in.h) rc = launch_k2f16_t<2, true, true, false>(p, grid, s);
-            else rc = launch_k2f16_t<2, true, false, false>(p, grid, s);
-        } else {
-            if (!single) rc = launch_k2f16_t<4, false, false, false>(p, grid, s);
-            else if (dy.h) rc = launch_k2f16_t<4, true, true, true>(p, grid, s);
-            else if (in.h) rc = launch_k2f16_t<4, true, true, false>(p, grid, s);
-            else rc = launch_k2f16_t<4, true, false, false>(p, grid, s);
-        }
-        if (rc) return rc;
-        const int totalw = dy.C * cin_real * 8;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(min((totalw + 255) / 256, 4096)), dim3(256), 0, s, ws, p.S, m_tiles * n_tiles, n_tiles, 8, dy.C, cin_real, 8, 0, mul, dW);
-        return nm_check_hip(hipGetLastError(), "wgrad reduce launch");
+        if (int rc = m_tiles <= 2 ? launch_k2f16_mt<2>(p, grid, s) : launch_k2f16_mt<4>(p, grid, s)) return rc;
+        return launch_wgrad_reduce(ws, p.S, m_tiles * n_tiles, n_tiles, 8, dy.C, cin_real, 8, 0, mul, dW, s);
     }
     WgradPlan q = plan_wgrad(in.N, dy.D, dy.H, dy.W, dy.C, in.C, ks, stride, false, f16);
     q.p.in = in; q.p.dy = dy; q.p.pad = pad;
-    static const int dbg = getenv("NM355_W16_DBG") ? atoi(getenv("NM355_W16_DBG")) : 0;
-    q.p.dbg = dbg;
     return run_wgrad(q, ws, dW, cin_real, ks * ks * ks, s, mul);
 }
 

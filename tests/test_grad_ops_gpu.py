@@ -227,8 +227,9 @@ _K3_CASES = [c for c in BWD_CASES if c[2] == 3]
 
 
 def test_conv3d_backward_valu_transposition_wgrad_variant():
-    """The older weight-gradient kernel (wgrad16_kernel, VALU transposition; A/B partner of the default wgrad16t_kernel,
-    profiles/r02_wgrad16t_ab.txt, and the path for more than 96 frames): the k3 cases again on a context created with NM355_WGRAD_TR=0."""
+    """The older weight-gradient kernel (wgrad16_kernel, VALU transposition): the path of the fp32-storage modes for more than 96
+    frames and for a volume one brick deep, and the A/B partner of the default wgrad16z_kernel - NM355_WGRAD_TR=0 forces it for every
+    call.  The k3 cases again on a context created with that switch."""
     with _switches({"NM355_WGRAD_TR": "0"}):
         c = _fresh_ctx()
     try:
@@ -238,27 +239,15 @@ def test_conv3d_backward_valu_transposition_wgrad_variant():
         c.close()
 
 
-@pytest.mark.parametrize("env", [{"NM355_WGRAD_Z": "0"}, {"NM355_WGRAD_Z": "0", "NM355_WGRAD_U": "0"}, {"NM355_TAIL_RANK1": "0"},
-                                 {"NM355_GNB_APPLY4": "0", "NM355_DEFER_SUMS": "0"}, {"NM355_WGRAD_ASYNC": "0"}, {"NM355_WGRAD_ASYNC": "2"}],
-                         ids=["wgrad16u", "wgrad16t", "tail-gradient-tensor", "gnb-apply-and-sums-per-layer", "weight-gradients-in-the-main-stream",
+@pytest.mark.parametrize("env", [{"NM355_TAIL_RANK1": "0"}, {"NM355_GNB_APPLY4": "0", "NM355_DEFER_SUMS": "0"}, {"NM355_WGRAD_ASYNC": "0"},
+                                 {"NM355_WGRAD_ASYNC": "2"}],
+                         ids=["tail-gradient-tensor", "gnb-apply-and-sums-per-layer", "weight-gradients-in-the-main-stream",
                               "weight-gradients-enqueued-before-the-data-gradient"])
 def test_conv3d_backward_older_kernel_variants(env, golden_dir):
-    """The A/B partners of the round-3 defaults stay under parity: wgrad16u_kernel (bricks in any order, full halo per brick) and
-    wgrad16t_kernel (conditional staging loads) against the default wgrad16z_kernel (the k3 cases in the split-fp16 and the f16 mode on a
-    fresh context), and - re-running the reference's gradient fixture G8 on a fresh network - the decoder tail's backward with its
-    [F][G^3][32] gradient materialised (NM355_TAIL_RANK1=0), the GroupNorm backward with the one-voxel-at-a-time apply kernel and its
-    gamma / beta / bias sums launched per layer, and the weight gradients inside the main stream's chain / enqueued on their own stream
-    in front of the data gradient.  The switches are read when a context is created."""
-    if "NM355_TAIL_RANK1" in env or "NM355_GNB_APPLY4" in env or "NM355_WGRAD_ASYNC" in env:
-        from test_train_detector_gpu import test_detector_gradients_vs_reference_fixture as g8
-        with _switches(env):
-            g8(golden_dir)
-        return
+    """The A/B partners of the round-3 defaults stay under parity, re-running the reference's gradient fixture G8 on a fresh network:
+    the decoder tail's backward with its [F][G^3][32] gradient materialised (NM355_TAIL_RANK1=0), the GroupNorm backward with the
+    one-voxel-at-a-time apply kernel and its gamma / beta / bias sums launched per layer, and the weight gradients inside the main
+    stream's chain / enqueued on their own stream in front of the data gradient.  The switches are read when a context is created."""
+    from test_train_detector_gpu import test_detector_gradients_vs_reference_fixture as g8
     with _switches(env):
-        c = _fresh_ctx()
-    try:
-        for case in _K3_CASES:
-            for mode in (1, 3):
-                test_conv3d_backward(c, case, mode)
-    finally:
-        c.close()
+        g8(golden_dir)

@@ -7,8 +7,9 @@ in the library sit just above what the rest of the suite runs (64 frames per net
   64 / T whole clips, every pass with its own offsets into the table, the keypoints, the features, the first frames, the target, the
   reconstruction and the tail partials; the clip block is enqueued behind the second encoder chunk.
 
-  96 frames (nm_grad.hip, W16_TAB_FRAMES): wgrad16z/u/t_kernel keep a per-frame scale / shift table in LDS; above 96 frames the
-  fp32-storage modes run wgrad16_kernel, and the 16-bit storage mode (conv mode 4) runs wgrad16z_kernel once per group of frames.
+  96 frames (nm_grad.hip, W16_TAB_FRAMES): wgrad16z_kernel keeps a per-frame scale / shift table in LDS; above 96 frames the
+  fp32-storage modes run wgrad16_kernel (as a volume one brick deep does at every frame count), and the 16-bit storage mode (conv
+  mode 4) runs wgrad16z_kernel once per group of frames.
 
 Op level: every kernel against torch CPU autograd of the same op in float64 (inputs drawn in fp32 and cast), at the project's own bounds
 (2e-5 of the gradient's max magnitude in modes 0 and 1, 3e-3 in mode 3; torch's fp32 autograd is 1.2e-6 .. 3.1e-6 from fp64 at these
@@ -21,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from test_ops_gpu import ctx, to_cl, from_cl, relerr, dev  # noqa: F401  (ctx is a fixture)
-from test_grad_ops_gpu import REL, F16_REL, _switches, _fresh_ctx
+from test_grad_ops_gpu import REL, F16_REL
 from test_train_detector_gpu import AIST, TOL, _setup, _oracle_grads, _hip_grads, _compare
 from test_network_gpu import KP_TOL, ACTS, PATHS, _net, _call, _err, _check_losses, _check_occupancy_set
 from neural_marionette_amd import HotPathOptions, synth
@@ -109,8 +110,8 @@ MANY_FRAMES = (
     [("a", K3, N, m, True) for N in (96, 97) for m in (0, 1, 3)] +
     # the same with 3 x 2 ragged tile pairs
     [("b", K3_RAGGED, N, m, True) for N in (96, 97) for m in (1, 3)] +
-    # nbz = 1: the default falls to wgrad16u_kernel, at the table's last row and past it
-    [("c", K3_NBZ1, N, 1, True) for N in (96, 97)] +
+    # nbz = 1 (no column for wgrad16z_kernel to walk): wgrad16_kernel at both counts, in both product forms
+    [("c", K3_NBZ1, N, m, True) for N in (96, 97) for m in (1, 3)] +
     # the reference's default frame count (24 clips of 10 frames)
     [("d", K3, 240, m, False) for m in (1, 3)] +
     # generic wgrad_kernel: 520 bricks over its 512 workgroup slots - one workgroup walks several bricks, the last ones ragged
@@ -126,19 +127,6 @@ MANY_FRAMES = (
 def test_conv3d_backward_many_frames(ctx, case):
     tag, shape, N, mode, prologue = case
     _conv_bwd(ctx, shape, N, mode, prologue, what="(%s)" % tag)
-
-
-@pytest.mark.parametrize("env", [{"NM355_WGRAD_Z": "0"}, {"NM355_WGRAD_Z": "0", "NM355_WGRAD_U": "0"}], ids=["wgrad16u", "wgrad16t"])
-def test_conv3d_backward_older_kernels_at_the_edge_of_lds(env):
-    """wgrad16u_kernel / wgrad16t_kernel at 96 frames: 135168 + 24576 + 64 = 159808 of the 163840 bytes of LDS, the table's last row in use."""
-    with _switches(env):
-        c = _fresh_ctx()
-    try:
-        for shape in (K3, K3_RAGGED):
-            for mode in (1, 3):
-                _conv_bwd(c, shape, 96, mode, True, what="(%s)" % ",".join(sorted(env)))
-    finally:
-        c.close()
 
 
 @pytest.mark.parametrize("C,groups,size,N,slope", [(32, 2, 4, 100, 0.01), (72, 4, 2, 130, 1.0)])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the weight-gradient path of one k3 layer (nm_op_conv3d_backward without data gradient): NM355_W16_DBG ablations.
+"""Times the weight-gradient path of one k3 layer (nm_op_conv3d_backward without data gradient); NM355_WGRAD_TR=0 times wgrad16_kernel.
 usage: time_wgrad16.py Cin Cout size N"""
 import sys, os, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -20,5 +20,5 @@ for _ in range(7):
     a.record(); call(); e.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(e))
 ts.sort()
 fl = 2.0 * N * size ** 3 * Cin * Cout * 27
-print("W16_DBG=%s  %dx%d @%d^3 x%d: median %.3f ms  (%.0f TFLOP/s algorithmic, x3 issued = %.2f of f16 peak)" % (
-    os.environ.get("NM355_W16_DBG", "0"), Cin, Cout, size, N, ts[3], fl / ts[3] / 1e9, 3 * fl / ts[3] / 1e9 / 2500))
+print("WGRAD_TR=%s  %dx%d @%d^3 x%d: median %.3f ms  (%.0f TFLOP/s algorithmic, x3 issued = %.2f of f16 peak)" % (
+    os.environ.get("NM355_WGRAD_TR", "1"), Cin, Cout, size, N, ts[3], fl / ts[3] / 1e9, 3 * fl / ts[3] / 1e9 / 2500))
