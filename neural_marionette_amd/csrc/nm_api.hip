@@ -39,8 +39,6 @@ NmLaunchState::NmLaunchState()
       up2c(env_int("NM355_UP2C", 1)),               // 0: fused-upsample layers stay on conv_f16s (diagnostic / A-B)
       up2c_diag(env_int("NM355_UP2C_DIAG", 0)),
       vrnn_mid(env_int("NM355_VRNN_MID", 1)),          // 0: prior steps as six launches instead of three (A/B)
-      vrnn_postmid(env_int("NM355_VRNN_POSTMID", 0)),   // 1: posterior steps of encode as three launches (vrnn_post_mid_kernel): measured slower, see there
-      vrnn_nb(env_int("NM355_VRNN_NB", 2)),             // batch rows per wavefront pass of the VRNN row kernels (4 / 8: the slow instantiations, A/B)
       vrnn_gemm(env_int("NM355_VRNN_GEMM", 1)),    // 0: one wavefront per output row at every batch size (A/B)
       vrnn_graph(env_int("NM355_VRNN_GRAPH", 1)),       // 0: rollouts enqueue their launches one by one instead of replaying a captured graph (A/B)
       sparse_first(env_int("NM355_SPARSE_FIRST", 1)), // 0: the first layer writes its dense output in inference too (A/B)
@@ -70,7 +68,7 @@ NmLaunchState::NmLaunchState()
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
       , up2c_shell(env_int("NM355_UP2C_SHELL", 1))          // the shell of the fused-upsample layers (split-fp16 mode, fp32 storage): 0: one line per face workgroup (A/B); 1: R lines per face workgroup (conv_up2c_face_r_kernel); 2: that and the edge items of the two-half layer with their loads in a ring (conv_up2c_edge_p_kernel: not the default, it does not clear the bar on the step); 3: the edge form alone; + 20 / 40: R = 2 / 4 at every layer (nm_up2c.hip)
-{ store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
+{ store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_backoff = env_int("NM355_CHAIN_BACKOFF", 0); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
   chain_wgpoll = env_int("NM355_CHAIN_WGPOLL", 1);      // 0: every wave of the cross-XCD rollout chain polls for itself (round 5; A/B)
   chain_xcd_nogo = env_int("NM355_CHAIN_XCD_NOGO", 0);  // test hook: the one-XCD chain never starts (its fallback must do the work)
   chain_xcd = env_int("NM355_CHAIN_XCD", 1); }           // 0: no one-XCD launch in front of the cross-XCD rollout chain (A/B); 1: for B = 1; 2: for B <= 8
@@ -224,11 +222,6 @@ int nm_ctx_create(nm_ctx** out, const nm_config* cfg) try {
     }
     for (int i = 0; i < 4; ++i) c->nf_host[i] = 0;
     { const char* e = getenv("NM355_RANGE_CHECK"); c->range_check = e ? atoi(e) : 1; }
-    if (hipMalloc(reinterpret_cast<void**>(&c->vrnn_cnt), 256 * sizeof(int32_t)) != hipSuccess || hipMemset(c->vrnn_cnt, 0, 256 * sizeof(int32_t)) != hipSuccess) {
-        nm_set_error("ctx_create: could not allocate the VRNN arrival counters");
-        delete c;
-        return NM_ERR_HIP;
-    }
     if (acquire_side_streams(cfg->device, &c->stream2, &c->stream3, &c->side_shared) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_w[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_w[1], hipEventDisableTiming) != hipSuccess ||
@@ -260,7 +253,6 @@ int nm_ctx_destroy(nm_ctx* ctx) try {
     for (void* p : ctx->owned) (void)hipFree(p);
     if (ctx->ws.base) (void)hipFree(ctx->ws.base);
     if (ctx->ws2.base) (void)hipFree(ctx->ws2.base);
-    if (ctx->vrnn_cnt) (void)hipFree(ctx->vrnn_cnt);
     if (ctx->ws_t.base) (void)hipFree(ctx->ws_t.base);
     if (ctx->copy_table) (void)hipFree(ctx->copy_table);
     if (ctx->pack_table) (void)hipFree(ctx->pack_table);

@@ -183,10 +183,11 @@ struct NmLaunchState {
     bool store16 = false;      // mode 4 ('bf16'): mode 3's arithmetic + bfloat16 storage of the training path's large tensors
     int op_in_h = 0, op_out_h = 0;   // op-level entry points (nm_op_*): element type of the input-side / output-side tensors (nm_op_set_storage16)
     int store16_min = 32768;   // ... those with at least this many voxels per frame (NM355_STORE16_MIN; 32^3: everything above the hourglass)
-    // persistent rollout kernel (nm_vrnn.hip vrnn_prior_chain_kernel): polls before a spin gives up (NM355_CHAIN_SPIN), trailing
+    // persistent rollout kernel (nm_vrnn.hip vrnn_prior_chain_kernel): polls before a spin gives up (NM355_CHAIN_SPIN), s_sleep(2) units
+    // between two polls (NM355_CHAIN_BACKOFF; 0 / 1 / 4 / 16 / 64: 17.0 / 18.0 / 17.3 / 19.5 / 25.9 us per step at B = 1), trailing
     // workgroups NOT launched (NM355_CHAIN_DROP_WG: the test hook that stands in for a workgroup that never becomes resident), and the
     // co-residency verdict of this context's device (-1: not asked yet, 0: the chain does not fit, 1: it does)
-    int chain_spin = 1 << 20, chain_drop = 0, chain_fits = -1, post_chain_fits = -1, chain_stat_delay = 0, chain_wgpoll = 1, chain_xcd_nogo = 0, chain_xcd = 1, chain_cus = 0;
+    int chain_spin = 1 << 20, chain_backoff = 0, chain_drop = 0, chain_fits = -1, post_chain_fits = -1, chain_stat_delay = 0, chain_wgpoll = 1, chain_xcd_nogo = 0, chain_xcd = 1, chain_cus = 0;
     bool prof_on = false;
     hipStream_t prof_stream = nullptr;     // main stream of the profiled context; prof_all: launches on any stream are recorded
     bool prof_all = false;
@@ -196,7 +197,7 @@ struct NmLaunchState {
     unsigned* nf_flag = nullptr;           // sticky device word gn_finalize ORs a 1 into (null: no reporting)
     // A/B and diagnostic switches (NM355_SUPERTILE, _SMALL16, _KSPLIT, _OCC16, _POOL16, _F16P2, _F16P, _WGRAD_TR, _UP2C, _UP2C_DIAG,
     // _VRNN_MID, _VRNN_GEMM, _VRNN_GRAPH, _SPARSE_FIRST, ..., _UP2Y_YPAD, _UP2C_SHELL)
-    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, tail_rank1, up2c, up2c_diag, vrnn_mid, vrnn_postmid, vrnn_nb, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, f16p_dma, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, up2c_x16, up2c_all, p2_defer, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell;
+    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, tail_rank1, up2c, up2c_diag, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, f16p_dma, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, up2c_x16, up2c_all, p2_defer, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell;
     NmLaunchState();
 };
 NmLaunchState& nm_ls();        // the state of the context whose ABI call runs on this thread

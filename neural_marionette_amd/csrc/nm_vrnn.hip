@@ -713,26 +713,13 @@ template <bool XCD> __device__ __forceinline__ void gran_store_t(nm_gran* p, flo
         asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(g) : "memory");
     } else gran_store(p, v, tag);
 }
-// (round-5 form, NM_GRAN_DWORDX2 == 0 only) HARDWARE ASSUMPTION (stated): a naturally aligned 16-byte global load observes each of its two naturally aligned 8-byte
-// halves whole - a granule {value, tag} written by ONE 8-byte store is never seen as {new tag, old value}.  The ISA text promises
-// single-copy atomicity for naturally aligned accesses up to 8 bytes and says nothing of 16-byte ones; on gfx950 a dwordx4 load of a
-// 16-byte-aligned address is served from one 64-byte L2 sector in one request and the writer's dwordx2 store updates its 8 bytes of
-// that sector in one piece, so a half cannot tear.  What the kernel relies on is exactly that, no more: the two halves MAY come from
-// different moments (one granule of the step, the other still of an older step - the poll then repeats).  Checked, not proved:
-// tests/test_network_gpu.py::test_persistent_rollout_long_chain_stays_bit_identical (6 000 steps at B = 4 beside a second context
-// hammering the device: one torn granule would change every later step) and tools/stress_identity.py.  NM355_VRNN_CHAIN=0 is the
-// path that does not depend on it.
-// A lane's granule loads of one poll as ONE asm statement: all loads issued (16-byte sc1 loads = two neighbouring granules, 8-byte = one),
-// then one wait - the compiler must not touch a destination between its load and the wait (an untracked load's register is stale until
-// then), hence a single statement with early-clobber outputs
-#ifndef NM_GRAN_DWORDX2
-#define NM_GRAN_DWORDX2 1
-#endif
-#if NM_GRAN_DWORDX2
-// Round 6 (verdict r5 item 11): every granule is read by an 8-byte load of its own - the access size the ISA's single-copy atomicity
-// covers - instead of 16-byte loads of granule PAIRS.  A pair is two loads at offset 0 / 8 from the same address register; the
-// returned register layout is the pair loads' (value, tag, value, tag).  Cost against the pair loads (same call, one device):
-// profiles/r06_granule_loads_ab.txt.  -DNM_GRAN_DWORDX2=0 (make x4: libnm355_x4.so) builds the round-5 loads for that A/B.
+// HARDWARE ASSUMPTION (stated): a granule {value, tag} written by ONE naturally aligned 8-byte store is never seen as
+// {new tag, old value}.  The ISA promises single-copy atomicity for naturally aligned accesses up to 8 bytes and says nothing of
+// 16-byte ones, so every granule is read by an 8-byte load of its own; a granule pair is two loads at offset 0 / 8 from the same
+// address register, returned as (value, tag, value, tag).  The two granules of a pair MAY come from different moments - the poll then
+// repeats.  (Round 5 read pairs with one 16-byte load: DESIGN_HISTORY.md, profiles/r06_granule_loads_ab.txt.)
+// A lane's granule loads of one poll are ONE asm statement: all loads issued, then one wait - the compiler must not touch a
+// destination between its load and the wait (an untracked load's register is stale until then), hence early-clobber outputs.
 #define NM_GL2(D, A, OFF) "global_load_dwordx2 " D ", " A ", off offset:" OFF " sc1\n\t"
 __device__ __forceinline__ f32x4 gran_join(const nm_f32x2& lo, const nm_f32x2& hi) { return f32x4{lo[0], lo[1], hi[0], hi[1]}; }
 __device__ __forceinline__ void gran_ld_2q1(const nm_gran* p0, const nm_gran* p1, const nm_gran* s0, f32x4& a0, f32x4& a1, nm_f32x2& b0) {
@@ -770,33 +757,6 @@ __device__ __forceinline__ void gran_ld_5q(const nm_gran* p0, const nm_gran* p1,
                  : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4) : "memory");
     a0 = gran_join(t0, t1); a1 = gran_join(t2, t3); a2 = gran_join(t4, t5); a3 = gran_join(t6, t7); a4 = gran_join(t8, t9);
 }
-#else
-__device__ __forceinline__ void gran_ld_5q(const nm_gran* p0, const nm_gran* p1, const nm_gran* p2, const nm_gran* p3, const nm_gran* p4,
-                                           f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4) {
-    asm volatile("global_load_dwordx4 %0, %5, off sc1\n\tglobal_load_dwordx4 %1, %6, off sc1\n\tglobal_load_dwordx4 %2, %7, off sc1\n\t"
-                 "global_load_dwordx4 %3, %8, off sc1\n\tglobal_load_dwordx4 %4, %9, off sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4) : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4) : "memory");
-}
-__device__ __forceinline__ void gran_ld_2q1(const nm_gran* p0, const nm_gran* p1, const nm_gran* s0, f32x4& a0, f32x4& a1, nm_f32x2& b0) {
-    asm volatile("global_load_dwordx4 %0, %3, off sc1\n\tglobal_load_dwordx4 %1, %4, off sc1\n\tglobal_load_dwordx2 %2, %5, off sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(b0) : "v"(p0), "v"(p1), "v"(s0) : "memory");
-}
-__device__ __forceinline__ void gran_ld_4q1(const nm_gran* p0, const nm_gran* p1, const nm_gran* p2, const nm_gran* p3, const nm_gran* s0,
-                                            f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, nm_f32x2& b0) {
-    asm volatile("global_load_dwordx4 %0, %5, off sc1\n\tglobal_load_dwordx4 %1, %6, off sc1\n\tglobal_load_dwordx4 %2, %7, off sc1\n\t"
-                 "global_load_dwordx4 %3, %8, off sc1\n\tglobal_load_dwordx2 %4, %9, off sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0) : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(s0) : "memory");
-}
-__device__ __forceinline__ void gran_ld_4q4(const nm_gran* p0, const nm_gran* p1, const nm_gran* p2, const nm_gran* p3, const nm_gran* s0,
-                                            const nm_gran* s1, const nm_gran* s2, const nm_gran* s3, f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3,
-                                            nm_f32x2& b0, nm_f32x2& b1, nm_f32x2& b2, nm_f32x2& b3) {
-    asm volatile("global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %9, off sc1\n\tglobal_load_dwordx4 %2, %10, off sc1\n\t"
-                 "global_load_dwordx4 %3, %11, off sc1\n\tglobal_load_dwordx2 %4, %12, off sc1\n\tglobal_load_dwordx2 %5, %13, off sc1\n\t"
-                 "global_load_dwordx2 %6, %14, off sc1\n\tglobal_load_dwordx2 %7, %15, off sc1\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3)
-                 : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(s0), "v"(s1), "v"(s2), "v"(s3) : "memory");
-}
-#endif
 // polls until `ok` holds in every lane of the wave (the body re-issues the lane's loads and re-evaluates ok); false: aborted
 #define NM_CHAIN_POLL(LOADS, OKEXPR)                                                                                  \
     {                                                                                                                \
@@ -1271,7 +1231,7 @@ __global__ __launch_bounds__(NM_CHAIN_T) void vrnn_prior_chain_kernel(ChainArgs 
 // one nearest to the detected keypoints is kept.  Roles (512 threads each, one workgroup per CU, all resident):
 //   * NM_CHAIN_NW worker workgroups: wave gw owns h-phase row gw (one of prior0 | post0 | root0_h | joint0_h, 128 rows each; the
 //     post0 rows also take the detected keypoints' 4K columns) and W_hh rows gw + 512 i, and GRU unit j = gw;
-//   * S x B sample workgroups: workgroup (s, b) = vrnn_post_mid_kernel's phases for sample s of clip b (posterior parameters from
+//   * S x B sample workgroups: workgroup (s, b) = vrnn_prior_mid_kernel's phases for sample s of clip b (posterior parameters from
 //     hid_post[b], z = mu + eps[t][s][b] sigma, decoder hidden layers, heads, kinematics, squared distance to the observation); it
 //     publishes its keypoints | latent and LAST its distance as granules, then polls the clip's S distances itself: the nearest sample
 //     (lowest index on ties: fk_kernel's scan) writes the step's outputs - keypoints, latent, rotations, index, distance - from its
@@ -1692,197 +1652,6 @@ __global__ __launch_bounds__(NM_CHAIN_T) void vrnn_post_chain_kernel(PostChainAr
     }
 }
 
-// ---- posterior step of encode (inference), middle phases: one workgroup per (sample, batch element) ---------------------------------
-// NOT the default (NM355_VRNN_POSTMID=1 selects it; parity-tested): measured against the six-launch step once the row kernels had
-// been fixed (pick_nb), it loses - encode alone 52.6 us per timestep against 40.7, and in the forward +0.4 ms: a 1024-thread,
-// 128-register workgroup only starts on a completely free CU, so beside the decoder's persistent convolutions it advances at their
-// kernel boundaries only (8 of 16 steps done when the decoder ends, against 11), and the two device-scope fences of the selection
-// write back / invalidate the L2 (40 us per launch in the forward's tail).  Kept as the measured alternative of BASELINE's "one
-// kernel per timestep".
-// hsvrnn_bvh.py:86-135: S posterior samples per clip and timestep, each decoded to keypoints; the sample nearest to the detected
-// keypoints is kept.  Here the step is three launches like a prior step of the rollout: h-phase, THIS kernel, GRU.  Workgroup (s, b) is vrnn_prior_mid_kernel with
-// the posterior's distribution (post2 on hid_post[b]) and noise eps[s][b], plus the squared distance of its keypoints to the
-// observation; the sample-0 workgroup of a clip also evaluates the prior's parameters and the KL term.  The LAST workgroup of a
-// clip to finish (device-scope counter behind a release fence; acquire fence before it reads the others' results) picks the
-// nearest sample - lowest index on ties, fk_kernel's scan - and copies its keypoints / latent / rotations to the step's outputs.
-// Arithmetic per row, the kinematic chain, the distance sum (joint order) and the KL reduction tree are fk_kernel's and the row
-// kernels': the fused step is bit-identical to the six-launch step (tests/test_network_gpu.py).
-struct PostArgs {
-    const float *hid_post, *hid_prior, *rh, *jh, *eps, *offset, *obs; int ldobs;     // [B][128] x4, (S,B,Z), [B][K][3], [B][ldobs]
-    const float *w_q2, *b_q2, *w_p2, *b_p2, *w_root0, *w_joint0, *w_root2, *b_root2, *w_joint2, *b_joint2;
-    const int32_t *parents, *lvl_joint, *lvl_start; int nlevels;
-    float *zall, *kpall, *rall, *dall;          // per (s, b): [S*B][Z], [S*B][128], [S*B][9K], [S*B]
-    int32_t* counter;                           // [B], zero between launches
-    float* out_kp; int ldkp; float* out_z; int ldz; float* out_R; int ldR; int32_t* best; int ldbest; float* kl; float* rec; int ldstat;
-    int B, S, K, Z, H;
-};
-
-__global__ __launch_bounds__(1024) void vrnn_post_mid_kernel(PostArgs a) {
-    __shared__ __attribute__((aligned(16))) float s_z[128], s_hr[128], s_hj[128], s_root[36], s_rot[192], s_mu[128], s_sg[128];
-    __shared__ float s_Rl[32 * 9], s_Rg[32 * 9], s_pos[32 * 3], s_dk[32], s_red[256];
-    __shared__ int s_last, s_best;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
-    const int sb = blockIdx.x, b = sb % a.B, smp = sb / a.B;
-    const int K = a.K, Z = a.Z, H = a.H, R0 = 3 + K, J6 = 6 * K, rows_c = R0 + J6;
-    f32x4 wa[MID_PAIRS], wb[MID_PAIRS], wc[MID_PAIRS];
-#pragma unroll
-    for (int u = 0; u < MID_PAIRS; ++u) {
-        const int p = wave * MID_PAIRS + u;
-        wa[u] = *reinterpret_cast<const f32x4*>(a.w_q2 + (size_t)(p + half * Z) * 128 + l32 * 4);
-        wb[u] = *reinterpret_cast<const f32x4*>((half ? a.w_joint0 : a.w_root0) + (size_t)p * (H + Z) + H + l32 * 4);
-        const int r = min(p * 2 + half, rows_c - 1);
-        const float* pc = r < R0 ? a.w_root2 + (size_t)r * 128 : a.w_joint2 + (size_t)(r - R0) * 128;
-        wc[u] = *reinterpret_cast<const f32x4*>(pc + l32 * 4);
-    }
-    const f32x4 xh = *reinterpret_cast<const f32x4*>(a.hid_post + (size_t)b * 128 + l32 * 4);
-    const int pl = wave * MID_PAIRS + (l32 < MID_PAIRS ? l32 : 0);
-    const float bias_a = a.b_q2[pl], bias_a2 = a.b_q2[pl + Z], epsv = a.eps[(size_t)sb * Z + pl];
-    const float add_b = (half ? a.jh : a.rh)[(size_t)b * 128 + pl];
-    const int rl = min(pl * 2 + half, rows_c - 1);
-    const float bias_c = *(rl < R0 ? a.b_root2 + rl : a.b_joint2 + (rl - R0));
-    const float obsv = a.obs[(size_t)b * a.ldobs + min(tid, K * 4 - 1)];
-    __shared__ FkTables tb;
-    fk_tables_load(tb, a.lvl_joint, a.lvl_start, a.parents, a.offset + (size_t)b * K * 3, K, a.nlevels, tid);
-    // ---- A. posterior distribution parameters and this workgroup's sample
-    {
-        float mine = 0.f, other = 0.f;
-#pragma unroll
-        for (int u = 0; u < MID_PAIRS; ++u) {
-            const float v = half_reduce(dot4(wa[u], xh));
-            const float o = nm_sx(v, 32);
-            if (l32 == u) { mine = v; other = o; }
-        }
-        if (!half && l32 < MID_PAIRS) {
-            const int p = wave * MID_PAIRS + l32;
-            const float mu = mine + bias_a, sraw = other + bias_a2;
-            const float sg = softplus(sraw) + 1e-4f;
-            const float z = mu + epsv * sg;
-            s_z[p] = z; s_mu[p] = mu; s_sg[p] = sg;
-            a.zall[(size_t)sb * Z + p] = z;
-        }
-    }
-    __syncthreads();
-    // ---- B. decoder hidden layers
-    {
-        const f32x4 xz = *reinterpret_cast<const f32x4*>(s_z + l32 * 4);
-        float mine = 0.f;
-#pragma unroll
-        for (int u = 0; u < MID_PAIRS; ++u) {
-            const float v = half_reduce(dot4(wb[u], xz));
-            if (l32 == u) mine = v;
-        }
-        if (l32 < MID_PAIRS) (half ? s_hj : s_hr)[wave * MID_PAIRS + l32] = lrelu(mine + add_b, 0.01f);
-    }
-    __syncthreads();
-    // ---- C. heads
-    {
-        const f32x4 xr = *reinterpret_cast<const f32x4*>(s_hr + l32 * 4);
-        const f32x4 xj = *reinterpret_cast<const f32x4*>(s_hj + l32 * 4);
-        float mine = 0.f;
-#pragma unroll
-        for (int u = 0; u < MID_PAIRS; ++u) {
-            const int r = (wave * MID_PAIRS + u) * 2 + half;
-            const float v = half_reduce(dot4(wc[u], r < R0 ? xr : xj));
-            if (l32 == u) mine = v;
-        }
-        if (l32 < MID_PAIRS) {
-            const int r = (wave * MID_PAIRS + l32) * 2 + half;
-            if (r < R0) s_root[r] = tanhf(mine + bias_c);
-            else if (r < rows_c) s_rot[r - R0] = mine + bias_c;
-        }
-    }
-    // (the sample-0 workgroup: the prior's rows into the registers phase A is done with - in flight across D)
-    const bool klwg = smp == 0 && a.kl != nullptr;
-    f32x4 xp = xh;
-    float pb = 0.f, pb2 = 0.f;
-    if (klwg) {
-#pragma unroll
-        for (int u = 0; u < MID_PAIRS; ++u) {
-            const int p = wave * MID_PAIRS + u;
-            wa[u] = *reinterpret_cast<const f32x4*>(a.w_p2 + (size_t)(p + half * Z) * 128 + l32 * 4);
-        }
-        xp = *reinterpret_cast<const f32x4*>(a.hid_prior + (size_t)b * 128 + l32 * 4);
-        pb = a.b_p2[pl]; pb2 = a.b_p2[pl + Z];
-    }
-    __syncthreads();
-    // ---- D. forward kinematics
-    if (tid < K) {
-        const float* p = s_rot + tid * 6;
-        float x0 = p[0], x1 = p[1], x2 = p[2], y0 = p[3], y1 = p[4], y2 = p[5];
-        float nx = sqrtf((x0 * x0 + x1 * x1) + x2 * x2) + 1e-10f;
-        x0 /= nx; x1 /= nx; x2 /= nx;
-        float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-        float nz = sqrtf((z0 * z0 + z1 * z1) + z2 * z2) + 1e-10f;
-        z0 /= nz; z1 /= nz; z2 /= nz;
-        float yy0 = z1 * x2 - z2 * x1, yy1 = z2 * x0 - z0 * x2, yy2 = z0 * x1 - z1 * x0;
-        float* R = s_Rl + tid * 9;
-        R[0] = x0; R[1] = yy0; R[2] = z0; R[3] = x1; R[4] = yy1; R[5] = z1; R[6] = x2; R[7] = yy2; R[8] = z2;
-    }
-    __syncthreads();
-    fk_levels(tb, a.nlevels, s_Rl, s_Rg, s_pos, s_root, 36, K, 1, 0, 0, tid, 1024);
-    // ---- E. this sample's keypoints, rotations, distance to the observation (fk_kernel: per-joint terms, summed in joint order)
-    float kpv = 0.f;
-    if (tid < K * 4) {
-        const int k = tid >> 2, c = tid & 3;
-        kpv = c < 3 ? s_pos[k * 3 + c] : (s_root[3 + k] + 1.0f) * 0.5f;
-        a.kpall[(size_t)sb * 128 + tid] = kpv;
-    }
-    if (tid < K * 9) a.rall[(size_t)sb * 9 * K + tid] = s_Rg[tid];
-    {
-        // u_c = obs - kp per component; lanes 4k .. 4k+3 hold joint k's four: ((u0^2 + u1^2) + u2^2) + u3^2
-        const float u = obsv - kpv, q = u * u;
-        const float q1 = __shfl_down(q, 1), q2 = __shfl_down(q, 2), q3 = __shfl_down(q, 3);
-        if (tid < K * 4 && (tid & 3) == 0) s_dk[tid >> 2] = ((q + q1) + q2) + q3;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float d = 0.f;
-        for (int k = 0; k < K; ++k) d += s_dk[k];
-        a.dall[sb] = d;
-    }
-    // ---- F. sample 0: prior parameters and the KL term (fk_kernel's 256-entry tree)
-    if (klwg) {
-        float mine = 0.f, other = 0.f;
-#pragma unroll
-        for (int u = 0; u < MID_PAIRS; ++u) {
-            const float v = half_reduce(dot4(wa[u], xp));
-            const float o = nm_sx(v, 32);
-            if (l32 == u) { mine = v; other = o; }
-        }
-        if (tid < 256) s_red[tid] = 0.f;
-        __syncthreads();
-        if (!half && l32 < MID_PAIRS) {
-            const int p = wave * MID_PAIRS + l32;
-            const float pmu = mine + pb, psg = softplus(other + pb2) + 1e-4f;
-            const float ratio = s_sg[p] / psg, vr = ratio * ratio, dm = (s_mu[p] - pmu) / psg;
-            s_red[p] = 0.f + 0.5f * (((vr + dm * dm) - 1.0f) - logf(vr));
-        }
-        __syncthreads();
-        for (int st = 128; st > 0; st >>= 1) { if (tid < st) s_red[tid] += s_red[tid + st]; __syncthreads(); }
-        if (tid == 0) a.kl[(size_t)b * a.ldstat] = s_red[0];
-    }
-    // ---- G. the clip's last workgroup selects
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) s_last = atomicAdd(a.counter + b, 1) == a.S - 1 ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (tid == 0) {
-        int bi = 0; float bd = __builtin_nontemporal_load(a.dall + b);
-        for (int i = 1; i < a.S; ++i) { const float d = __builtin_nontemporal_load(a.dall + (size_t)i * a.B + b); if (d < bd) { bd = d; bi = i; } }
-        s_best = bi;
-        if (a.best) a.best[(size_t)b * a.ldbest] = bi;
-        if (a.rec) a.rec[(size_t)b * a.ldstat] = bd;
-        a.counter[b] = 0;
-    }
-    __syncthreads();
-    const size_t src = (size_t)s_best * a.B + b;
-    if (tid < K * 4) a.out_kp[(size_t)b * a.ldkp + tid] = __builtin_nontemporal_load(a.kpall + src * 128 + tid);
-    if (tid < Z) a.out_z[(size_t)b * a.ldz + tid] = __builtin_nontemporal_load(a.zall + src * Z + tid);
-    if (a.out_R && tid < K * 9) a.out_R[(size_t)b * a.ldR + tid] = __builtin_nontemporal_load(a.rall + src * 9 * K + tid);
-}
-
 // get_offset (hsvrnn_bvh.py:236-253): lower median over T of |p_k - p_parent(k)| times unit(offset_param[k])
 __global__ __launch_bounds__(64) void offsets_kernel(const float* __restrict__ kp, const float* __restrict__ offset_param,
                                                      const int32_t* __restrict__ parents, int T, int K, float* __restrict__ out) {
@@ -2173,7 +1942,6 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamItem* __restr
 
 struct StepBufs {
     float *hid_prior, *hid_post, *rh, *jh, *gh, *pmu, *psig, *qmu, *qsig, *z, *hr, *hj, *rootout, *rot;
-    float *rall, *dall;   // vrnn_post_mid_kernel: every sample's global rotations [S*B][9K] and distance to the observation [S*B]
     float* gi;        // [B][3H] input projection of the GRU (large batches only, else null)
 };
 
@@ -2187,18 +1955,16 @@ void add_job(LinJobs& J, const LinearW& L, int col0, const float* xa, int na, in
     J.n++;
 }
 
-// rows per wavefront pass: at most two.  The 4- and 8-row instantiations of the row kernels - meant to amortise a weight row over
-// more batch rows - measure 30 / 22 us per launch (linear_rows / gru_rows, idle device, tools/time_vrnn_rows.py) where the 1- and
-// 2-row ones take 4.8: with the batch split into more workgroups instead, nm_vrnn_gru at B = 4 / 8 / 16 runs 9.3 / 10.0 / 12.6 us
-// instead of 50 / 53 / 64, and a posterior step of encode (B = 4, S = 10) 41 us instead of 95 (NM355_VRNN_NB = 4 / 8 restores them)
-int pick_nb(int batch) {
-    const int cap = nm_ls().vrnn_nb;
-    const int nb = batch >= 8 ? 8 : (batch >= 4 ? 4 : (batch >= 2 ? 2 : 1));
-    return nb < cap ? nb : cap;
+// rows per wavefront pass: at most two.  4- and 8-row instantiations of the row kernels, meant to amortise a weight row over more
+// batch rows, existed until they were measured: 30 / 22 us per launch against 4.8 for the 1- and 2-row ones, so the batch is split
+// into more workgroups instead (DESIGN_HISTORY.md, "Retired VRNN arms").
+int pick_nb(int batch) { return batch >= 2 ? 2 : 1; }
+// launches the <1> or <2> instantiation of a row kernel (256 threads: four rows per workgroup)
+template <typename... P, typename... A>
+void launch_rows(void (*k1)(P...), void (*k2)(P...), int nb, dim3 grid, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(nb == 1 ? k1 : k2, grid, dim3(256), 0, s, args...);
 }
 
-// prior steps of a rollout (nm_ls().vrnn_mid, NM355_VRNN_MID): 1 (default) three dependent launches (h-phase, vrnn_prior_mid_kernel,
-// GRU), 0 six.  A/B: profiles/r03_rollout_ab.txt (tools/time_rollout.py, bit-identical outputs).
 #define NM_GEMM_MIN_BATCH 128
 
 // batches of >= 128 rows take the MFMA GEMM (every input segment of this model is a multiple of 32 columns wide)
@@ -2226,10 +1992,7 @@ int launch_jobs(const LinJobs& J, hipStream_t s) {
     for (int i = 0; i < J.n; ++i) maxb = J.j[i].batch > maxb ? J.j[i].batch : maxb;
     const int nb = pick_nb(maxb);
     dim3 grid((J.start[J.n] + 3) / 4, (maxb + nb - 1) / nb);
-    if (nb == 1) hipLaunchKernelGGL((linear_rows_kernel<1>), grid, dim3(256), 0, s, J);
-    else if (nb == 2) hipLaunchKernelGGL((linear_rows_kernel<2>), grid, dim3(256), 0, s, J);
-    else if (nb == 4) hipLaunchKernelGGL((linear_rows_kernel<4>), grid, dim3(256), 0, s, J);
-    else hipLaunchKernelGGL((linear_rows_kernel<8>), grid, dim3(256), 0, s, J);
+    launch_rows(linear_rows_kernel<1>, linear_rows_kernel<2>, nb, grid, s, J);
     return nm_check_hip(hipGetLastError(), "linear_rows launch");
 }
 
@@ -2249,13 +2012,14 @@ int launch_gru(const float* W_ih, const float* b_ih, const float* xa, int na, in
     }
     const int nb = pick_nb(B);
     dim3 grid((H + 3) / 4, (B + nb - 1) / nb);
-    if (nb == 1) hipLaunchKernelGGL((gru_rows_kernel<1>), grid, dim3(256), 0, s, W_ih, b_ih, xa, na, lda, xb, nb_, ldb, gh, h, ldh, hout, ldo, H, B, tg);
-    else if (nb == 2) hipLaunchKernelGGL((gru_rows_kernel<2>), grid, dim3(256), 0, s, W_ih, b_ih, xa, na, lda, xb, nb_, ldb, gh, h, ldh, hout, ldo, H, B, tg);
-    else if (nb == 4) hipLaunchKernelGGL((gru_rows_kernel<4>), grid, dim3(256), 0, s, W_ih, b_ih, xa, na, lda, xb, nb_, ldb, gh, h, ldh, hout, ldo, H, B, tg);
-    else hipLaunchKernelGGL((gru_rows_kernel<8>), grid, dim3(256), 0, s, W_ih, b_ih, xa, na, lda, xb, nb_, ldb, gh, h, ldh, hout, ldo, H, B, tg);
+    launch_rows(gru_rows_kernel<1>, gru_rows_kernel<2>, nb, grid, s, W_ih, b_ih, xa, na, lda, xb, nb_, ldb, gh, h, ldh, hout, ldo, H, B, tg);
     return nm_check_hip(hipGetLastError(), "gru launch");
 }
 
+// floats alloc_step carves (its callers add the slack for the 256-byte alignment of the pieces)
+size_t step_floats(int B, int S, int K, int Z, int H) {
+    return (size_t)B * (4 * 128 + 3 * H + 4 * Z) + (size_t)S * B * (Z + 256 + 3 + K + 6 * K) + (B >= NM_GEMM_MIN_BATCH ? (size_t)B * 3 * H : 0);
+}
 StepBufs alloc_step(Arena& ws, int B, int S, int K, int Z, int H) {
     StepBufs b;
     b.hid_prior = ws.f((size_t)B * 128); b.hid_post = ws.f((size_t)B * 128); b.rh = ws.f((size_t)B * 128); b.jh = ws.f((size_t)B * 128);
@@ -2263,7 +2027,6 @@ StepBufs alloc_step(Arena& ws, int B, int S, int K, int Z, int H) {
     b.pmu = ws.f((size_t)B * Z); b.psig = ws.f((size_t)B * Z); b.qmu = ws.f((size_t)B * Z); b.qsig = ws.f((size_t)B * Z);
     b.z = ws.f((size_t)S * B * Z); b.hr = ws.f((size_t)S * B * 128); b.hj = ws.f((size_t)S * B * 128);
     b.rootout = ws.f((size_t)S * B * (3 + K)); b.rot = ws.f((size_t)S * B * 6 * K);
-    b.rall = ws.f((size_t)S * B * 9 * K); b.dall = ws.f((size_t)S * B);
     b.gi = B >= NM_GEMM_MIN_BATCH ? ws.f((size_t)B * 3 * H) : nullptr;
     return b;
 }
@@ -2279,6 +2042,16 @@ struct StepIO {
     float* hout; int ldho;
     bool want_prior;                   // also evaluate the prior (encode: KL)
 };
+
+// the middle phases' weights, tree and shape; the data pointers stay null for the caller to set (the chains use none but `offset`)
+MidArgs mid_args(const VrnnW& w, int B, int K, int Z, int H) {
+    MidArgs m = {};
+    m.w_p2 = w.prior2.w; m.b_p2 = w.prior2.b; m.w_root0 = w.root0.w; m.w_joint0 = w.joint0.w;
+    m.w_root2 = w.root2.w; m.b_root2 = w.root2.b; m.w_joint2 = w.joint2.w; m.b_joint2 = w.joint2.b;
+    m.order = w.order; m.parents = w.parents; m.lvl_joint = w.lvl_joint; m.lvl_start = w.lvl_start; m.nlevels = w.nlevels;
+    m.B = B; m.K = K; m.Z = Z; m.H = H;
+    return m;
+}
 
 // one VRNN timestep (posterior best-of-S when io.obs != null, otherwise a single prior sample)
 int vrnn_step(nm_ctx* c, const StepBufs& sb, const StepIO& io, int B, int S) {
@@ -2300,33 +2073,13 @@ int vrnn_step(nm_ctx* c, const StepBufs& sb, const StepIO& io, int B, int S) {
         if ((rc = launch_jobs(J, s))) return rc;
     }
     if (!post && B <= 64 && !io.tape && !io.out_R && !io.best && !io.kl && !io.rec && nm_ls().vrnn_mid && K >= 2 && K <= 32 && Z == 128) {
-        // 2-4 in one workgroup per batch element (prior steps of a rollout): see vrnn_prior_mid_kernel
-        MidArgs a;
+        // 2-4 in one workgroup per batch element (prior steps of a rollout): vrnn_prior_mid_kernel, three dependent launches per step
+        // instead of six (NM355_VRNN_MID=0: six.  A/B: profiles/r03_rollout_ab.txt, tools/time_rollout.py, bit-identical outputs)
+        MidArgs a = mid_args(w, B, K, Z, H);
         a.hid_prior = sb.hid_prior; a.rh = sb.rh; a.jh = sb.jh; a.eps = io.eps; a.offset = io.offset;
-        a.w_p2 = w.prior2.w; a.b_p2 = w.prior2.b; a.w_root0 = w.root0.w; a.w_joint0 = w.joint0.w;
-        a.w_root2 = w.root2.w; a.b_root2 = w.root2.b; a.w_joint2 = w.joint2.w; a.b_joint2 = w.joint2.b;
-        a.order = w.order; a.parents = w.parents; a.lvl_joint = w.lvl_joint; a.lvl_start = w.lvl_start; a.nlevels = w.nlevels;
         a.out_kp = io.out_kp; a.ldkp = io.ldkp; a.out_z = io.out_z; a.ldz = io.ldz;
-        a.B = B; a.K = K; a.Z = Z; a.H = H;
         hipLaunchKernelGGL(vrnn_prior_mid_kernel, dim3(B), dim3(1024), 0, s, a);
         if ((rc = nm_check_hip(hipGetLastError(), "vrnn_prior_mid launch"))) return rc;
-        if (io.hout && (rc = launch_gru(w.w_ih, w.b_ih, io.out_kp, S4, io.ldkp, io.out_z, Z, io.ldz, sb.gh, io.h, io.ldh, io.hout, io.ldho, H, B, s, nullptr, sb.gi))) return rc;
-        return NM_OK;
-    }
-    if (post && !io.tape && nm_ls().vrnn_postmid && c->vrnn_cnt && B <= 256 && (size_t)S * B <= 4096 && K >= 2 && K <= 32 && Z == 128 && io.out_kp && io.out_z) {
-        // 2-4 of a posterior step in one workgroup per (sample, clip), selection by the clip's last workgroup: vrnn_post_mid_kernel
-        PostArgs a;
-        a.hid_post = sb.hid_post; a.hid_prior = sb.hid_prior; a.rh = sb.rh; a.jh = sb.jh; a.eps = io.eps; a.offset = io.offset;
-        a.obs = io.obs; a.ldobs = io.ldobs;
-        a.w_q2 = w.post2.w; a.b_q2 = w.post2.b; a.w_p2 = w.prior2.w; a.b_p2 = w.prior2.b; a.w_root0 = w.root0.w; a.w_joint0 = w.joint0.w;
-        a.w_root2 = w.root2.w; a.b_root2 = w.root2.b; a.w_joint2 = w.joint2.w; a.b_joint2 = w.joint2.b;
-        a.parents = w.parents; a.lvl_joint = w.lvl_joint; a.lvl_start = w.lvl_start; a.nlevels = w.nlevels;
-        a.zall = sb.z; a.kpall = sb.hr; a.rall = sb.rall; a.dall = sb.dall; a.counter = c->vrnn_cnt;
-        a.out_kp = io.out_kp; a.ldkp = io.ldkp; a.out_z = io.out_z; a.ldz = io.ldz; a.out_R = io.out_R; a.ldR = io.ldR;
-        a.best = io.best; a.ldbest = io.ldbest; a.kl = (io.want_prior && io.kl) ? io.kl : nullptr; a.rec = io.rec; a.ldstat = io.ldstat;
-        a.B = B; a.S = S; a.K = K; a.Z = Z; a.H = H;
-        hipLaunchKernelGGL(vrnn_post_mid_kernel, dim3(S * B), dim3(1024), 0, s, a);
-        if ((rc = nm_check_hip(hipGetLastError(), "vrnn_post_mid launch"))) return rc;
         if (io.hout && (rc = launch_gru(w.w_ih, w.b_ih, io.out_kp, S4, io.ldkp, io.out_z, Z, io.ldz, sb.gh, io.h, io.ldh, io.hout, io.ldho, H, B, s, nullptr, sb.gi))) return rc;
         return NM_OK;
     }
@@ -2337,10 +2090,7 @@ int vrnn_step(nm_ctx* c, const StepBufs& sb, const StepIO& io, int B, int S) {
         const int nj = (prior && post) ? 2 : 1;
         const int nb = pick_nb(B);
         dim3 grid((nj * Z + 3) / 4, (B + nb - 1) / nb);
-        if (nb == 1) hipLaunchKernelGGL((dist_rows_kernel<1>), grid, dim3(256), 0, s, first, second, nj, Z, 128, B);
-        else if (nb == 2) hipLaunchKernelGGL((dist_rows_kernel<2>), grid, dim3(256), 0, s, first, second, nj, Z, 128, B);
-        else if (nb == 4) hipLaunchKernelGGL((dist_rows_kernel<4>), grid, dim3(256), 0, s, first, second, nj, Z, 128, B);
-        else hipLaunchKernelGGL((dist_rows_kernel<8>), grid, dim3(256), 0, s, first, second, nj, Z, 128, B);
+        launch_rows(dist_rows_kernel<1>, dist_rows_kernel<2>, nb, grid, s, first, second, nj, Z, 128, B);
         if ((rc = nm_check_hip(hipGetLastError(), "dist_rows launch"))) return rc;
     }
     {   // 3. decoders: z-halves of the first layers (+ shared h-half), then the heads
@@ -2452,16 +2202,50 @@ int nm_vrnn_offsets(nm_ctx* c, const float* keypoints, int32_t B, int32_t T, flo
     return nm_check_hip(hipGetLastError(), "offsets launch");
 } catch (...) { return nm_abi_catch("nm_vrnn_offsets"); }
 
-// ---- host side of vrnn_post_chain_kernel ----------------------------------------------------------------------------------------------
-// Tstat: steps of a launch WITH statistics workgroups (encode: the KL term), 0 for the conditioning steps of generate / rollouts
-static size_t post_chain_granules(int B, int S, int K, int Z, int H, int Tstat) {
-    const size_t nd = ((size_t)S * B + 1) & ~(size_t)1;              // (an even count: the arrays behind it are read in 16-byte granule pairs)
-    return (size_t)B * (3 * 128 + 5 * H) + (size_t)S * B * (4 * K + Z) + 2 * nd + (size_t)2 * (Tstat > 0 ? Tstat : 1) * B * 128;
+// ---- host side of the persistent chains -------------------------------------------------------------------------------------------------
+// A chain's granule buffer is described ONCE, by the function that sets the kernel's granule pointers: it walks the buffer array by
+// array, and the same walk without a buffer (gb null) gives the size to request.  Behind the last array: the abort word, and 16 bytes
+// behind that the one-XCD form's four ctl words - 64 bytes of control words, zeroed with the granules before every launch.
+struct GranWalk {
+    nm_gran* base; size_t n = 0;
+    nm_gran* take(size_t k) { nm_gran* p = base ? base + n : nullptr; n += k; return p; }
+    size_t floats() const { return 2 * n + 64; }                       // scratch to request
+    size_t zero_bytes() const { return n * sizeof(nm_gran) + 64; }      // what a launch zeroes: every granule and the control words
+};
+static GranWalk carve_prior_chain(ChainArgs& a, nm_gran* gb, int B, int K, int Z, int H) {
+    GranWalk g{gb};
+    a.g_hid = g.take((size_t)B * 128); a.g_rh = g.take((size_t)B * 128); a.g_jh = g.take((size_t)B * 128);
+    a.g_gh = g.take((size_t)B * 3 * H); a.g_kpz = g.take((size_t)B * (4 * K + Z));
+    a.g_h[0] = g.take((size_t)B * H); a.g_h[1] = g.take((size_t)B * H);
+    a.abort = reinterpret_cast<unsigned*>(g.take(0));
+    return g;
 }
-static size_t post_chain_gran_floats(int B, int S, int K, int Z, int H, int Tstat) { return 2 * post_chain_granules(B, S, K, Z, H, Tstat) + 64; }
-// Can the chain run: shape limits, and EVERY workgroup resident at once - the kernel's workgroups spin on each other and an ordinary launch
-// does not promise co-residency: workgroups of this shape (512 threads at up to 256 registers, the heads' weights in dynamic LDS) per
-// CU x the device's CUs must cover the NM_CHAIN_NW workers + S B sample + nstat statistics workgroups (asked once per context).
+static size_t prior_chain_gran_floats(int B, int K, int Z, int H) { ChainArgs a; return carve_prior_chain(a, nullptr, B, K, Z, H).floats(); }
+// Tstat: steps of a launch WITH statistics workgroups (encode: the KL term), 0 for the conditioning steps of generate / rollouts
+static GranWalk carve_post_chain(PostChainArgs& a, nm_gran* gb, int B, int S, int K, int Z, int H, int Tstat) {
+    const size_t nd = ((size_t)S * B + 1) & ~(size_t)1;              // (an even count: the arrays behind it are read as granule pairs)
+    const size_t nst = (size_t)(Tstat > 0 ? Tstat : 1) * B * 128;
+    GranWalk g{gb};
+    a.g_hidq = g.take((size_t)B * 128); a.g_rh = g.take((size_t)B * 128); a.g_jh = g.take((size_t)B * 128);
+    a.g_gh = g.take((size_t)B * 3 * H); a.g_kpz = g.take((size_t)S * B * (4 * K + Z));
+    a.g_d[0] = g.take(nd); a.g_d[1] = g.take(nd);
+    a.g_h[0] = g.take((size_t)B * H); a.g_h[1] = g.take((size_t)B * H);
+    a.g_sq = g.take(nst); a.g_hidp = g.take(nst);
+    a.abort = reinterpret_cast<unsigned*>(g.take(0));
+    return g;
+}
+static size_t post_chain_gran_floats(int B, int S, int K, int Z, int H, int Tstat) { PostChainArgs a; return carve_post_chain(a, nullptr, B, S, K, Z, H, Tstat).floats(); }
+// Co-residency: a chain's workgroups spin on each other, so ALL of them must be resident at once - an ordinary launch does not promise
+// that.  Resident workgroups of a chain kernel's shape (NM_CHAIN_T threads at up to 256 registers, the heads' weights of K = 32 joints in
+// dynamic LDS) this context's device can hold: per CU x its CUs (*cus_out); 0 when a query fails.  Asked once per context and chain.
+static int chain_resident_wgs(nm_ctx* c, const void* kernel, int* cus_out) {
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, NM_CHAIN_T, (size_t)(3 + 7 * 32) * 128 * sizeof(float)) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+    if (cus_out) *cus_out = cus;
+    return per_cu * cus;
+}
+// Can the post chain run: shape limits, and room for the NM_CHAIN_NW workers + S B sample + nstat statistics workgroups.
 static bool post_chain_fits(nm_ctx* c, int B, int S, int nstat, int& rc) {
     const int K = c->cfg.nkeypoints, Z = c->cfg.nlatent, H = c->cfg.nhidden;
     rc = NM_OK;
@@ -2469,10 +2253,7 @@ static bool post_chain_fits(nm_ctx* c, int B, int S, int nstat, int& rc) {
     if (nm_ls().post_chain_fits < 0) {
         static NmDeviceOnce attr_set;
         if ((rc = nm_raise_lds_limit(attr_set, 150 * 1024, "hipFuncSetAttribute(vrnn_post_chain)", &vrnn_post_chain_kernel))) return false;
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&vrnn_post_chain_kernel), NM_CHAIN_T, (size_t)(3 + 7 * 32) * 128 * sizeof(float)) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-        nm_ls().post_chain_fits = per_cu * cus;         // resident workgroups the device can hold
+        nm_ls().post_chain_fits = chain_resident_wgs(c, reinterpret_cast<const void*>(&vrnn_post_chain_kernel), nullptr);
     }
     return nm_ls().post_chain_fits >= NM_CHAIN_NW + S * B + nstat;
 }
@@ -2483,37 +2264,24 @@ static int launch_post_chain(nm_ctx* c, const float* obs, int ldobs, const float
                              float* out_kp, int ldkp, float* out_z, int ldz, float* out_R, int ldR, float* out_h, int ldh,
                              int32_t* best, int ldbest, float* kl, float* rec, int ldstat, float* gran) {
     const VrnnW& w = c->vrnn;
-    const int K = c->cfg.nkeypoints, Z = c->cfg.nlatent, H = c->cfg.nhidden, S4 = K * 4;
-    const size_t nd = ((size_t)S * B + 1) & ~(size_t)1;
-    const int Tstat = kl ? T : 0;
-    const size_t ngran = post_chain_granules(B, S, K, Z, H, Tstat), nst = (size_t)(Tstat > 0 ? Tstat : 1) * B * 128;
-    nm_gran* gb = reinterpret_cast<nm_gran*>(gran);
+    const int K = c->cfg.nkeypoints, Z = c->cfg.nlatent, H = c->cfg.nhidden;
     PostChainArgs a;
     a.w_prior0 = w.prior0.w; a.b_prior0 = w.prior0.b; a.w_post0 = w.post0.w; a.b_post0 = w.post0.b;
     a.w_root0 = w.root0.w; a.b_root0 = w.root0.b; a.w_joint0 = w.joint0.w; a.b_joint0 = w.joint0.b;
     a.w_hh = w.w_hh; a.b_hh = w.b_hh; a.w_ih = w.w_ih; a.b_ih = w.b_ih;
     a.w_q2 = w.post2.w; a.b_q2 = w.post2.b; a.w_p2 = w.prior2.w; a.b_p2 = w.prior2.b;
-    MidArgs& m = a.mid;
-    m.hid_prior = m.rh = m.jh = m.eps = nullptr; m.offset = offset;
-    m.w_p2 = w.prior2.w; m.b_p2 = w.prior2.b; m.w_root0 = w.root0.w; m.w_joint0 = w.joint0.w;
-    m.w_root2 = w.root2.w; m.b_root2 = w.root2.b; m.w_joint2 = w.joint2.w; m.b_joint2 = w.joint2.b;
-    m.order = w.order; m.parents = w.parents; m.lvl_joint = w.lvl_joint; m.lvl_start = w.lvl_start; m.nlevels = w.nlevels;
-    m.out_kp = nullptr; m.ldkp = 0; m.out_z = nullptr; m.ldz = 0; m.B = B; m.K = K; m.Z = Z; m.H = H;
+    a.mid = mid_args(w, B, K, Z, H); a.mid.offset = offset;
     a.h0 = w.h0; a.obs = obs; a.ldobs = ldobs; a.eps = eps;
     a.out_kp = out_kp; a.ldkp = ldkp; a.out_z = out_z; a.ldz = ldz; a.out_R = out_R; a.ldR = ldR;
     a.out_h = out_h; a.ldh = ldh; a.best = best; a.ldbest = ldbest; a.kl = kl; a.rec = rec; a.ldstat = ldstat;
-    a.g_hidq = gb; a.g_rh = gb + (size_t)B * 128; a.g_jh = gb + (size_t)2 * B * 128;
-    a.g_gh = gb + (size_t)3 * B * 128; a.g_kpz = a.g_gh + (size_t)B * 3 * H; a.g_d[0] = a.g_kpz + (size_t)S * B * (S4 + Z); a.g_d[1] = a.g_d[0] + nd;
-    a.g_h[0] = a.g_d[1] + nd; a.g_h[1] = a.g_h[0] + (size_t)B * H;
-    a.g_sq = a.g_h[1] + (size_t)B * H; a.g_hidp = a.g_sq + nst;
-    a.abort = reinterpret_cast<unsigned*>(a.g_hidp + nst);
+    const GranWalk g = carve_post_chain(a, reinterpret_cast<nm_gran*>(gran), B, S, K, Z, H, kl ? T : 0);
     a.status = c->nf_flag;
     a.B = B; a.S = S; a.T = T; a.K = K; a.Z = Z; a.H = H; a.nstat = kl ? B : 0;
-    { static const int bo = getenv("NM355_CHAIN_BACKOFF") ? atoi(getenv("NM355_CHAIN_BACKOFF")) : 0; a.backoff = bo; }
+    a.backoff = nm_ls().chain_backoff;
     a.spin_limit = nm_ls().chain_spin > 0 ? nm_ls().chain_spin : NM_CHAIN_SPIN;
     a.stat_delay = nm_ls().chain_stat_delay;
     int rc;
-    if ((rc = nm_check_hip(hipMemsetAsync(gb, 0, ngran * sizeof(nm_gran) + 64, c->stream), "vrnn post chain: granule buffers"))) return rc;
+    if ((rc = nm_check_hip(hipMemsetAsync(gran, 0, g.zero_bytes(), c->stream), "vrnn post chain: granule buffers"))) return rc;
     const int drop = std::min(std::max(nm_ls().chain_drop, 0), B);          // (NM355_CHAIN_DROP_WG, test hook: see rollout_steps)
     hipLaunchKernelGGL(vrnn_post_chain_kernel, dim3(NM_CHAIN_NW + a.nstat + S * B - drop), dim3(NM_CHAIN_T), (size_t)(3 + 7 * K) * 128 * sizeof(float), c->stream, a);
     return nm_check_hip(hipGetLastError(), "vrnn_post_chain launch");
@@ -2528,8 +2296,8 @@ static int encode_impl(nm_ctx* c, const float* keypoints, const float* eps, int3
     }
     if ((rc = max_fk_lds(c, S))) return rc;
     const int K = c->cfg.nkeypoints, Z = c->cfg.nlatent, H = c->cfg.nhidden, S4 = K * 4;
-    size_t need = ((size_t)B * (4 * 128 + 6 * H + 4 * Z + K * 3 + 2 * T) + (size_t)S * B * (Z + 256 + 3 + K + 6 * K + 9 * K + 1)) * sizeof(float) + 64 * 256 +
-                  ((size_t)B * (4 * 128 + 5 * H) + (size_t)S * B * (S4 + Z + 1)) * sizeof(nm_gran) + 4096;          // (+ the posterior chain's granule buffers)
+    // the step's scratch, offsets, kl | rec, the posterior chain's granule buffers; 256-byte alignment of the ~20 pieces
+    size_t need = (step_floats(B, S, K, Z, H) + (size_t)B * (K * 3 + 2 * T) + post_chain_gran_floats(B, S, K, Z, H, T)) * sizeof(float) + 64 * 256;
     if ((rc = nm_ctx_reserve(c, need))) return rc;
     c->ws.release(0);
     StepBufs sb = alloc_step(c->ws, B, S, K, Z, H);
@@ -2541,10 +2309,11 @@ static int encode_impl(nm_ctx* c, const float* keypoints, const float* eps, int3
     if ((rc = nm_vrnn_offsets(c, keypoints, B, T, offset))) return rc;
     hipLaunchKernelGGL(broadcast_rows_kernel, dim3((H * B + 255) / 256), dim3(256), 0, c->stream, c->vrnn.h0, H, h, (T + 1) * H, B);
     // The T posterior steps as ONE persistent launch (vrnn_post_chain_kernel) when the shape allows and every workgroup of it can be
-    // resident.  Stand-alone encode only (NM355_VRNN_POST_CHAIN: 0 off, 1 default, 2 also inside nm_forward_fused): beside the decoder's
-    // one-workgroup-per-CU persistent convolutions the chain's ~100 spinning workgroups take their CUs for the whole encode, where the
-    // launch-per-phase steps run in the gaps for free (A/B: profiles/r05_encode_ab.txt: +0.17 ms per forward step).  The training forward
-    // keeps the launches (it fills the tape).
+    // resident.  NM355_VRNN_POST_CHAIN: 0 off; 1 a stand-alone encode only; 2 (default since round 6) inside nm_forward_fused too.
+    // Beside the decoder's one-workgroup-per-CU persistent convolutions the chain's ~100 spinning workgroups take their CUs for the
+    // whole encode, where the launch-per-phase steps run in the gaps: +0.03 ... 0.13 ms per forward step for 148 instead of 238 launches
+    // (profiles/r06_forward_ab.txt; round 5 measured +0.17 ms, profiles/r05_encode_ab.txt).  The training forward keeps the launches
+    // (it fills the tape).
     const int pc = nm_ls().vrnn_post_chain;
     bool chain = !train && pc && (pc >= 2 || !c->in_fused) && post_chain_fits(c, B, S, B, rc);
     if (rc) return rc;
@@ -2812,9 +2581,9 @@ extern "C" {
 
 static size_t rollout_floats(int B, int Tcond, int Ttot, int S, int K, int Z, int H) {
     const size_t S4 = (size_t)K * 4, Tg = Ttot - Tcond;
-    return (size_t)B * (4 * 128 + 3 * H + 4 * Z) + (size_t)S * B * (Z + 256 + 3 + K + 6 * K + 9 * K + 1) + (B >= NM_GEMM_MIN_BATCH ? (size_t)B * 3 * H : 0)
+    return step_floats(B, S, K, Z, H)
          + (size_t)B * Tcond * S4 * 2 + (size_t)Tcond * S * B * Z + Tg * B * Z + (size_t)B * Tg * S4 + (size_t)B * K * 3 + 3 * (size_t)B * H + (size_t)B * Z
-         + 2 * (size_t)B * (3 * 128 + 3 * H + S4 + Z + 2 * H) + 64 + 64 * 36          // (256-byte alignment of each of the ~32 pieces)
+         + prior_chain_gran_floats(B, K, Z, H) + 64 * 36          // (256-byte alignment of each of the ~30 pieces)
          + (size_t)B * Tcond * Z + (size_t)B * (Tcond + 1) * H + post_chain_gran_floats(B, S, K, Z, H, 0);
 }
 static RolloutBufs carve_rollout(Arena& ws, int B, int Tcond, int Ttot, int S, int K, int Z, int H) {
@@ -2825,7 +2594,7 @@ static RolloutBufs carve_rollout(Arena& ws, int B, int Tcond, int Ttot, int S, i
     r.out_cond = ws.f((size_t)B * Tcond * S4 + 1); r.out_gen = ws.f((size_t)B * Tg * S4 + 1);
     r.h_in = ws.f((size_t)B * H); r.offset = ws.f((size_t)B * K * 3);
     r.hbuf[0] = ws.f((size_t)B * H); r.hbuf[1] = ws.f((size_t)B * H); r.zbuf = ws.f((size_t)B * Z);
-    r.chain_g = ws.f(2 * (size_t)B * (3 * 128 + 3 * H + S4 + Z + 2 * H) + 64);
+    r.chain_g = ws.f(prior_chain_gran_floats(B, K, Z, H));
     r.pc_z = ws.f((size_t)B * Tcond * Z + 1); r.pc_h = ws.f((size_t)B * (Tcond + 1) * H); r.pc_g = ws.f(post_chain_gran_floats(B, S, K, Z, H, 0));
     return r;
 }
@@ -2843,8 +2612,8 @@ static int rollout_steps(nm_ctx* c, RolloutBufs& r, int kind, int B, int Tcond, 
         h = r.hbuf[0]; nxt = 1;
     }
     // the prior steps as ONE persistent launch (vrnn_prior_chain_kernel) when the shape allows: weights register-resident for the whole
-    // chain, three counter hand-offs per step instead of three launches (NM355_VRNN_CHAIN=0: the launch-per-phase steps, A/B)
-    bool chain = nm_ls().vrnn_chain && nm_ls().vrnn_mid && Tg >= 1 && B <= 4 && K >= 2 && K <= 32 && Z == 128 && H == 512 && c->vrnn_cnt && c->nf_flag;
+    // chain, three granule hand-offs per step instead of three launches (NM355_VRNN_CHAIN=0: the launch-per-phase steps, A/B)
+    bool chain = nm_ls().vrnn_chain && nm_ls().vrnn_mid && Tg >= 1 && B <= 4 && K >= 2 && K <= 32 && Z == 128 && H == 512 && c->nf_flag;
     const size_t chain_lds = (size_t)(3 + 7 * K) * 128 * sizeof(float);
     // the conditioning (posterior) steps of generate as ONE persistent launch too (vrnn_post_chain_kernel without statistics workgroups:
     // generate evaluates no prior during conditioning, hsvrnn_bvh.py:171-202): a whole HSVRNNBVH.generate is then two kernels
@@ -2860,19 +2629,13 @@ static int rollout_steps(nm_ctx* c, RolloutBufs& r, int kind, int B, int Tcond, 
     }
     if (rc) return rc;
     if (chain) {
-        // Co-residency: the kernel's workgroups spin on each other, so ALL of them must be resident at once - an ordinary launch does not
-        // promise that.  Asked once per context: workgroups of this shape (512 threads at up to 256 registers, the heads' weights in
-        // dynamic LDS) per CU x the device's CUs must cover the NM_CHAIN_NW workers + 4 middle workgroups; a partition with fewer CUs
-        // (CPX mode: 32) takes the launch-per-phase steps.  A device that is busy with OTHER work when the chain starts is what the
-        // bounded spins are for: the time-out is reported by the next call and switches the chain off for this context (nm_nf_poll).
+        // Co-residency (chain_resident_wgs): room for the NM_CHAIN_NW workers + 4 middle workgroups; a partition with fewer CUs (CPX
+        // mode: 32) takes the launch-per-phase steps.  A device that is busy with OTHER work when the chain starts is what the bounded
+        // spins are for: the time-out is reported by the next call and switches the chain off for this context (nm_nf_poll).
         if (nm_ls().chain_fits < 0) {
             static NmDeviceOnce attr_set;
             if ((rc = nm_raise_lds_limit(attr_set, 140 * 1024, "hipFuncSetAttribute(vrnn_prior_chain)", &vrnn_prior_chain_kernel<false>, &vrnn_prior_chain_kernel<true>))) return rc;
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&vrnn_prior_chain_kernel<false>), NM_CHAIN_T, (size_t)(3 + 7 * 32) * 128 * sizeof(float)) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-            nm_ls().chain_fits = ((long long)per_cu * cus >= NM_CHAIN_NW + 4) ? 1 : 0;
-            nm_ls().chain_cus = cus;
+            nm_ls().chain_fits = chain_resident_wgs(c, reinterpret_cast<const void*>(&vrnn_prior_chain_kernel<false>), &nm_ls().chain_cus) >= NM_CHAIN_NW + 4 ? 1 : 0;
         }
         chain = nm_ls().chain_fits == 1;
     }
@@ -2895,28 +2658,17 @@ static int rollout_steps(nm_ctx* c, RolloutBufs& r, int kind, int B, int Tcond, 
         ChainArgs a;
         a.w_prior0 = w.prior0.w; a.b_prior0 = w.prior0.b; a.w_root0 = w.root0.w; a.b_root0 = w.root0.b; a.w_joint0 = w.joint0.w; a.b_joint0 = w.joint0.b;
         a.w_hh = w.w_hh; a.b_hh = w.b_hh; a.w_ih = w.w_ih; a.b_ih = w.b_ih;
-        MidArgs& m = a.mid;
-        m.hid_prior = m.rh = m.jh = m.eps = nullptr; m.offset = r.offset;
-        m.w_p2 = w.prior2.w; m.b_p2 = w.prior2.b; m.w_root0 = w.root0.w; m.w_joint0 = w.joint0.w;
-        m.w_root2 = w.root2.w; m.b_root2 = w.root2.b; m.w_joint2 = w.joint2.w; m.b_joint2 = w.joint2.b;
-        m.order = w.order; m.parents = w.parents; m.lvl_joint = w.lvl_joint; m.lvl_start = w.lvl_start; m.nlevels = w.nlevels;
-        m.out_kp = nullptr; m.ldkp = 0; m.out_z = nullptr; m.ldz = 0; m.B = B; m.K = K; m.Z = Z; m.H = H;
+        a.mid = mid_args(w, B, K, Z, H); a.mid.offset = r.offset;
         a.h0 = h; a.ldh0 = H; a.eps = r.eps_prior; a.out_kp = r.out_gen; a.ldkp = Tg * S4;
         a.h_out = r.hbuf[nxt];
-        // granule buffers: [hid | rh | jh : B x 128 each][gh : B x 3H][kpz : B x (4K + Z)][h0 | h1 : B x H each][abort word]
-        nm_gran* gb = reinterpret_cast<nm_gran*>(r.chain_g);
-        a.g_hid = gb; a.g_rh = gb + (size_t)B * 128; a.g_jh = gb + (size_t)2 * B * 128; a.g_gh = gb + (size_t)3 * B * 128;
-        a.g_kpz = a.g_gh + (size_t)B * 3 * H; a.g_h[0] = a.g_kpz + (size_t)B * (S4 + Z); a.g_h[1] = a.g_h[0] + (size_t)B * H;
-        a.abort = reinterpret_cast<unsigned*>(a.g_h[1] + (size_t)B * H);
+        const GranWalk g = carve_prior_chain(a, reinterpret_cast<nm_gran*>(r.chain_g), B, K, Z, H);
         a.ctl = nullptr; a.stamps = g_chain_stamps;
         a.status = c->nf_flag;
         a.B = B; a.T = Tg; a.K = K; a.Z = Z; a.H = H;
-        // poll back-off in s_sleep(2) units (0 / 1 / 4 / 16 / 64: 17.0 / 18.0 / 17.3 / 19.5 / 25.9 us per step at B = 1)
-        { static const int bo = getenv("NM355_CHAIN_BACKOFF") ? atoi(getenv("NM355_CHAIN_BACKOFF")) : 0; a.backoff = bo; }
+        a.backoff = nm_ls().chain_backoff;
         a.spin_limit = nm_ls().chain_spin > 0 ? nm_ls().chain_spin : NM_CHAIN_SPIN;
         a.wg_poll = nm_ls().chain_wgpoll; a.force_nogo = nm_ls().chain_xcd_nogo;
-        const size_t gbytes = (size_t)B * (3 * 128 + 3 * H + S4 + Z + 2 * H) * sizeof(nm_gran) + 64;
-        if ((rc = nm_check_hip(hipMemsetAsync(r.chain_g, 0, gbytes, c->stream), "rollout: granule buffers"))) return rc;
+        if ((rc = nm_check_hip(hipMemsetAsync(r.chain_g, 0, g.zero_bytes(), c->stream), "rollout: granule buffers"))) return rc;
         // (NM355_CHAIN_DROP_WG, test hook: the last workgroups are not launched - what a workgroup that never becomes resident looks like
         //  to the others; their spins run into the limit, the abort word ends the kernel, bit 1 of the status word reports it)
         const int drop = std::min(std::max(nm_ls().chain_drop, 0), B);
@@ -3020,7 +2772,7 @@ static int rollout_impl(nm_ctx* c, int kind, const float* kp_cond, const float* 
     RolloutBufs r;
     r.sb = alloc_step(c->ws, B, S, K, Z, H);
     r.hbuf[0] = c->ws.f((size_t)B * H); r.hbuf[1] = c->ws.f((size_t)B * H); r.zbuf = c->ws.f((size_t)B * Z);
-    r.chain_g = c->ws.f(2 * (size_t)B * (3 * 128 + 3 * H + K * 4 + Z + 2 * H) + 64);
+    r.chain_g = c->ws.f(prior_chain_gran_floats(B, K, Z, H));
     if (kind == 0) { r.pc_z = c->ws.f((size_t)B * Tcond * Z + 1); r.pc_h = c->ws.f((size_t)B * (Tcond + 1) * H); r.pc_g = c->ws.f(post_chain_gran_floats(B, S, K, Z, H, 0)); }
     r.offset = kind == 0 ? c->ws.f((size_t)B * K * 3) : const_cast<float*>(offset_in);
     if (c->ws.overflow) { nm_set_error("vrnn rollout: workspace overflow"); return NM_ERR_STATE; }
@@ -3064,7 +2816,7 @@ int nm_vrnn_step(nm_ctx* c, int32_t posterior, const float* h_in, const float* k
     if (!posterior) S = 1;
     if ((rc = max_fk_lds(c, S))) return rc;
     const int K = c->cfg.nkeypoints, Z = c->cfg.nlatent, H = c->cfg.nhidden, S4 = K * 4;
-    size_t need = ((size_t)B * (4 * 128 + 6 * H + 4 * Z) + (size_t)S * B * (Z + 256 + 3 + K + 6 * K + 9 * K + 1)) * sizeof(float) + 64 * 256;
+    size_t need = step_floats(B, S, K, Z, H) * sizeof(float) + 64 * 256;
     if ((rc = nm_ctx_reserve(c, need))) return rc;
     c->ws.release(0);
     StepBufs sb = alloc_step(c->ws, B, S, K, Z, H);

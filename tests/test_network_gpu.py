@@ -1151,12 +1151,9 @@ def test_fused_hourglass_core_runs_at_this_grid(G):
 
 
 
-@pytest.mark.parametrize("env", [{"NM355_VRNN_POSTMID": "1"}, {"NM355_VRNN_NB": "8"}, {"NM355_VRNN_MID": "0"}],
-                         ids=["posterior-mid-kernel", "rows-per-pass-8", "six-launch-prior-step"])
+@pytest.mark.parametrize("env", [{"NM355_VRNN_MID": "0"}], ids=["six-launch-prior-step"])
 def test_vrnn_kernel_variants_stay_under_parity(env, golden_dir):
-    """The VRNN's A/B partners: posterior steps as three launches (vrnn_post_mid_kernel: measured slower than the six-launch step and not
-    the default), the 4- / 8-row instantiations of the row kernels (6x slower per launch than the 1- / 2-row ones, the
-    default since round 3) and prior steps as six launches.  Under the switch, the VRNN parity tests run again on fresh contexts
+    """The VRNN's A/B partner: prior steps as six launches.  Under the switch, the VRNN parity tests run again on fresh contexts
     (reference fixture G2 with exact best-of-10 indices, G4 generation, the rollouts, the submodule callables, the generation driver)."""
     with _switches(env):
         test_g2_vrnn_unit_parity_on_reference_keypoints(golden_dir)

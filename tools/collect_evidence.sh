@@ -45,12 +45,10 @@ python3 tools/pmc_mfma.py $(find $E/pm -name "*.db" | head -1) $E/${R}_pmc_mfma.
 TBCMD="python3 bench.py --workload train --conv-mode bf16 --steps 2 --warmup 1 --no-extras --no-cpu-baseline"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $E/pmb -- $TBCMD > $E/pmb.log 2>&1
 python3 tools/pmc_mfma.py $(find $E/pmb -name "*.db" | head -1) $E/${R}_pmc_mfma_train_bf16.json > $E/pmc_mfma_train_bf16_summary.txt 2>&1
-# same-call A/Bs of the round (r06): MFMA shape of conv_up2c, hand-off latency by placement / store flavour, granule loads of the persistent
-# chains (needs libnm355_x4.so: make -C neural_marionette_amd/csrc x4), the rollout chain's forms + where a step's time goes, encode,
-# forward-step switches, R processes on one GPU
+# same-call A/Bs of the round (r06): MFMA shape of conv_up2c, hand-off latency by placement / store flavour, the rollout chain's forms +
+# where a step's time goes, encode, forward-step switches, R processes on one GPU
 bash tools/ab_mfma_shape.sh 7 > $E/${R}_mfma_shape_ab.txt 2>&1
 (hipcc -O3 -w --offload-arch=gfx950 tools/calib/hop_latency.hip -o /tmp/hop_latency && timeout 120 /tmp/hop_latency) > $E/${R}_hop_latency.txt 2>&1
-if [ -f neural_marionette_amd/libnm355_x4.so ]; then bash tools/ab_granule_loads.sh 2>&1 | grep -v amdgpu.ids > $E/${R}_granule_loads_ab.txt; fi
 # conv_f16p2's deferred epilogue (built, slower, opt-in) against the shipped exposed one; in-kernel stamps of both (libnm355_stamps.so: make stamps)
 { bash tools/ab_p2_defer.sh; if [ -f neural_marionette_amd/libnm355_stamps.so ]; then for D in 0 1; do echo "in-kernel stamps, NM355_P2_DEFER=$D (tools/diag_f16p2_steps.py):"; NM355_P2_DEFER=$D python3 tools/diag_f16p2_steps.py 2>&1 | grep -v amdgpu.ids | head -5; done; fi; } > $E/${R}_p2_defer_ab.txt 2>&1
 {
