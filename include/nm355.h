@@ -461,6 +461,66 @@ int nm_skeleton_draw(nm_ctx* ctx, const float* keypoints, const int32_t* parents
                      const double* bone_color, double light_a, double light_b, const double* background, int32_t overlay, int32_t* index,
                      double* depth, uint8_t* image);
 
+/* ---- Loop subdivision and smooth vertex normals of posed meshes (vis_retarget.py:416-423, :497-512: temp_mesh.subdivide_loop(
+ * arg.subdivide_iter) and compute_vertex_normals() on every frame, in open3d on the host), and the mesh shaded with those normals ----
+ * This is NOT open3d's result: open3d numbers the new vertices in traversal order and sums unit face normals unweighted.  The result is
+ * defined by this text alone, in float64, unfused, in exactly this operation order (tests/subdiv_ref.py restates it).  The topology is a
+ * PLAN of index tables, built once per mesh on the host (neural_marionette_amd/subdivide.py, LoopPlan.build); the device applies them
+ * per frame.  All tables are int32 on the device but w, which is float64; they are shared by all frames.
+ *
+ * PLAN, one level: V vertices, triangles (M,3) with every index in [0, V), no triangle with a repeated index, no undirected edge in more
+ * than two triangles (LoopPlan.build refuses the rest).
+ *   edges      the E undirected edges {a < b}, sorted by (a, b); edge e creates vertex V + e.  edge (E,4) = a, b, c, d: c and d are the
+ *     vertices opposite the edge in its triangles, in ascending triangle-row order; d = -1 marks a boundary edge (one triangle).
+ *   children   parent row m = (i, j, k) with the edge vertices p = ev(i,j), q = ev(j,k), r = ev(k,i) gives the rows 4m .. 4m+3 =
+ *     (i,p,r) (p,j,q) (r,q,k) (p,q,r): the winding is kept.  The next level is built from these rows over V + E vertices.
+ *   rings      ring_offsets (V+1), ring (ring_len), w (V,2) = (w_self, w_ring).  A vertex with no boundary edge and n >= 1 edges: its n
+ *     neighbours in ascending order, w_ring = beta_n = (0.625 - (0.375 + 0.25 cos(2 pi / n))^2) / n (C's cos, float64, on the host),
+ *     w_self = 1 - n beta_n.  A vertex with exactly two boundary edges: those two neighbours in ascending order, (0.75, 0.125).  Any
+ *     other vertex (unreferenced, or a bow-tie with another number of boundary edges): an empty list and (1, 0) - it stays where it is.
+ *     The weights are plan data; the device only multiplies by them.
+ *   finest level only   triangles (M,3), and the vertex -> triangle index face_offsets (V+1), faces (3 M): each vertex's triangle rows,
+ *     ascending.
+ * nm_subdiv_apply - one level for T frames: in (T,V,3) float64 -> out (T,V+E,3) float64 (posed points, or any three values per vertex
+ *   such as colours), per frame and component x:
+ *     row v < V (old vertex)     s = 0.0; for j = ring_offsets[v] .. ring_offsets[v+1] - 1 in that order: s = s + x[ring[j]];
+ *                                out = w_self * x[v] + w_ring * s
+ *     row V + e, d >= 0          out = 0.375 * (x[a] + x[b]) + 0.125 * (x[c] + x[d])
+ *     row V + e, d == -1         out = 0.5 * (x[a] + x[b])
+ *   The tables are judged on the device, nothing is read through a bad entry: a, b, c or a ring entry outside [0, V), d outside [0, V)
+ *   other than -1, ring_offsets[v] < 0, ring_offsets[v+1] > ring_len or ring_offsets[v] > ring_offsets[v+1].  A row with a bad entry is
+ *   quiet NaN in every frame and component; bad_rows (1) int32 on the device receives the number of such rows (each once, whatever T) -
+ *   every call writes it, 0 for a plan of LoopPlan.build.  edge may be NULL with E == 0, ring with ring_len == 0.
+ * nm_vertex_normals - vertices (F,V,3) float64 -> normals (F,V,3) float64, per frame and vertex:  acc = (0, 0, 0);  for each triangle
+ *   row m of faces[face_offsets[v] .. face_offsets[v+1]) in that order, with its vertices p0 p1 p2 in the row's order (whichever of
+ *   them v is): e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2 by the MESH formula above, acc = acc + c componentwise;
+ *   r = sqrt((acc_x acc_x + acc_y acc_y) + acc_z acc_z);  normal = acc / r componentwise, or (0, 0, 0) where r is 0 or not finite.  The
+ *   cross product has twice the triangle's area for its length: the normal is AREA-WEIGHTED on purpose (open3d's is not), so a sliver
+ *   does not turn the normal of a vertex it touches.  Bad entries - an offset pair as above with 3 M for ring_len, a faces entry outside
+ *   [0, M), a vertex of such a triangle outside [0, V) - make the vertex's row quiet NaN in every frame and count once in bad_rows.
+ *   triangles and faces may be NULL with M == 0 (every normal is zero).
+ * nm_mesh_shade - a deferred pass over index (F,H,W) as nm_mesh_draw wrote it from the same rec (nm_mesh_bin's, F M rows of 16 with iz at
+ *   entries 10 .. 12), camera, triangles and vertices: image (F,H,W,3) uint8 is written again with SMOOTH shading from normals (F,V,3)
+ *   float64 (nm_vertex_normals' rows, world space).  For a pixel with winner m >= 0:  a_k, b_k, w_k from the record exactly as MESH
+ *   coverage does;  l_k = w_k * iz_k, L = (l_0 + l_1) + l_2;  each vertex normal in camera space n'_r = (E[r,0] n_x + E[r,1] n_y) + E[r,2] n_z;
+ *   h_r = ((l_0 n'_0,r + l_1 n'_1,r) + l_2 n'_2,r) / L;  shade = light_a + light_b * |h . d| / (sqrt(h . h) * sqrt(A)); where h . h is 0 or
+ *   not finite the MESH shade of the record's flat n.  Colour (vertex_colors (V,3) or `color`) and the uint8 conversion as in the draw;
+ *   pixels with index -1 take `background` - as do, judged on the device, pixels whose index lies outside [0, M) or whose triangle has a
+ *   vertex outside [0, V).  nm_mesh_draw and its results are untouched: draw with image NULL, then shade.
+ * All three are stream-ordered, synchronise nothing (but for the workspace's first growth: nm_subdiv_apply and nm_vertex_normals keep one
+ * int32 per workgroup there) and need no weights.  No atomic of any kind is used: every output row is written by the one lane that owns it
+ * and bad_rows by a single-workgroup sum, so results are bit-identical from run to run.  Arguments are judged before any launch.
+ * NM_ERR_ARG: null ctx, in / ring_offsets / w / out / vertices / face_offsets / normals / bad_rows / index / image / camera, null edge with
+ * E > 0, ring with ring_len > 0, triangles / faces / rec / normals with M > 0, T, F, V, width, height < 1, E, ring_len, M < 0, the camera
+ * numbers as for nm_mesh_draw; NM_ERR_UNSUPPORTED: V + E >= 2^31, 3 M >= 2^31, F M >= 2^31, F height width >= 2^31. */
+int nm_subdiv_apply(nm_ctx* ctx, const double* in, int32_t T, int32_t V, int32_t E, const int32_t* edge, const int32_t* ring_offsets,
+                    const int32_t* ring, int32_t ring_len, const double* w, double* out, int32_t* bad_rows);
+int nm_vertex_normals(nm_ctx* ctx, const double* vertices, int32_t F, int32_t V, const int32_t* triangles, int64_t M,
+                      const int32_t* face_offsets, const int32_t* faces, double* normals, int32_t* bad_rows);
+int nm_mesh_shade(nm_ctx* ctx, const double* rec, const int32_t* index, const int32_t* triangles, const double* normals,
+                  const double* vertex_colors, const double* color, int32_t F, int32_t V, int64_t M, const nm_camera* camera, double light_a,
+                  double light_b, const double* background, uint8_t* image);
+
 /* Evaluation metrics (utils/eval_utils.py).
  * nm_eval_voxel_chamfer — voxel_chamfer_distance :29-55 for every frame of a batch: gt_vox, recon (B,T,1,G,G,G) fp32 on the
  *   device (gt occupied = non-zero, recon occupied = value >= 0.5; neither is modified), per_frame (B*T) fp64 out =

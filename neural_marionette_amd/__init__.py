@@ -9,5 +9,6 @@ skeleton builder and synthetic data generators.  No CPU / PyTorch fallback exist
 from .spec import HotPathOptions, param_spec, param_count, DETECTOR_LOSS_KEYS  # noqa: F401
 from .modules import NeuralMarionette, KyptDetector, HSVRNNBVH  # noqa: F401
 from .render import PinholeCamera  # noqa: F401
+from .subdivide import LoopPlan  # noqa: F401
 
-__all__ = ["NeuralMarionette", "KyptDetector", "HSVRNNBVH", "HotPathOptions", "param_spec", "param_count", "PinholeCamera"]
+__all__ = ["NeuralMarionette", "KyptDetector", "HSVRNNBVH", "HotPathOptions", "param_spec", "param_count", "PinholeCamera", "LoopPlan"]

@@ -84,6 +84,10 @@ SIGNATURES = {
                                C.POINTER(C.c_double), C.c_int64, _P, _P, _P, _P]),
     "nm_skeleton_draw": (C.c_int, [C.c_void_p, _P, _P, _I, _I, C.POINTER(NmCamera), C.c_double, C.c_double, C.c_double, _P, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double), _I, _P, _P, _P]),
+    "nm_subdiv_apply": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "nm_vertex_normals": (C.c_int, [C.c_void_p, _P, _I, _I, _P, C.c_int64, _P, _P, _P, _P]),
+    "nm_mesh_shade": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _P, C.POINTER(C.c_double), _I, _I, C.c_int64, C.POINTER(NmCamera), C.c_double, C.c_double,
+                                C.POINTER(C.c_double), _P]),
     "nm_eval_voxel_chamfer": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P]),
     "nm_eval_semantic": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _P, _P]),
     "nm_vrnn_set_tree": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),

@@ -19,6 +19,7 @@
 //              (nm_tiles.h) gives the tile offsets; nm_mesh_draw's fill pass writes the record rows into the tile lists
 //   draw       a workgroup per tile, a thread per pixel: the tile's triangles go through LDS NM_MESH_CHUNK at a time, every thread keeps
 //              its own (s, row) minimum in registers, fetches the winner's vertex colours and writes its pixel once
+//   shade      (nm_mesh_shade, optional) a thread per pixel shades the winner in `index` again, with interpolated vertex normals
 // The skeleton is one launch, a workgroup per tile: its first K threads transform the frame's joints and bones into LDS (at most 32
 // spheres and 31 bones), then every thread tests its pixel against those whose rectangle holds it.
 #include "nm_ctx.h"
@@ -221,6 +222,67 @@ __global__ __launch_bounds__(NM_RENDER_BLOCK) void mesh_draw_kernel(const double
             for (int ch = 0; ch < 3; ++ch) im[ch] = mesh_byte(c[ch] * shade);
         }
     }
+}
+
+// The deferred smooth-shading pass.  grid ceil(F H W / 256), a thread per pixel: the winner mesh_draw_kernel left in index is shaded again
+// with the perspective-correct mix of its three vertex normals (nm_vertex_normals' rows) instead of the record's flat n.  a_k, b_k, w_k, l_k
+// and L are recomputed from the record exactly as the draw computes them, so the colour mix is the draw's to the bit.  An index outside
+// [0, M) or a winner with a vertex outside [0, V) takes the background: nothing is read through either.
+__global__ __launch_bounds__(NM_RENDER_BLOCK) void mesh_shade_kernel(const double* __restrict__ rec, const int* __restrict__ index, const int* __restrict__ triangles,
+                                                                      const double* __restrict__ normals, const double* __restrict__ vertex_colors, int V,
+                                                                      long long M, long long pixels, RenderCam cam, MeshShade sh, unsigned char* __restrict__ image) {
+    const long long o = (long long)blockIdx.x * NM_RENDER_BLOCK + threadIdx.x;
+    if (o >= pixels) return;
+    const long long hw = (long long)cam.H * cam.W;
+    const long long f = o / hw, rem = o - f * hw;
+    const int py = (int)(rem / cam.W), px = (int)(rem - (long long)py * cam.W);
+    unsigned char* im = image + (size_t)o * 3;
+    const long long m = index[o];
+    int t0 = -1, t1 = -1, t2 = -1;
+    if (m >= 0 && m < M) { const int* tri = triangles + (size_t)m * 3; t0 = tri[0]; t1 = tri[1]; t2 = tri[2]; }
+    if (!(t0 >= 0 && t0 < V && t1 >= 0 && t1 < V && t2 >= 0 && t2 < V)) {
+        im[0] = (unsigned char)sh.bg[0]; im[1] = (unsigned char)sh.bg[1]; im[2] = (unsigned char)sh.bg[2];
+        return;
+    }
+    const double dx = ((double)px - cam.cx) / cam.fx, dy = ((double)py - cam.cy) / cam.fy;
+    const double* r = rec + ((size_t)f * (size_t)M + (size_t)m) * NM_MESH_REC;
+    const double a0 = r[0] - dx, b0 = r[1] - dy, a1 = r[2] - dx, b1 = r[3] - dy, a2 = r[4] - dx, b2 = r[5] - dy;
+    const double w0 = a1 * b2 - b1 * a2, w1 = a2 * b0 - b2 * a0, w2 = a0 * b1 - b0 * a1;
+    const double l0 = w0 * r[10], l1 = w1 * r[11], l2 = w2 * r[12];
+    const double L = (l0 + l1) + l2;
+    const double A = (dx * dx + dy * dy) + 1.0;
+    const double* n0 = normals + ((size_t)f * (size_t)V + (size_t)t0) * 3;
+    const double* n1 = normals + ((size_t)f * (size_t)V + (size_t)t1) * 3;
+    const double* n2 = normals + ((size_t)f * (size_t)V + (size_t)t2) * 3;
+    double h[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {                                    // n' = (E[k,0] n_x + E[k,1] n_y) + E[k,2] n_z: a direction, no translation
+        const double* e = cam.e + 4 * k;
+        const double c0 = (e[0] * n0[0] + e[1] * n0[1]) + e[2] * n0[2];
+        const double c1 = (e[0] * n1[0] + e[1] * n1[1]) + e[2] * n1[2];
+        const double c2 = (e[0] * n2[0] + e[1] * n2[1]) + e[2] * n2[2];
+        h[k] = ((l0 * c0 + l1 * c1) + l2 * c2) / L;
+    }
+    const double hh = (h[0] * h[0] + h[1] * h[1]) + h[2] * h[2];
+    double shade;
+    if (hh == 0.0 || !isfinite(hh)) {                                // no usable normal there: the draw's flat shade
+        const double den = (r[6] * dx + r[7] * dy) + r[8];
+        const double nn = (r[6] * r[6] + r[7] * r[7]) + r[8] * r[8];
+        shade = sh.light_a + sh.light_b * fabs(den) / (sqrt(nn) * sqrt(A));
+    } else {
+        const double hd = (h[0] * dx + h[1] * dy) + h[2];
+        shade = sh.light_a + sh.light_b * fabs(hd) / (sqrt(hh) * sqrt(A));
+    }
+    double c[3] = {sh.color[0], sh.color[1], sh.color[2]};
+    if (vertex_colors) {
+        const double* c0 = vertex_colors + (size_t)t0 * 3;
+        const double* c1 = vertex_colors + (size_t)t1 * 3;
+        const double* c2 = vertex_colors + (size_t)t2 * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) c[ch] = ((l0 * c0[ch] + l1 * c1[ch]) + l2 * c2[ch]) / L;
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) im[ch] = mesh_byte(c[ch] * shade);
 }
 
 // ---- skeleton ------------------------------------------------------------------------------------------------------------------------
@@ -506,6 +568,28 @@ int nm_mesh_draw(nm_ctx* c, const double* rec, const int32_t* rect, const int64_
                        (const int*)list, (long long)M, rows, rows > 0 ? (long long)capacity : 0ll, cam, sh, (int*)index, depth, (unsigned char*)image);
     return nm_check_hip(hipGetLastError(), "mesh_draw launch");
 } catch (...) { return nm_abi_catch("nm_mesh_draw"); }
+
+int nm_mesh_shade(nm_ctx* c, const double* rec, const int32_t* index, const int32_t* triangles, const double* normals, const double* vertex_colors,
+                  const double* color, int32_t F, int32_t V, int64_t M, const nm_camera* camera, double light_a, double light_b, const double* background,
+                  uint8_t* image) try { NmScope nm_scope_(c);
+    RenderCam cam;
+    long long nt = 0;
+    int rc = mesh_check("mesh_shade", c, F, camera, &cam, &nt);
+    if (rc) return rc;
+    if ((rc = mesh_sizes("mesh_shade", F, V, M))) return rc;
+    if (!index || !image || (M > 0 && (!rec || !triangles || !normals))) { nm_set_error("mesh_shade: null argument"); return NM_ERR_ARG; }
+    if ((rc = nm_check_hip(hipSetDevice(c->cfg.device), "hipSetDevice"))) return rc;
+    const double white[3] = {1.0, 1.0, 1.0}, grey[3] = {0.7, 0.7, 0.7};
+    const double* bg = background ? background : white;
+    const double* uc = color ? color : grey;
+    MeshShade sh;
+    sh.light_a = light_a; sh.light_b = light_b;
+    for (int k = 0; k < 3; ++k) { sh.color[k] = uc[k]; sh.bg[k] = mesh_host_byte(bg[k]); }
+    const long long pixels = (long long)F * cam.H * cam.W;
+    hipLaunchKernelGGL(mesh_shade_kernel, dim3((unsigned)((pixels + NM_RENDER_BLOCK - 1) / NM_RENDER_BLOCK)), dim3(NM_RENDER_BLOCK), 0, c->stream, rec,
+                       (const int*)index, (const int*)triangles, normals, vertex_colors, (int)V, (long long)M, pixels, cam, sh, (unsigned char*)image);
+    return nm_check_hip(hipGetLastError(), "mesh_shade launch");
+} catch (...) { return nm_abi_catch("nm_mesh_shade"); }
 
 int nm_skeleton_draw(nm_ctx* c, const float* keypoints, const int32_t* parents, int32_t F, int32_t K, const nm_camera* camera, double threshold,
                      double radius, double bone_radius, const double* joint_colors, const double* joint_color, const double* bone_color, double light_a,

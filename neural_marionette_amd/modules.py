@@ -33,6 +33,7 @@ from torch import nn
 
 from . import _lib, holders
 from .skeleton import build_skeleton
+from .subdivide import LoopPlan
 from .spec import DETECTOR_LOSS_KEYS, FEAT_DIM, HotPathOptions, param_spec
 
 Priority = namedtuple("Priority", ["values", "indices"])   # what torch.topk returns in the reference
@@ -42,6 +43,7 @@ CONV_MODES = {"fp32": 0, "0": 0, "exact": 0, "split16": 1, "1": 1, "f16": 3, "3"
 NM_ERR_RANGE = -5
 CONV_MODE_NAMES = ("split16", "fp32", "f16", "bf16", "auto")
 MESH_RECORD_BYTES = 512 << 20   # render_mesh draws its frames in groups whose triangle records (144 bytes per frame and triangle) stay under this
+SUBDIV_BYTES = 512 << 20        # subdivide and render_retarget work on groups of frames whose intermediate levels / fine meshes stay under this
 
 
 class Engine:
@@ -1117,6 +1119,78 @@ class NeuralMarionette(nn.Module):
             out["points"] = pts
         return out
 
+    def _plan_values(self, who, values, plan, count, name="values"):
+        """values (T,count,3) or (count,3) float64 on the network's device and a LoopPlan there -> the 3-d tensor, whether it was 2-d"""
+        if not isinstance(plan, LoopPlan):
+            raise ValueError(f"{who}: plan must be a neural_marionette_amd.LoopPlan, got {type(plan).__name__}")
+        if not isinstance(values, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a tensor, got {type(values).__name__}")
+        flat = values.dim() == 2
+        v3 = values[None] if flat else values
+        n = plan.vertex_counts[count]
+        if values.dtype != torch.float64 or v3.dim() != 3 or tuple(v3.shape[1:]) != (n, 3) or v3.shape[0] < 1:
+            raise ValueError(f"{who}: {name} must be (T,{n},3) or ({n},3) float64 with T >= 1, got {tuple(values.shape)} {values.dtype}")
+        if not values.is_cuda or not values.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous on the network's device, got {values.device}")
+        dev = self._engine._device()
+        if values.device != dev or plan.device != dev:
+            raise ValueError(f"{who}: {name} and the plan must be on the network's device ({dev}), got {values.device} and {plan.device}")
+        return v3, flat
+
+    @torch.no_grad()
+    def subdivide(self, values, plan, bytes_bound: Optional[int] = None):
+        """Device version of vis_retarget.py's ``temp_mesh.subdivide_loop(arg.subdivide_iter)`` (:416-423, :497-512: open3d, on the host,
+        every frame): ``plan.levels`` Loop subdivisions of ``values`` (T,V,3) or (V,3) float64 - sample_retarget's posed ``points``, or
+        the vertex colours, which the script's mesh carries through the same stencils - by ``plan`` (LoopPlan.build(triangles, V,
+        levels), built once per mesh).  nm_subdiv_apply per level (csrc/nm_subdiv.hip).  **Not open3d's vertex order**: the contract is
+        include/nm355.h's, tests/subdiv_ref.py restates it.  Returns (T,V_L,3), or (V_L,3) for (V,3) values; the matching triangles are
+        ``plan.triangles``.  The frames go in groups whose intermediate levels stay under ``bytes_bound`` (SUBDIV_BYTES = 512 MiB by
+        default; a single frame past the bound goes alone); the result does not depend on the grouping.  Never synchronises, no atomics:
+        results are bit-identical from run to run."""
+        who = "subdivide"
+        v3, flat = self._plan_values(who, values, plan, 0)
+        bound = SUBDIV_BYTES if bytes_bound is None else int(bytes_bound)
+        if bound < 1:
+            raise ValueError(f"{who}: bytes_bound must be >= 1, got {bytes_bound}")
+        if plan.levels == 0:
+            return values.clone()
+        eng = self._engine
+        dev = eng._device()
+        eng.ready()
+        T, counts = int(v3.shape[0]), plan.vertex_counts
+        out = torch.empty(T, counts[-1], 3, device=dev, dtype=torch.float64)
+        bad = torch.empty(1, device=dev, dtype=torch.int32)
+        group = max(1, min(T, bound // max(1, 24 * sum(counts[1:-1]))))
+        mid = [torch.empty(group, n, 3, device=dev, dtype=torch.float64) for n in counts[1:-1]]
+        null = lambda t: t.data_ptr() if t.numel() else None
+        for f0 in range(0, T, group):
+            n = min(group, T - f0)
+            src = v3[f0:]
+            for level, tab in enumerate(plan.levels_tables):
+                dst = out[f0:] if level == plan.levels - 1 else mid[level]
+                eng.call("nm_subdiv_apply", src.data_ptr(), n, counts[level], int(tab["edge"].shape[0]), null(tab["edge"]), tab["ring_offsets"].data_ptr(),
+                         null(tab["ring"]), int(tab["ring"].numel()), tab["w"].data_ptr(), dst.data_ptr(), bad.data_ptr())
+                src = dst
+        return out[0] if flat else out
+
+    @torch.no_grad()
+    def vertex_normals(self, vertices, plan):
+        """Device version of open3d's ``compute_vertex_normals()`` as vis_retarget.py calls it per frame (:421, :510): smooth unit normals
+        (F,V_L,3) float64 of ``vertices`` (F,V_L,3) or (V_L,3) float64 over ``plan.triangles`` - the finest level of ``plan``, or the
+        mesh itself for a plan of 0 levels (nm_vertex_normals, csrc/nm_subdiv.hip).  **Not open3d's normals**: each is the sum of its
+        triangles' cross products in ascending row order, so AREA-WEIGHTED, divided by its length; a vertex whose sum is zero (no
+        triangle, or degenerate ones only) or not finite gets (0, 0, 0).  Contract: include/nm355.h; tests/subdiv_ref.py restates it."""
+        who = "vertex_normals"
+        v3, flat = self._plan_values(who, vertices, plan, -1, "vertices")
+        eng = self._engine
+        eng.ready()
+        out = torch.empty_like(v3)
+        bad = torch.empty(1, device=v3.device, dtype=torch.int32)
+        null = lambda t: t.data_ptr() if t.numel() else None
+        eng.call("nm_vertex_normals", v3.data_ptr(), int(v3.shape[0]), int(v3.shape[1]), null(plan.triangles), int(plan.triangles.shape[0]),
+                 plan.face_offsets.data_ptr(), null(plan.faces), out.data_ptr(), bad.data_ptr())
+        return out[0] if flat else out
+
     @staticmethod
     def _render_numbers(who, camera, light, background, **colors):
         """the arguments render_mesh and render_skeleton share, as floats: (light_a, light_b), background, and each named colour"""
@@ -1135,7 +1209,8 @@ class NeuralMarionette(nn.Module):
 
     @torch.no_grad()
     def render_mesh(self, vertices, triangles, camera, vertex_colors=None, color=(0.7, 0.7, 0.7), light=(0.3, 0.7), background=(1.0, 1.0, 1.0),
-                    bin_capacity=None, return_index: bool = False, return_depth: bool = False, record_bytes: Optional[int] = None):
+                    bin_capacity=None, return_index: bool = False, return_depth: bool = False, record_bytes: Optional[int] = None,
+                    vertex_normals=None):
         """Device version of vis_retarget.py's mesh images (:400-430, :497-512: a TriangleMesh per frame into open3d's off-screen
         visualiser): the triangles ``triangles`` (M,3) int32 over the posed ``vertices`` (F,V,3) float64 - sample_retarget's ``points``
         - drawn through ``camera`` (render.PinholeCamera), the nearest triangle winning each pixel (nm_mesh_bin + nm_mesh_draw,
@@ -1145,7 +1220,11 @@ class NeuralMarionette(nn.Module):
         is culled WHOLE (no clipping), as are triangles with an index outside the vertices or a non-finite vertex; of equal depths the
         lower row wins.  The pixel is the perspective-correct mix of the winner's ``vertex_colors`` (V,3) float64 - or ``color`` without
         them - times light[0] + light[1] * |cos(face normal, ray)|, clamped to [0, 1] (NaN: 0) and truncated to uint8; light (1, 0)
-        leaves the colours flat.  Loop subdivision, textures and smooth vertex normals are the caller's.
+        leaves the colours flat.  With ``vertex_normals`` (F,V,3) float64 - NeuralMarionette.vertex_normals' rows - the cosine is taken
+        with the perspective-correct mix of the winner's three vertex normals instead (smooth shading, the script's ``smooth_imgs``): each
+        group of frames draws index and depth, then nm_mesh_shade writes the image; index and depth are the flat call's, and a pixel
+        whose mixed normal is zero or not finite keeps the flat shade.  None is the flat path, bit for bit as before.  Loop subdivision
+        is NeuralMarionette.subdivide (render_retarget does both per group of frames); textures are the caller's.
         The records take 144 bytes per frame and triangle, so the frames are drawn in groups whose records stay under
         ``record_bytes`` (MESH_RECORD_BYTES = 512 MiB by default; a single frame past the bound is drawn alone).  The result does not
         depend on the grouping.
@@ -1178,6 +1257,11 @@ class NeuralMarionette(nn.Module):
         if H * W >= 2 ** 31 or M >= 2 ** 31:
             raise ValueError(f"{who}: {W} x {H} pixels and {M} triangles, one frame indexes fewer than 2^31 of either")
         tensors = [("vertices", vertices), ("triangles", triangles)] + ([("vertex_colors", vertex_colors)] if vertex_colors is not None else [])
+        if vertex_normals is not None:
+            if not isinstance(vertex_normals, torch.Tensor) or vertex_normals.dtype != torch.float64 or tuple(vertex_normals.shape) != (F, V, 3):
+                raise ValueError(f"{who}: vertex_normals must be a ({F},{V},3) float64 tensor, got "
+                                 f"{(tuple(vertex_normals.shape), vertex_normals.dtype) if isinstance(vertex_normals, torch.Tensor) else type(vertex_normals).__name__}")
+            tensors.append(("vertex_normals", vertex_normals))
         for name, t in tensors:
             if not t.is_cuda or not t.is_contiguous():
                 raise ValueError(f"{who}: {name} must be contiguous on the network's device, got {t.device}")
@@ -1201,6 +1285,10 @@ class NeuralMarionette(nn.Module):
         null = lambda t: t.data_ptr() if t is not None and t.numel() else None
         part = lambda t, f0: t[f0:].data_ptr() if t is not None else None
         lst = torch.empty(int(bin_capacity), device=dev, dtype=torch.int32) if bin_capacity is not None else None
+        smooth = vertex_normals is not None
+        index = out.get("index")
+        if smooth and index is None:
+            index = torch.empty(F, H, W, device=dev, dtype=torch.int32)     # the shade pass reads the winners
         for f0 in range(0, F, group):
             n = min(group, F - f0)
             last = tile_offsets[n * TX * TY]
@@ -1210,7 +1298,11 @@ class NeuralMarionette(nn.Module):
             out["bin_total"] += last
             eng.call("nm_mesh_draw", null(rec), null(rect), tile_offsets.data_ptr(), null(triangles), null(vertex_colors), (C.c_double * 3)(*num["color"]),
                      n, V, M, C.byref(cam), light_a, light_b, (C.c_double * 3)(*num["background"]), int(lst.numel()), null(lst),
-                     part(out.get("index"), f0), part(out.get("depth"), f0), out["image"][f0:].data_ptr())
+                     part(index, f0), part(out.get("depth"), f0), None if smooth else out["image"][f0:].data_ptr())
+            if smooth:
+                eng.call("nm_mesh_shade", null(rec), index[f0:].data_ptr(), null(triangles), vertex_normals[f0:].data_ptr() if M else None, null(vertex_colors),
+                         (C.c_double * 3)(*num["color"]), n, V, M, C.byref(cam), light_a, light_b, (C.c_double * 3)(*num["background"]),
+                         out["image"][f0:].data_ptr())
         return out
 
     @torch.no_grad()
@@ -1287,12 +1379,20 @@ class NeuralMarionette(nn.Module):
     @torch.no_grad()
     def render_retarget(self, result, triangles, camera, skin_colors: bool = False, joint_colors=None, parents=None, threshold=0.2, radius=0.03,
                         bone_radius=0.03, color=(0.7, 0.7, 0.7), joint_color=(0.7, 0.1, 0.0), bone_color=(0.0, 0.6, 0.1), light=(0.3, 0.7),
-                        background=(1.0, 1.0, 1.0), record_bytes: Optional[int] = None):
+                        background=(1.0, 1.0, 1.0), record_bytes: Optional[int] = None, subdivide: int = 0, smooth: bool = False, plan=None):
         """vis_retarget.py's loop :497-553 from sample_retarget's dict ``result``: per frame the posed mesh (``triangles`` (M,3) int32 over
         result['points']), the skeleton of the retargeted keypoints, the skeleton of the source keypoints, and the first pasted over
         the mesh - render_mesh and render_skeleton, which see.  ``parents`` defaults to the learner's tree as sample_retarget left it.
         skin_colors=True colours the mesh as :415 does, vertex_colors = skin_weights @ joint_colors with ``joint_colors`` (K,3) - a
         torch matmul on the device; the spheres take ``joint_color`` either way, as in the script's loop.
+        ``subdivide`` = n > 0 is the script's ``subdivide_loop(arg.subdivide_iter)`` (:418, :507; 3 there): the points - and the skin
+        colours, as :416-423 - go through n Loop subdivisions (NeuralMarionette.subdivide) by ``plan``, or by a LoopPlan built here from
+        ``triangles`` (host work and one copy of the triangles to the host: pass a plan to call this more than once per mesh; a plan's
+        levels must equal ``subdivide``).  ``smooth`` = True is its ``compute_vertex_normals()`` (:421, :510): the mesh and the overlay are
+        shaded with NeuralMarionette.vertex_normals of the (subdivided) mesh, render_mesh's ``vertex_normals``.  Both work on groups of
+        frames whose fine points and normals stay under SUBDIV_BYTES, so the fine mesh of all frames never exists at once; the result
+        does not depend on the grouping and equals composing the four calls by hand.  The defaults are the unsubdivided, flat-shaded
+        images, bit for bit as before.
         Returns a dict of (T,H,W,3) uint8 images: mesh, skeleton, source_skeleton, overlay."""
         who = "render_retarget"
         if not isinstance(result, dict) or any(k not in result for k in ("points", "keypoints", "source_keypoints", "skin_weights")):
@@ -1311,7 +1411,31 @@ class NeuralMarionette(nn.Module):
             if parents is None:
                 raise ValueError(f"{who}: the learner has no tree yet: pass parents (K)")
         common = dict(light=light, background=background)
-        mesh = self.render_mesh(result["points"], triangles, camera, vertex_colors=vc, color=color, record_bytes=record_bytes, **common)["image"]
+        levels = int(subdivide)
+        if levels < 0:
+            raise ValueError(f"{who}: subdivide must be >= 0, got {subdivide}")
+        if levels == 0 and not smooth:
+            mesh = self.render_mesh(result["points"], triangles, camera, vertex_colors=vc, color=color, record_bytes=record_bytes, **common)["image"]
+        else:
+            points = result["points"]
+            if not isinstance(points, torch.Tensor) or points.dim() != 3:
+                raise ValueError(f"{who}: result['points'] must be a (T,N,3) tensor")
+            if plan is None:
+                plan = LoopPlan.build(triangles, int(points.shape[1]), levels, device=points.device)
+            elif not isinstance(plan, LoopPlan) or plan.levels != levels or plan.V != int(points.shape[1]):
+                raise ValueError(f"{who}: plan must be a LoopPlan of {levels} levels over {int(points.shape[1])} vertices")
+            if vc is not None:
+                vc = self.subdivide(vc, plan)
+            T = int(points.shape[0])
+            per_frame = 24 * (plan.vertex_counts[-1] * (2 if smooth else 1) + sum(plan.vertex_counts[1:-1]))
+            group = max(1, min(T, SUBDIV_BYTES // per_frame))
+            parts = []
+            for f0 in range(0, T, group):
+                fine = self.subdivide(points[f0:f0 + group], plan)
+                normals = self.vertex_normals(fine, plan) if smooth else None
+                parts.append(self.render_mesh(fine, plan.triangles, camera, vertex_colors=vc, color=color, record_bytes=record_bytes, vertex_normals=normals,
+                                              **common)["image"])
+            mesh = parts[0] if len(parts) == 1 else torch.cat(parts)
         skel = dict(threshold=threshold, radius=radius, bone_radius=bone_radius, joint_colors=joint_color, bone_color=bone_color, **common)
         drawn = self.render_skeleton(result["keypoints"], parents, camera, return_index=True, **skel)
         skeleton = drawn["image"]
