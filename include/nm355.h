@@ -265,6 +265,59 @@ int nm_sample_surface(nm_ctx* ctx, const void* vertices, int32_t vertices_f64, c
                       float* points, float* normals, int32_t* face_index, double* uniforms_out, int32_t* counters);
 int nm_sample_tables(nm_ctx* ctx, const void* scratch, int32_t T, int32_t F, double* areas, int64_t* cum);
 
+/* ---- body models: posed meshes and joints from SMPL-form pose streams - what the reference's AIST++ preparation computes on the host
+ * with smplx before it samples the surface (dataset/aistpp/prepare_aistpp.py:54-62: SMPL(...).forward(global_orient, body_pose, transl,
+ * scaling).vertices; :86-89: the joint regressor times the posed vertices, the ground-truth joints of semantic_scores) ----
+ * One model form: linear blend skinning with shape and pose blend shapes.  This is NOT smplx's float32 arithmetic, and the order "scale,
+ * then translate" of the last step is this library's choice: the AIST++ fork of smplx that takes `scaling` is not available to compare
+ * with.  The result is defined by this text alone, in float64, unfused, in exactly this operation order (tests/body_ref.py restates it in
+ * numpy).  A dot product of three terms is (a0 b0 + a1 b1) + a2 b2; a "running sum" starts from the stated value and adds one product at a
+ * time in ascending index order.
+ *
+ * MODEL (neural_marionette_amd/body.py, BodyModel), float64 on the device: V vertices, J <= 64 joints, S >= 0 shape coefficients,
+ * P = 9 (J - 1).  v_template (V,3); shapedirs (V,3,S); posedirs (P, 3V), row p = 9 (j - 1) + 3 a + b for entry (a, b) of joint j >= 1,
+ * column 3 v + c; lbs_weights (V,J); the joint regressor (J,V) as CSR - reg_offsets (J+1) int32, reg_cols (nnz) int32 ascending within a
+ * row, reg_vals (nnz) float64; parents (J) int32 ON THE HOST with parents[0] = -1 and 0 <= parents[j] < j.
+ *   1. shape, once per (model, betas)   v_shaped[v,c] = the running sum from v_template[v,c] of shapedirs[v,c,s] * betas[s];
+ *      J_rest[j,c] = the running sum from 0.0, over row j's CSR entries, of val * v_shaped[col,c].  betas NULL means S = 0.
+ *   2. rotations, per (frame, joint)   given as rotations (T,J,3,3) float64, or computed from poses (T,J,3), float32 (widened exactly)
+ *      or float64, axis-angle r:  e = r + 1e-8 per component;  angle = sqrt((e_x e_x + e_y e_y) + e_z e_z);  u = r / angle per
+ *      component;  s = sin(angle), c = cos(angle);  K = [[0,-u_z,u_y],[u_z,0,-u_x],[-u_y,u_x,0]];  KK_ab = the three-term dot of row a
+ *      and column b of K;  R_ab = (I_ab + s * K_ab) + (1 - c) * KK_ab.  A zero vector gives exactly I.  (smplx's batch_rodrigues as it is
+ *      remembered; it cannot be compared here.)  This is the one stage with sin, cos and a square root, whose last bits are the math
+ *      library's: it is an output, rotations_out (T,J,3,3), so that everything after it can be checked exactly.
+ *   3. chain, per frame, j ascending   Gr_0 = R_0, Gt_0 = J_rest_0;  for j > 0 with p = parents[j]: rel = J_rest_j - J_rest_p;
+ *      Gr_j = Gr_p R_j (three-term dots);  Gt_j = (Gr_p rel) + Gt_p.  Posed joint Jp_j = Gt_j.  Skinning transform A_j = [Ar_j | At_j]
+ *      (3x4): Ar_j = Gr_j, At_j = Gt_j - (Gr_j J_rest_j).
+ *   4. vertices, per (frame, vertex)   off_c = the running sum from 0.0, over p ascending, of (R[j,a,b] - I_ab) * posedirs[p, 3v+c];
+ *      vp = v_shaped + off;  M (3x4) = the running sum from 0.0, over j ascending, of w[v,j] * A_j entry by entry, terms with
+ *      w[v,j] == 0.0 skipped;  x_c = ((M_c0 vp_x + M_c1 vp_y) + M_c2 vp_z) + M_c3;  vertices[t,v,c] = scaling * x_c + transl[t,c]
+ *      (transl (T,3) float64; NULL: no addition).  posed_joints[t,j,c] = scaling * Jp_j,c + transl[t,c].
+ *   5. regressed joints (prepare_aistpp.py:86-89)   joints[t,j,c] = the running sum from 0.0, over row j's CSR entries, of
+ *      val * vertices[t,col,c] - the posed, scaled, translated vertices.
+ * A non-finite pose or rotation poisons its own frame only.  A regressor row with an offset pair outside [0, nnz] or a column outside
+ * [0, V) reads nothing through the bad entry and is quiet NaN (BodyModel builds no such table).
+ * nm_body_shape - step 1: two launches.  reg_cols / reg_vals may be NULL with reg_nnz == 0, shapedirs with S == 0.
+ * nm_body_pose - steps 2 to 4: the rotations (a lane per frame and joint; skipped with `rotations`), the chain (a lane per frame and row of the
+ *   3x4 transforms walking the J joints, its parents' rows in LDS), the vertices.  The vertex kernel: a lane per vertex, 128 vertices a workgroup, NM_BODY_FRAMES = 8 frames per read of
+ *   posedirs, the per-frame sums in registers; the 8 frames' pose features and then their J skinning transforms in LDS, 8 * J * 12 * 8
+ *   bytes (18 432 at J = 24, 49 152 at J = 64).  Exactly one of poses and rotations is given; rotations_out is needed with poses.
+ *   transforms (T,J,3,4) float64 receives the A_j (scratch the caller owns, and an output).  posedirs may be NULL with J == 1.
+ * nm_body_joints - step 5: a lane per (frame, joint, component).
+ * All three are stream-ordered, allocate nothing, synchronise nothing and need no weights.  No atomic of any kind is used: results are
+ * bit-identical from run to run.  Arguments are judged before any launch.  NM_ERR_ARG: null ctx or a null pointer other than those
+ * named optional, T, V, J < 1, J > 64, S < 0, reg_nnz < 0, both or neither of poses / rotations, a parent table that is not topological,
+ * a scaling that is zero or not finite; NM_ERR_UNSUPPORTED: T V, T J, 3 V, 3 T J or the vertex kernel's workgroups >= 2^31. */
+int nm_body_shape(nm_ctx* ctx, const double* v_template, const double* shapedirs, const double* betas, int32_t V, int32_t S, int32_t J,
+                  const int32_t* reg_offsets, const int32_t* reg_cols, const double* reg_vals, int32_t reg_nnz, double* v_shaped,
+                  double* J_rest);
+int nm_body_pose(nm_ctx* ctx, const void* poses, int32_t poses_f64, const double* rotations, int32_t T, int32_t V, int32_t J,
+                 const int32_t* parents_host, const double* v_shaped, const double* J_rest, const double* posedirs,
+                 const double* lbs_weights, const double* transl, double scaling, double* rotations_out, double* transforms,
+                 double* posed_joints, double* vertices);
+int nm_body_joints(nm_ctx* ctx, const double* vertices, int32_t T, int32_t V, int32_t J, const int32_t* reg_offsets,
+                   const int32_t* reg_cols, const double* reg_vals, int32_t reg_nnz, double* joints);
+
 /* Device output path: thresholded voxels to ordered point sets - the host lines every consumer of the decoder's voxels starts with
  * (vis_generation.py:137-170, vis_interpolation.py:141-177, vis/visualize.py:58-59, :130-137): binarise, np.where / torch.where per
  * frame, divide into [-1, 1] coordinates, min_z / max_z of the last coordinate over a clip and the per-point (z - min_z) / z_len.

@@ -10,5 +10,6 @@ from .spec import HotPathOptions, param_spec, param_count, DETECTOR_LOSS_KEYS  #
 from .modules import NeuralMarionette, KyptDetector, HSVRNNBVH  # noqa: F401
 from .render import PinholeCamera  # noqa: F401
 from .subdivide import LoopPlan  # noqa: F401
+from .body import BodyModel  # noqa: F401
 
-__all__ = ["NeuralMarionette", "KyptDetector", "HSVRNNBVH", "HotPathOptions", "param_spec", "param_count", "PinholeCamera", "LoopPlan"]
+__all__ = ["NeuralMarionette", "KyptDetector", "HSVRNNBVH", "HotPathOptions", "param_spec", "param_count", "PinholeCamera", "LoopPlan", "BodyModel"]

@@ -73,6 +73,9 @@ SIGNATURES = {
     "nm_sample_surface_workspace": (C.c_size_t, [_I, _I]),
     "nm_sample_surface": (C.c_int, [C.c_void_p, _P, _I, _P, _I, _I, _I, _I, C.c_int64, C.c_uint64, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "nm_sample_tables": (C.c_int, [C.c_void_p, _P, _I, _I, _P, _P]),
+    "nm_body_shape": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "nm_body_pose": (C.c_int, [C.c_void_p, _P, _I, _P, _I, _I, _I, c_int32_p, _P, _P, _P, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "nm_body_joints": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "nm_occupied_count": (C.c_int, [C.c_void_p, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P]),
     "nm_occupied_write": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _P, _P, _P]),
     "nm_occupied_surface": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P]),

@@ -5,7 +5,8 @@ item.  Here the sequences stay on the device (ClipBank), the host only picks the
 dataset.py:51-68, on the reference's own random stream) and one library call builds the (B,T,1,G,G,G) batch
 (NeuralMarionette.voxelize_batch -> nm_voxelize_batch).  DeviceClipLoader ties the three together for the trainers.
 File I/O is the caller's: ``bank.add(np.load(path)[..., :3])`` for a prepared point sequence, or ``bank.add_mesh(net, vertices,
-triangles)`` for a mesh sequence, which is sampled on the device (NeuralMarionette.sample_surface -> nm_sample_surface).
+triangles)`` for a mesh sequence, which is sampled on the device (NeuralMarionette.sample_surface -> nm_sample_surface), or
+``bank.add_body(net, model, poses)`` for an SMPL-form pose stream, which is posed on the device first (NeuralMarionette.pose_bodies).
 """
 from __future__ import annotations
 
@@ -54,6 +55,18 @@ class ClipBank:
         device (NeuralMarionette.sample_surface) and stores the float32 points - what the reference's prepared ``.npy[..., :3]``
         holds - as a new sequence; returns its id."""
         return self.add(net.sample_surface(vertices, triangles, count=count, seed=seed)["points"], joints)
+
+    def add_body(self, net, model, poses, betas=None, transl=None, scaling: float = 1.0, count: int = 20000, seed: int = 0) -> int:
+        """The reference's AIST++ preparation for one motion sequence (dataset/aistpp/prepare_aistpp.py:54-62, :75-89) on the device:
+        ``model`` (body.BodyModel) posed by ``poses`` (frames,J,3) axis-angle with ``betas`` / ``transl`` / ``scaling``
+        (NeuralMarionette.pose_bodies), ``count`` surface points per frame of the posed meshes over ``model.faces`` (add_mesh), and the
+        regressed joints stored with the sequence as float32 - what ``voxelize_batch(..., return_joints=True)`` and
+        ``eval_utils.semantic_scores`` read for prepared data.  Returns the sequence's id.
+        The whole sequence is posed in one call, there is NO frame grouping: the transient is the float64 vertices, 24 V bytes per frame -
+        about 480 MB for a 2 900-frame sequence at SMPL's 6 890 vertices.  (Posing in groups would be harmless, but the sampler counts
+        its uniforms by the frame's index within a call, so sampling in groups would change the points.)"""
+        out = net.pose_bodies(model, poses=poses, betas=betas, transl=transl, scaling=scaling, return_joints=True)
+        return self.add_mesh(net, out["vertices"], model.faces, count=count, seed=seed, joints=out["joints"].to(torch.float32))
 
     def __len__(self) -> int:
         return len(self.points)

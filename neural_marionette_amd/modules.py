@@ -890,6 +890,90 @@ class NeuralMarionette(nn.Module):
         return out
 
     @torch.no_grad()
+    def pose_bodies(self, model, poses=None, rotations=None, betas=None, transl=None, scaling: float = 1.0, return_joints: bool = True,
+                    dtype=torch.float64):
+        """Device version of the body-model step of the reference's AIST++ preparation (dataset/aistpp/prepare_aistpp.py:54-62: smplx's
+        ``SMPL(...).forward(global_orient, body_pose, transl, scaling).vertices``; :86-89: the joint regressor times the posed vertices):
+        ``model`` (body.BodyModel, on the network's device) posed for T frames - linear blend skinning with shape and pose blend shapes
+        (nm_body_shape / nm_body_pose / nm_body_joints, csrc/nm_body.hip).  **Not smplx's float32 arithmetic**: the result is defined by
+        the contract of include/nm355.h alone, in float64 (tests/body_ref.py restates it), and the order "scale, then translate" is this
+        library's choice.
+        Exactly one of poses (T,J,3) axis-angle, float32 or float64, and rotations (T,J,3,3) float64 is given; betas (S) float32 or float64
+        (None: the template), transl (T,3) float32 or float64 (None: no translation), all contiguous on the network's device; scaling a
+        finite number other than 0.
+        Returns a dict: vertices (T,V,3); rotations (T,J,3,3) float64 - computed from poses (the one stage with sin, cos and a square
+        root), or the tensor given; posed_joints (T,J,3), the kinematic chain's; joints (T,J,3), the regressor over the posed, scaled,
+        translated vertices [return_joints]; v_shaped (V,3) and J_rest (J,3) float64, cached on the model per betas tensor (the tensor
+        object and its version).  dtype=torch.float32 returns rounded copies of vertices, posed_joints and joints.  Never synchronises,
+        no atomics: results are bit-identical from run to run."""
+        from .body import BodyModel
+        who = "pose_bodies"
+        if not isinstance(model, BodyModel):
+            raise ValueError(f"{who}: model must be a neural_marionette_amd.BodyModel, got {type(model).__name__}")
+        if (poses is None) == (rotations is None):
+            raise ValueError(f"{who}: exactly one of poses and rotations is given")
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{who}: dtype must be torch.float32 or torch.float64, got {dtype}")
+        given = [(n, t) for n, t in (("poses", poses), ("rotations", rotations), ("betas", betas), ("transl", transl)) if t is not None]
+        for name, t in given:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        V, J, S = model.V, model.J, model.S
+        if poses is not None and (poses.dtype not in (torch.float32, torch.float64) or poses.dim() != 3 or tuple(poses.shape[1:]) != (J, 3) or poses.shape[0] < 1):
+            raise ValueError(f"{who}: poses must be (T,{J},3) float32 or float64 with T >= 1, got {tuple(poses.shape)} {poses.dtype}")
+        if rotations is not None and (rotations.dtype != torch.float64 or rotations.dim() != 4 or tuple(rotations.shape[1:]) != (J, 3, 3) or rotations.shape[0] < 1):
+            raise ValueError(f"{who}: rotations must be (T,{J},3,3) float64 with T >= 1, got {tuple(rotations.shape)} {rotations.dtype}")
+        T = int((poses if poses is not None else rotations).shape[0])
+        if betas is not None and (betas.dtype not in (torch.float32, torch.float64) or tuple(betas.shape) != (S,)):
+            raise ValueError(f"{who}: betas must be ({S}) float32 or float64, got {tuple(betas.shape)} {betas.dtype}")
+        if transl is not None and (transl.dtype not in (torch.float32, torch.float64) or tuple(transl.shape) != (T, 3)):
+            raise ValueError(f"{who}: transl must be ({T},3) float32 or float64, got {tuple(transl.shape)} {transl.dtype}")
+        if isinstance(scaling, bool) or not isinstance(scaling, (int, float)) or not np.isfinite(scaling) or scaling == 0:
+            raise ValueError(f"{who}: scaling must be a finite number other than 0, got {scaling!r}")
+        if T * V >= 2 ** 31 or T * J * 3 >= 2 ** 31:
+            raise ValueError(f"{who}: {T} frames of {V} vertices and {J} joints, one call indexes fewer than 2^31 rows")
+        for name, t in given:
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"{who}: {name} must be contiguous on the network's device, got {t.device}")
+        eng = self._engine
+        dev = eng._device()
+        for name, t in given + [("model", model.v_template)]:
+            if t.device != dev:
+                raise ValueError(f"{who}: {name} must be on the network's device ({dev}), got {t.device}")
+        eng.ready()
+        null = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)
+        # shape: once per (model, betas tensor)
+        key = None if betas is None or S == 0 else id(betas)
+        hit = model._shape_cache.get(key)
+        if hit is None or (key is not None and (hit[0] is not betas or hit[1] != betas._version)):
+            b64 = None if key is None else betas.to(torch.float64)
+            v_shaped, J_rest = f64(V, 3), f64(J, 3)
+            eng.call("nm_body_shape", model.v_template.data_ptr(), null(model.shapedirs), null(b64), V, S, J, model.reg_offsets.data_ptr(),
+                     null(model.reg_cols), null(model.reg_vals), int(model.reg_cols.numel()), v_shaped.data_ptr(), J_rest.data_ptr())
+            if key is not None:
+                model._shape_cache = {k: h for k, h in model._shape_cache.items() if k is None}     # one betas tensor at a time
+            hit = model._shape_cache[key] = (betas, None if key is None else betas._version, v_shaped, J_rest)
+        v_shaped, J_rest = hit[2], hit[3]
+        t64 = None if transl is None else transl.to(torch.float64)
+        rot_out = f64(T, J, 3, 3) if poses is not None else None
+        transforms, posed, vertices = f64(T, J, 3, 4), f64(T, J, 3), f64(T, V, 3)
+        parents = np.ascontiguousarray(model.parents, dtype=np.int32)
+        eng.call("nm_body_pose", null(poses), int(poses is not None and poses.dtype == torch.float64), null(rotations), T, V, J,
+                 parents.ctypes.data_as(_lib.c_int32_p), v_shaped.data_ptr(), J_rest.data_ptr(), null(model.posedirs), model.lbs_weights.data_ptr(),
+                 null(t64), float(scaling), null(rot_out), transforms.data_ptr(), posed.data_ptr(), vertices.data_ptr())
+        out = dict(vertices=vertices, rotations=rotations if rot_out is None else rot_out, posed_joints=posed, v_shaped=v_shaped, J_rest=J_rest)
+        if return_joints:
+            out["joints"] = f64(T, J, 3)
+            eng.call("nm_body_joints", vertices.data_ptr(), T, V, J, model.reg_offsets.data_ptr(), null(model.reg_cols), null(model.reg_vals),
+                     int(model.reg_cols.numel()), out["joints"].data_ptr())
+        if dtype == torch.float32:
+            for k in ("vertices", "posed_joints", "joints"):
+                if k in out:
+                    out[k] = out[k].to(torch.float32)
+        return out
+
+    @torch.no_grad()
     def occupied_points(self, vox, threshold=0.5, dtype=torch.float64, capacity=None, return_indices: bool = False,
                         return_depth: bool = False, return_bits: bool = False):
         """Device version of the host lines every consumer of the decoder's voxels starts with (vis_generation.py:137-170,
