@@ -825,6 +825,18 @@ int nm_op_volfit_gauss(nm_ctx* ctx, const float* vox, const float* keypoints, in
                        float* vol);
 int nm_op_volfit_gauss_backward(nm_ctx* ctx, const float* vox, const float* keypoints, const float* dloss, int32_t B, int32_t T, int32_t K,
                                 int32_t G, float sigma, float* dkp);
+/* The two lowest hourglass levels of one feature net (vox_modules.py:78-120: encoder_res2, skip_res3, encoder_pool3, encoder_res3,
+ * decoder_res3, decoder_upsample3 + skip, decoder_res2) with the weights nm_ctx_set_weights loaded; unit parity against fp64 in
+ * tests/test_hgcore_gpu.py.  which: 0 = the frame feature net's hourglass, 1 = the clip-mean net's.  in [N][D^3][32] channels-last is the
+ * pool-2 output, its pending GroupNorm + LeakyReLU as per-frame in_scale / in_shift [N][32] and in_slope (both NULL and slope 1: `in` is
+ * already activated); out [N][D^3][48] plain fp32.  The transposed conv's output_padding is D % 2; the context's grid_size plays no part.
+ * fused = 1: the one-launch form of the inference forward (hg_core_kernel); NM_ERR_UNSUPPORTED, never a fall-back, where it is not
+ * eligible - conv mode other than 1, a layer without a split-fp16 pack, D outside 2 .. 6, tensors that do not fit in LDS.  fused = 0: the
+ * same layers as the separate launches of the inference forward without the core (D 2 .. 64).  Neither form looks at NM355_HG_CORE.
+ * NM_ERR_ARG: null ctx / in / out, only one of in_scale / in_shift, which or fused not 0 / 1, N < 1, D < 1.  Scratch comes from the
+ * context's workspace; the range guard's status word is left alone (a non-finite result is in `out` for the caller to see). */
+int nm_op_hourglass_core(nm_ctx* ctx, int32_t which, const float* in, const float* in_scale, const float* in_shift,
+                         float in_slope, int32_t N, int32_t D, int32_t fused, float* out);
 /* Conv arithmetic (per context: two contexts in one process may run in different modes; like every other launch-time
  * switch it lives in the nm_ctx).  mode 0: exact fp32 MFMA (v_mfma_f32_32x32x2_f32) for every conv.
  * mode 1 (default): layers with Cin % 16 == 0 run on the fp16 matrix cores with every fp32 operand split

@@ -141,6 +141,7 @@ SIGNATURES = {
     "nm_op_affinity_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "nm_op_volfit_gauss": (C.c_int, [C.c_void_p, _P, _P, _I, _I, _I, _I, _F, _P]),
     "nm_op_volfit_gauss_backward": (C.c_int, [C.c_void_p, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "nm_op_hourglass_core": (C.c_int, [C.c_void_p, _I, _P, _P, _P, _F, _I, _I, _I, _P]),
     "nm_set_conv_mode": (C.c_int, [C.c_void_p, _I]),
     "nm_get_conv_mode": (C.c_int, [C.c_void_p]),
     "nm_op_set_storage16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

@@ -474,32 +474,47 @@ static bool hg_core_params(const HourglassW& w, const TensorRef& a2, float* out,
     return ok;
 }
 
+// The two lowest levels, encoder_res2 ... decoder_res2, on the pool-2 output a2 (lazy GroupNorm + LeakyReLU): one hg_core launch or the
+// separate launches.  form < 0: the network's choice (the core in the inference forward, conv mode split16, unless NM355_HG_CORE=0 or
+// hg_core_params declines); form 1 / 0 (nm_op_hourglass_core): the core or an error / the separate launches, whatever the switch says.
+TensorRef hourglass_core(Net& n, const TensorRef& a2, const HourglassW& w, int op3, HgRec* r = nullptr, int form = -1) {
+    NmHgCoreParams hp;
+    const bool eligible = !r && nm_conv_get_mode() == 1 && (form == 1 || (form < 0 && nm_ls().hg_core)) && hg_core_params(w, a2, nullptr, hp);
+    if (form == 1 && !eligible) {
+        if (!n.rc) {
+            if (nm_conv_get_mode() != 1) nm_set_error("hourglass core: conv mode %d (the fused launch is split-fp16 arithmetic: mode 1 only)", nm_conv_get_mode());
+            else if (a2.D < 2 || a2.D > 6) nm_set_error("hourglass core: level-2 extent %d (the fused launch takes 2 .. 6)", a2.D);
+            else if (nm_hg_core_scratch_items(hp) < 0) nm_set_error("hourglass core: %zu bytes of LDS per frame do not fit", nm_hg_core_lds_bytes(hp));
+            else nm_set_error("hourglass core: a layer has no split-fp16 weight pack (or the channel counts do not chain)");
+            n.rc = NM_ERR_UNSUPPORTED;
+        }
+        return a2;
+    }
+    if (eligible) {
+        // inference: encoder_res2 ... decoder_res2 (13 convs, 14 GroupNorms, the transposed conv and the adds) in one launch
+        float* d2out = n.alloc((size_t)a2.N * vox(a2) * w.d2.c2.Cout);
+        hp.out = d2out;
+        if (n.live()) n.run(nm_launch_hg_core(hp, n.s));
+        return mk(d2out, a2.N, a2.D, a2.H, a2.W, w.d2.c2.Cout);
+    }
+    TensorRef x = res(n, a2, w.e2, nullptr, r ? &r->e2 : nullptr);
+    TensorRef s3 = res(n, x, w.s3, nullptr, r ? &r->s3 : nullptr);
+    x = res(n, pool(n, x, w.p3, r ? &r->p3 : nullptr), w.e3, nullptr, r ? &r->e3 : nullptr);
+    x = res(n, x, w.d3, nullptr, r ? &r->d3 : nullptr);
+    TensorRef u = up(n, x, w.u3, op3, r ? &r->u3 : nullptr); x = add2(n, u, &s3);
+    return res(n, x, w.d2, nullptr, r ? &r->d2 : nullptr);
+}
+
 TensorRef hourglass(Net& n, const TensorRef& x0, const HourglassW& w, int Ng, HgRec* r = nullptr) {
     const int op3 = (Ng / 4) % 2, op2 = (Ng / 2) % 2, op1 = Ng % 2;
     TensorRef s1 = res(n, x0, w.s1, nullptr, r ? &r->s1 : nullptr);
     TensorRef x = res(n, pool(n, x0, w.p1, r ? &r->p1 : nullptr), w.e1, nullptr, r ? &r->e1 : nullptr);
     TensorRef s2 = res(n, x, w.s2, nullptr, r ? &r->s2 : nullptr);
     TensorRef a2 = pool(n, x, w.p2, r ? &r->p2 : nullptr);
-    NmHgCoreParams hp;
-    TensorRef u;
-    if (!r && nm_conv_get_mode() == 1 && nm_ls().hg_core && hg_core_params(w, a2, nullptr, hp)) {
-        // inference: encoder_res2 ... decoder_res2 (13 convs, 14 GroupNorms, the transposed conv and the adds) in one launch
-        float* d2out = n.alloc((size_t)a2.N * vox(a2) * w.d2.c2.Cout);
-        hp.out = d2out;
-        if (n.live()) n.run(nm_launch_hg_core(hp, n.s));
-        x = mk(d2out, a2.N, a2.D, a2.H, a2.W, w.d2.c2.Cout);
-    } else {
-        x = res(n, a2, w.e2, nullptr, r ? &r->e2 : nullptr);
-        TensorRef s3 = res(n, x, w.s3, nullptr, r ? &r->s3 : nullptr);
-        x = res(n, pool(n, x, w.p3, r ? &r->p3 : nullptr), w.e3, nullptr, r ? &r->e3 : nullptr);
-        x = res(n, x, w.d3, nullptr, r ? &r->d3 : nullptr);
-        u = up(n, x, w.u3, op3, r ? &r->u3 : nullptr); x = add2(n, u, &s3);
-        x = res(n, x, w.d2, nullptr, r ? &r->d2 : nullptr);
-    }
-    u = up(n, x, w.u2, op2, r ? &r->u2 : nullptr); x = add2(n, u, &s2);
+    x = hourglass_core(n, a2, w, op3, r);
+    TensorRef u = up(n, x, w.u2, op2, r ? &r->u2 : nullptr); x = add2(n, u, &s2);
     x = res(n, x, w.d1, nullptr, r ? &r->d1 : nullptr);
     u = up(n, x, w.u1, op1, r ? &r->u1 : nullptr); x = add2(n, u, &s1);
-    (void)op3;
     return x;
 }
 
@@ -1507,6 +1522,30 @@ int nm_decode_from_keypoints(nm_ctx* c, const float* keypoints, const float* fir
     if (!rc) nm_nf_post(c, "nm_decode_from_keypoints");
     return rc;
 } catch (...) { return nm_abi_catch("nm_decode_from_keypoints"); }
+
+// Unit parity of the two lowest hourglass levels (tests/test_hgcore_gpu.py): hourglass_core() - the code the network runs - on a
+// tensor the caller chooses, with the loaded weights of one feature net.  Like the other op-level entry points it leaves the range
+// guard's status word alone: the caller reads `out`.
+int nm_op_hourglass_core(nm_ctx* c, int32_t which, const float* in, const float* in_scale, const float* in_shift, float in_slope,
+                         int32_t N, int32_t D, int32_t fused, float* out) try { NmScope nm_scope_(c);
+    int rc = check_ready(c, "op_hourglass_core");
+    if (rc) return rc;
+    if (!in || !out || (in_scale == nullptr) != (in_shift == nullptr)) { nm_set_error("op_hourglass_core: null argument"); return NM_ERR_ARG; }
+    if (which < 0 || which > 1 || fused < 0 || fused > 1 || N < 1 || D < 1) {
+        nm_set_error("op_hourglass_core: which=%d fused=%d N=%d D=%d (which and fused are 0 or 1, N and D at least 1)", which, fused, N, D); return NM_ERR_ARG;
+    }
+    if (!fused && (D < 2 || D > 64)) { nm_set_error("op_hourglass_core: level-2 extent %d (the separate launches take 2 .. 64)", D); return NM_ERR_UNSUPPORTED; }
+    nm_elem_set_nonfinite_flag(nullptr);
+    const HourglassW& w = (which ? c->det.clip : c->det.frame).hg;
+    const size_t numel = (size_t)N * D * D * D * w.d2.c2.Cout;
+    return with_workspace(c, [&]() {
+        Net n(c);
+        n.ws.release(0);
+        TensorRef x = hourglass_core(n, mk(in, N, D, D, D, w.e2.c1.Cin_pad, in_scale, in_shift, in_slope), w, D % 2, nullptr, fused);
+        if (n.live()) n.run(nm_check_hip(hipMemcpyAsync(out, x.p, numel * sizeof(float), hipMemcpyDeviceToDevice, n.s), "op_hourglass_core: copy"));
+        return n.rc;
+    });
+} catch (...) { return nm_abi_catch("nm_op_hourglass_core"); }
 
 // the ctx-owned block behind the weight-gradient stream (ring of dY buffers + scratch + scale pool), grown to the last sizing pass
 static int reserve_wside(nm_ctx* c) {
