@@ -37,7 +37,6 @@ NmLaunchState::NmLaunchState()
       wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: every split-fp16 k3 weight gradient on wgrad16_kernel (VALU transposition) instead of wgrad16z_kernel: the one A/B of the family (w16z_takes)
       tail_rank1(env_int("NM355_TAIL_RANK1", 1)),   // 0: the decoder tail's backward materialises its [F][G^3][32] gradient (A/B)
       up2c(env_int("NM355_UP2C", 1)),               // 0: fused-upsample layers stay on conv_f16s (diagnostic / A-B)
-      up2c_diag(env_int("NM355_UP2C_DIAG", 0)),
       vrnn_mid(env_int("NM355_VRNN_MID", 1)),          // 0: prior steps as six launches instead of three (A/B)
       vrnn_gemm(env_int("NM355_VRNN_GEMM", 1)),    // 0: one wavefront per output row at every batch size (A/B)
       vrnn_graph(env_int("NM355_VRNN_GRAPH", 1)),       // 0: rollouts enqueue their launches one by one instead of replaying a captured graph (A/B)
@@ -60,11 +59,9 @@ NmLaunchState::NmLaunchState()
       , f16r(env_int("NM355_F16R", 1))                      // 0: the one-product modes keep conv_f16p<SINGLE> on the 32-output-channel layers instead of conv_f16r (resident weights; A/B)
       , up2_mat(env_int("NM355_UP2_MAT", 1))                // 0: the one-product training forward keeps the fused-upsample staging on its 32-output layer instead of materialising the upsampled input for conv_f16r (A/B)
       , conv_wgs(env_int("NM355_CONV_WGS", 0))              // > 0: the persistent producer / consumer convs launch at most this many workgroups (co-residency A/B: CUs left free for the other queues)
-      , up2c_x16(env_int("NM355_UP2C_X16", 1))              // 0: conv_up2c stays on v_mfma_f32_32x32x16_f16 (A/B; 1: conv_up2c_x16_kernel, v_mfma_f32_16x16x32_f16, fp32-storage modes)
-      , up2c_all(env_int("NM355_UP2C_ALL", 0))              // 1: the decoder's FIRST fused-upsample layer (128 -> 64 @16^3 -> 32^3) on the composite-weight kernel too (A/B)
       , p2_defer(env_int("NM355_P2_DEFER", 0))              // 1: conv_f16p2 with one accumulator per tile and the epilogue deferred into the next brick's first step (A/B: slower)
       , fast_decode(env_int("NM355_FAST_DECODE", 1))        // 0: the persistent convs decode a brick's position with integer divisions instead of host-made reciprocal multiplications (A/B)
-      , up2y(env_int("NM355_UP2Y", 2))                      // 0: the fused-upsample layers keep the composite-weight kernel in all three axes (A/B); 1: conv_up2y_kernel (products on the coarse grid, interpolated along y) on the 64 -> 32 layer; 2: on the 128 -> 64 layer too
+      , up2y(env_int("NM355_UP2Y", 1))                      // 0: the split-fp16 mode keeps the composite-weight kernel in all three axes (conv_up2c_x16_kernel) on the 64 -> 32 fused-upsample layer and conv_f16s on the 128 -> 64 one (A/B, the tests' reference); else: conv_up2y_kernel (products on the coarse grid, interpolated along y) on both
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
       , up2c_shell(env_int("NM355_UP2C_SHELL", 1))          // the shell of the fused-upsample layers (split-fp16 mode, fp32 storage): 0: one line per face workgroup (A/B); 1: R lines per face workgroup (conv_up2c_face_r_kernel); 2: that and the edge items of the two-half layer with their loads in a ring (conv_up2c_edge_p_kernel: not the default, it does not clear the bar on the step); 3: the edge form alone; + 20 / 40: R = 2 / 4 at every layer (nm_up2c.hip)

@@ -3,10 +3,12 @@
 #pragma once
 #include "nm_common.h"
 
-// true when the layer shape is taken by the composite-weight kernel (otherwise conv_f16s<.., UP2> of nm_conv.hip runs it)
+// true when the layer shape is taken by this family (otherwise conv_f16s<.., UP2> of nm_conv.hip runs it): the 64 -> 32 layer, and in
+// the product form also the 128 -> 64 one
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad);
 // true when the split-fp16 mode runs the main launch in the product-then-interpolate form along y (conv_up2y_kernel: 4 x 27 instead of
-// 8 x 27 products per coarse voxel); NM355_UP2Y=0 keeps conv_up2c[_x16]_kernel
+// 8 x 27 products per coarse voxel); NM355_UP2Y=0 keeps the composite form there (conv_up2c_x16_kernel), and the one-product modes
+// always run theirs (conv_up2c_kernel)
 bool nm_up2y_active();
 // floats (4-byte units) of the packed composite weight sets of one layer: 8 parity sets of 27 coarse taps + 56 shell-correction sets
 // + the four (pz, px) sets of conv_up2y_kernel

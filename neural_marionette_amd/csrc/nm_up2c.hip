@@ -11,16 +11,19 @@
 // the fine convolution's MAC count, 8 x 27 products per coarse voxel - of which the result needs 27: the channel contraction commutes
 // with the interpolation, so the products can be taken once per coarse voxel and RAW tap and interpolated afterwards.  The split-fp16
 // mode does that along y (conv_up2y_kernel below: 4 x 27 per coarse voxel + one halo cell per side of a COLUMN of bricks along y:
-// a workgroup marches along y and carries the halo products from brick to brick); the composite
-// kernels remain for the one-product modes and as the A/B arm NM355_UP2Y=0.  The coarse halo tile of a brick is 8x smaller than the fine one: all 64 input channels of
-// a (2+2) x (8+2) x (8+2) coarse tile sit in LDS at once (split fp16 hi/lo, 104 KB), staged once per brick, and the 864 k-steps of
-// the brick's eight parity classes run from it without a barrier.
+// a workgroup marches along y and carries the halo products from brick to brick).  Two composite kernels remain, each with one kind of
+// arithmetic: conv_up2c_kernel is the main kernel of the one-product modes (fp32 and bfloat16 storage), conv_up2c_x16_kernel the
+// split-fp16 composite form behind NM355_UP2Y=0 (the A/B arm and the tests' exact reference of the product form).  The coarse halo
+// tile of a brick is 8x smaller than the fine one: the input channels of a (2+2) x (8+2) x (8+2) coarse tile sit in LDS, 32 at a
+// time in two buffers (split fp16 hi/lo), staged while the previous group's k-steps run, and the k-steps of the brick's eight parity
+// classes run from it with two barriers per 32-channel group.
 //
-// Machine mapping: one 512-thread workgroup per CU, wave w = parity class (pz,py,px) = bits of w, 4 MFMA row tiles per wave
-// (2z x 8y x 8x coarse cells = 128 rows x 32 output channels), v_mfma_f32_32x32x16_f16 with the 3-product hi/lo split of
-// nm_conv.hip (fp32-equivalent products, fp32 accumulate).  Each wave streams ITS parity's weights from L2 (2 KB per k-step for
-// 12 MFMAs, prefetched two k-steps ahead); a row tile is 8(x) x 2(z) x 2(y) cells, dealt to the lanes so that each lane group of a
-// ds_read_b128 hits 16 distinct 16-byte slots (z-plane pitch = 8 mod 16 slots).
+// Machine mapping: one 512-thread workgroup per CU, wave w = parity class (pz,py,px) = bits of w, 2z x 8y x 8x coarse cells = 128
+// rows x 32 output channels per wave.  conv_up2c_kernel: 4 row tiles of v_mfma_f32_32x32x16_f16, one hi x hi product per MAC;
+// conv_up2c_x16_kernel: 8 row tiles x 2 column blocks of v_mfma_f32_16x16x32_f16 with the 3-product hi/lo split of nm_conv.hip
+// (fp32-equivalent products, fp32 accumulate) in one accumulator.  Each wave streams ITS parity's weights from L2, prefetched ahead
+// of their k-step; the row tiles are dealt to the lanes so that each lane group of a ds_read_b128 hits 16 distinct 16-byte slots
+// (z-plane pitch = 8 mod 16 slots).
 //
 // Volume border.  The coarse tile is staged with clamped indices, which reproduces torch's clamped interpolation for every fine
 // position INSIDE the volume.  The fine convolution, however, zero-pads: taps that leave the fine volume must contribute nothing,
@@ -37,14 +40,7 @@
 
 namespace {
 
-#ifndef UP2C_SCHED
-#define UP2C_SCHED 1
-#endif
-#if UP2C_SCHED
 #define UP2C_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define UP2C_SB() do {} while (0)
-#endif
 #define UP2C_SPLIT_SCALE 2048.0f          // same hi/lo split as nm_conv.hip: v = hi + lo * 2^-11
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -58,7 +54,9 @@ constexpr int CG = 32;                                // input channels per LDS 
 constexpr int NPLANES = CG / 16 * 4;
 constexpr size_t LDS_BYTES = (size_t)2 * NPLANES * HVP * 16 + 2 * CG * sizeof(float);      // + the next tile's GroupNorm scale / shift
 
-struct Up2cParams {
+// (16-byte aligned: 128 bytes of kernel arguments, so the shell kernels' trailing ints start on a 16-byte boundary and arrive in one
+//  aligned scalar load)
+struct alignas(16) Up2cParams {
     const float* in; const float* in_scale; const float* in_shift; float in_slope;
     int N, ID, IH, IW, Cin;
     const half8* wc;             // composite sets (see set_offset)
@@ -69,7 +67,6 @@ struct Up2cParams {
     int nblk;                    // partial blocks per frame (bricks + shell items)
     int march;                   // conv_up2y_kernel<true> is launched: workgroups take whole columns of bricks along y and carry the two halo row tiles
     int ypad;                    // conv_up2y_kernel is the main kernel and zero-pads along y itself: the y faces are not the shell kernels'
-    int diag;                    // NM355_UP2C_DIAG (timing experiments only): 1 (unused), 2 no staging, 4 no shell launch, 8 no MFMA loop, 16 weights from one address, 32 no barriers, 64 (with NM355_UP2C_X16=0) the 32x32x16 kernel with one accumulator
 };
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -220,17 +217,18 @@ __global__ void up2y_compose_kernel(const float* __restrict__ w, int Cout, int C
 // ---- main kernel -----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ constexpr int tap_off(int t) { return (t / 9) * ZP + ((t / 3) % 3) * HX + (t % 3); }
 
-// One STEP = (brick, 32-output-channel group, 32-input-channel group): 2 chunks x 27 taps = 54 k-steps of 12 MFMAs per wave on
+// One STEP = (brick, 32-output-channel group, 32-input-channel group): 2 chunks x 27 taps = 54 k-steps of 4 MFMAs per wave on
 // the LDS buffer `cur`.  The tile of the NEXT step is staged into the other buffer from inside the k-loop: each thread owns up to
 // four (voxel, channel octet) items; an item's global loads are issued a dozen k-steps before its activate / split / LDS write,
 // so neither the load latency nor the conversion VALU is exposed - they run in the shadow of the two waves' MFMAs (a loop that
 // only issues MFMAs and LDS reads keeps the pipe ~100 % busy; staged as a separate phase the same work cost 22 % of the kernel:
-// one workgroup per CU has nothing else to run meanwhile).  One workgroup barrier per step.
+// one workgroup per CU has nothing else to run meanwhile).  Two workgroup barriers per step.
 struct StepPos { int n, br, nh, cg, cz0, cy0, cx0; };
 
+// The main kernel of the one-product modes (conv modes 3 / 4): ONE fp16 product per MAC, so only the hi planes of the LDS image and
+// the hi halves of the packed weights are touched.
 // IO: bit 0 = bfloat16 input, bit 1 = bfloat16 output (16-bit storage; the shell kernels then read-modify-write bfloat16 values)
-// ONE (A/B arm of profiles/r06_mfma_shape_ab.txt): the three products in one accumulator as in conv_up2c_x16_kernel
-template <bool SINGLE, int IO = 0, bool ONE = false>
+template <int IO>
 __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
     constexpr bool IH16 = (IO & 1) != 0, OH16 = (IO & 2) != 0;
     extern __shared__ f32x4 lds_raw[];
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
     const size_t kstride = 4 * plane;                             // half8 units between consecutive k-steps of a set
     const half8* __restrict__ wset = p.wc + (size_t)wave * 27 * C16 * kstride;      // wave-uniform
     const unsigned wlane = (unsigned)(h * (int)plane + l31) * 16u;                  // per-lane byte offset of every weight load
-    const size_t kbytes = kstride * 16, lobytes = 2 * plane * 16;
+    const size_t kbytes = kstride * 16;
     const int OD = 2 * p.ID, OH = 2 * p.IH, OW = 2 * p.IW;
     // A rows of this lane (16-byte slots, lane half's plane included): tile j covers y in {2j, 2j+1}.  A ds_read_b128 is served in
     // the lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} (quads {0,3,5,6} / {1,2,4,7} of a lane half): a group's four quads are
@@ -301,8 +299,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
             widen8<IH16>(pr_a, pr_b);
             split8(act4(pr_a, sca, sha, affine, p.in_slope), act4(pr_b, scb, shb, affine, p.in_slope), hi, lo);
             const int slot = hz * ZP + hy * HX + hx;
-            buf[s_plane * HVP + slot] = hi;
-            if constexpr (!SINGLE) buf[(s_plane + 2) * HVP + slot] = lo;      // (the one-product modes never read the lo planes)
+            buf[s_plane * HVP + slot] = hi;      // (the lo planes keep their place in the image and stay unwritten: nothing reads them)
         }
     };
     auto ldw = [&](const char* base, size_t extra) { return *reinterpret_cast<const half8*>(base + extra + wlane); };
@@ -314,7 +311,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
     for (int k = 0; k < SITEMS; ++k) { issue(cs, k); commit(tile, k); }
     lds_barrier();
     int cur = 0, item = item0;
-    f32x16 acc[4], accl[4];
+    f32x16 acc[4];
     // The k-steps of consecutive steps form ONE software-pipelined stream: the B operands (two k-steps ahead) and the A operands
     // (one ahead) of a step's first k-steps are fetched during the last k-steps of the step before it, so a step boundary costs no
     // pipeline refill.  Two workgroup barriers per step keep the two LDS buffers apart: at k-step 10 (before this step's first
@@ -322,11 +319,11 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
     // write: the other buffer is complete before the first read of the next step is issued at k-step 53).
     constexpr int KS = CG / 16 * 27;                                  // k-steps per step (54)
     const char* wk = reinterpret_cast<const char*>(wset);              // (cs.nh = cs.cg = 0)
-    half8 bh[3], bl[3], ah[4], al[4];
-    bh[0] = ldw(wk, 0); bl[0] = ldw(wk, lobytes);
-    bh[1] = ldw(wk, kbytes); bl[1] = ldw(wk, kbytes + lobytes);
+    half8 bh[3], ah[4];
+    bh[0] = ldw(wk, 0);
+    bh[1] = ldw(wk, kbytes);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { ah[j] = tile[arow[j]]; al[j] = tile[arow[j] + 2 * HVP]; }
+    for (int j = 0; j < 4; ++j) ah[j] = tile[arow[j]];
     for (;;) {
         // the step after this one
         StepPos ns = cs; bool have_next = true;
@@ -338,58 +335,43 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { acc[j][r] = 0.f; accl[j][r] = 0.f; }
+                for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         }
         const half8* tb = tile + cur * (NPLANES * HVP);
         half8* nb = tile + (cur ^ 1) * (NPLANES * HVP);
-        const bool stage = have_next && !(p.diag & 2);
         // weights of the next step's first k-steps (a finished workgroup reads its own first set again: any valid address)
         const char* wnext = reinterpret_cast<const char*>(wset + (size_t)ns.nh * 32 + (size_t)(ns.cg * (CG / 16)) * 27 * kstride);
-        if (stage) issue_affine(ns);
-        if (!(p.diag & 8)) {
+        if (have_next) issue_affine(ns);
 #pragma unroll
         for (int c = 0; c < CG / 16; ++c) {
 #pragma unroll
             for (int t = 0; t < 27; ++t) {
                 const int ks = c * 27 + t, s = ks % 3, s2 = (ks + 2) % 3;
-                if (ks + 2 < KS) { bh[s2] = ldw(wk, 2 * kbytes); bl[s2] = ldw(wk, 2 * kbytes + lobytes); }
-                else { bh[s2] = ldw(wnext, (size_t)(ks + 2 - KS) * kbytes); bl[s2] = ldw(wnext, (size_t)(ks + 2 - KS) * kbytes + lobytes); }
-                if (!(p.diag & 16)) wk += kbytes;
+                if (ks + 2 < KS) bh[s2] = ldw(wk, 2 * kbytes);
+                else bh[s2] = ldw(wnext, (size_t)(ks + 2 - KS) * kbytes);
+                wk += kbytes;
                 // staging pieces of the next tile: item i loaded at k-step 1 + 13 i, written at 11 + 13 i
-                if (stage) {
+                if (have_next) {
 #pragma unroll
                     for (int i = 0; i < SITEMS; ++i) {
                         if (ks == 1 + 13 * i) issue(ns, i);
                         if (ks == 11 + 13 * i) commit(nb, i);
                     }
                 }
-                if (have_next && (ks == 10 || ks == 51) && !(p.diag & 32)) lds_barrier();
+                if (have_next && (ks == 10 || ks == 51)) lds_barrier();
                 UP2C_SB();
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (ONE) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[j], bh[s] * (_Float16)UP2C_SPLIT_SCALE, acc[j], 0, 0, 0);
-                    else acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[j], bh[s], acc[j], 0, 0, 0);
-                }
+                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[j], bh[s], acc[j], 0, 0, 0);
                 UP2C_SB();
                 // A operands of the next k-step (after the last one: tap 0 of the other buffer)
                 const half8* xb = (ks == KS - 1) ? nb : tb;
                 const int nof = (ks == KS - 1) ? 0 : ((t < 26) ? c * 4 * HVP + tap_off((t + 1) % 27) : (c + 1) * 4 * HVP);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (ONE) acc[j] = nm_mfma_lo<SINGLE>(ah[j], bl[s], acc[j]);
-                    else accl[j] = nm_mfma_lo<SINGLE>(ah[j], bl[s], accl[j]);
                     ah[j] = xb[arow[j] + nof];
                     UP2C_SB();
                 }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (ONE) acc[j] = nm_mfma_lo<SINGLE>(al[j], bh[s], acc[j]);
-                    else accl[j] = nm_mfma_lo<SINGLE>(al[j], bh[s], accl[j]);
-                    al[j] = xb[arow[j] + 2 * HVP + nof];
-                    UP2C_SB();
-                }
             }
-        }
         }
         wk = wnext;
         if (cs.cg == NCG - 1) {
@@ -411,8 +393,8 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
                         const int x = 4 * ((r >> 2) & 1) + (r & 3), zb = (r >> 3) & 1, yb = (0x96 >> (h + 2 * (r >> 2))) & 1;
-                        const float v0 = (ONE ? acc[j][r] * (1.0f / UP2C_SPLIT_SCALE) : __builtin_fmaf(accl[j][r], 1.0f / UP2C_SPLIT_SCALE, acc[j][r])) + bv;
-                        const float v1 = (ONE ? acc[j][r + 1] * (1.0f / UP2C_SPLIT_SCALE) : __builtin_fmaf(accl[j][r + 1], 1.0f / UP2C_SPLIT_SCALE, acc[j][r + 1])) + bv;
+                        const float v0 = acc[j][r] + bv;
+                        const float v1 = acc[j][r + 1] + bv;
                         const float send = odd ? v0 : v1;
                         const float recv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), 0xB1, 0xf, 0xf, true));
                         const unsigned pk = odd ? nm_pk_bf16(recv, v1) : nm_pk_bf16(v0, recv);
@@ -433,7 +415,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
                     for (int r = 0; r < 16; ++r) {
                         // register r of lane half h is row (r & 3) + 4 h + 8 (r >> 2) of the tile (see arow)
                         const int x = 4 * ((r >> 2) & 1) + (r & 3), zb = (r >> 3) & 1, yb = (0x96 >> (h + 2 * (r >> 2))) & 1;
-                        const float v = (ONE ? acc[j][r] * (1.0f / UP2C_SPLIT_SCALE) : __builtin_fmaf(accl[j][r], 1.0f / UP2C_SPLIT_SCALE, acc[j][r])) + bv;
+                        const float v = acc[j][r] + bv;
                         base[(size_t)(2 * zb) * sZ + (size_t)(2 * yb) * sY + (size_t)(2 * x) * sX] = v;
                         s += v; ss = __builtin_fmaf(v, v, ss);
                         __builtin_amdgcn_sched_barrier(0);
@@ -442,7 +424,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int x = 4 * ((r >> 2) & 1) + (r & 3), zb = (r >> 3) & 1, yb = (0x96 >> (h + 2 * (r >> 2))) & 1;
-                        const float v = (ONE ? acc[j][r] * (1.0f / UP2C_SPLIT_SCALE) : __builtin_fmaf(accl[j][r], 1.0f / UP2C_SPLIT_SCALE, acc[j][r])) + bv;
+                        const float v = acc[j][r] + bv;
                         base[(size_t)(2 * zb) * sZ + (size_t)(2 * yb) * sY + (size_t)(2 * x) * sX] = v;
                         const int oz = 2 * (cs.cz0 + zb) + pz, oy = 2 * (cs.cy0 + 2 * j + yb) + py, ox = 2 * (cs.cx0 + x) + px;
                         const bool shell = oz == 0 || oz == OD - 1 || oy == 0 || oy == OH - 1 || ox == 0 || ox == OW - 1;
@@ -463,13 +445,14 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
     }
 }
 
-// ---- the same kernel on v_mfma_f32_16x16x32_f16 (round 6) -------------------------------------------------------------------
-// Same bricks, same LDS image (the staging code is shared verbatim), same packed weights, same 3-product arithmetic; what changes is
-// the MFMA shape: K = 32 takes BOTH 16-channel chunks of the 32-channel LDS buffer in one instruction, a row tile is 16 rows, a
-// column block 16 output channels.  Per wave and tap: 8 row tiles x 2 column blocks x 3 products = 48 MFMAs of 16 cycles (the
-// 32x32x16 form: 2 chunks x 4 tiles x 3 = 24 of 32 cycles) - the same FLOPs, the same operand bytes (16 A reads + 4 B loads per
-// tap), a step is 27 k-steps instead of 54.  MI355X_MICROARCH.md 'DVFS give-back' item 7: where the chip holds its clock down under
-// matrix load (this kernel: 1.49 GHz, profiles/r05_pmc_mfma.json) it holds a higher one on this shape.
+// ---- the split-fp16 composite kernel, on v_mfma_f32_16x16x32_f16 (NM355_UP2Y=0) ------------------------------------------------
+// Same bricks, same LDS image (hi AND lo planes), same packed weights as conv_up2c_kernel; 3-product arithmetic, and another
+// MFMA shape: K = 32 takes BOTH 16-channel chunks of the 32-channel LDS buffer in one instruction, a row tile is 16 rows, a
+// column block 16 output channels.  Per wave and tap: 8 row tiles x 2 column blocks x 3 products = 48 MFMAs of 16 cycles (on
+// 32x32x16 it would be 2 chunks x 4 tiles x 3 = 24 of 32 cycles) - the same FLOPs, the same operand bytes (16 A reads + 4 B loads
+// per tap), a step is 27 k-steps instead of 54.  MI355X_MICROARCH.md 'DVFS give-back' item 7: where the chip holds its clock down under
+// matrix load (the three products on 32x32x16: 1.49 GHz, profiles/r05_pmc_mfma.json) it holds a higher one on this shape
+// (profiles/r06_mfma_shape_ab.txt; the 32x32x16 arm is retired: DESIGN_HISTORY.md).
 //   lane = 16 q + r:  A row r of the tile, k = 8 q + j -> channel (q >> 1) * 16 + (q & 1) * 8 + j of the 32-channel group, i.e. LDS
 //   plane (q >> 1) * 4 + hl * 2 + (q & 1);  B column r of the block, the same k -> weight chunk 2 cg + (q >> 1), half q & 1.
 // Row tile j = (x parity j & 1, y pair j >> 1):  row r -> x = 2 (r & 3) + (j & 1),  z = r >> 3,  y = 2 (j >> 1) + (bit 2 ^ bit 3 of r).
@@ -477,13 +460,6 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_kernel(Up2cParams p) {
 // plane and rows {4-11} of the NEXT plane (or the other way round); each of the two row sets covers the eight even slots (mod 16)
 // - x stride 2, z-plane pitch = 8 (mod 16), y pitch 10 - and consecutive planes are HVP = 1 (mod 16) slots apart: 16 distinct slots.
 // C/D: column = lane & 15 (output channel of the block), row = 4 q + reg:  x = 2 reg + (j & 1),  z = q >> 1,  y = 2 (j >> 1) + ((q ^ (q >> 1)) & 1).
-template <bool SINGLE>
-__device__ __forceinline__ f32x4 up2c_mfma16_lo(half8 a, half8 b, f32x4 c) {
-    if constexpr (SINGLE) return c;
-    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-template <bool SINGLE>
 __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
     extern __shared__ f32x4 lds_raw[];
     half8* tile = reinterpret_cast<half8*>(lds_raw);               // [buffer][chunk*4 + hl*2 + h][HVP] x 16 B, slot = hz*ZP + hy*HX + hx
@@ -549,7 +525,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
             split8(act4(pr_a, sca, sha, affine, p.in_slope), act4(pr_b, scb, shb, affine, p.in_slope), hi, lo);
             const int slot = hz * ZP + hy * HX + hx;
             buf[s_plane * HVP + slot] = hi;
-            if constexpr (!SINGLE) buf[(s_plane + 2) * HVP + slot] = lo;
+            buf[(s_plane + 2) * HVP + slot] = lo;
         }
     };
     auto ldw = [&](const char* base, size_t extra) { return *reinterpret_cast<const half8*>(base + extra + wlane); };
@@ -592,14 +568,12 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
         }
         const half8* tb = tile + cur * (NPLANES * HVP);
         half8* nb_ = tile + (cur ^ 1) * (NPLANES * HVP);
-        const bool stage = have_next && !(p.diag & 2);
         const char* wnext = reinterpret_cast<const char*>(wset + (size_t)ns.nh * 32 + (size_t)(ns.cg * (CG / 16)) * 27 * kstride);
-        if (!(p.diag & 8)) {
 #pragma unroll
         for (int t = 0; t < KS; ++t) {
             const int s = t % 3, s1 = (t + 1) % 3;
             // staging pieces of the next tile: item i loaded at k-step 0 / 7 / 13 / 19, written at 5 / 12 / 18 / 24
-            if (stage) {
+            if (have_next) {
                 if (t == 0) aff_load(ns);
                 if (t == 3) aff_store();
 #pragma unroll
@@ -608,7 +582,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
                     if (t == (i == 0 ? 5 : 6 * i + 6)) commit(nb_, i);
                 }
             }
-            if (have_next && (t == 4 || t == 25) && !(p.diag & 32)) lds_barrier();
+            if (have_next && (t == 4 || t == 25)) lds_barrier();
             // B operands of the next k-step - requested BEHIND the staging code: a commit waits for its item with vmcnt(0) (the item's
             // loads sit under a condition, so hipcc does not count), which then finds only loads that are a k-step old
             {
@@ -620,10 +594,8 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
             // ONE accumulator for the three products: x w 2^11 = x_hi (2^11 w_hi) + x_hi w_lo' + x_lo' w_hi with the lo parts stored
             // times 2^11 as everywhere; 2^11 w_hi is exact in fp16 (|w| < 32) and made here from w_hi (four packed multiplies per block)
             half8 b2k[2];
-            if constexpr (!SINGLE) {
 #pragma unroll
-                for (int nb = 0; nb < 2; ++nb) b2k[nb] = bh[s][nb] * (_Float16)UP2C_SPLIT_SCALE;
-            } else { b2k[0] = bh[s][0]; b2k[1] = bh[s][1]; }
+            for (int nb = 0; nb < 2; ++nb) b2k[nb] = bh[s][nb] * (_Float16)UP2C_SPLIT_SCALE;
             UP2C_SB();
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -640,19 +612,18 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
 #pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) acc[2 * u + x][nb] = up2c_mfma16_lo<SINGLE>(ah[rs][x], bl[s][nb], acc[2 * u + x][nb]);
+                    for (int nb = 0; nb < 2; ++nb) acc[2 * u + x][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rs][x], bl[s][nb], acc[2 * u + x][nb], 0, 0, 0);
                     ah[rs][x] = xb[abase + 2 * un * HX + x + nof];
                     UP2C_SB();
                 }
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
 #pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) acc[2 * u + x][nb] = up2c_mfma16_lo<SINGLE>(al[rs][x], bh[s][nb], acc[2 * u + x][nb]);
-                    if constexpr (!SINGLE) al[rs][x] = xb[abase + 2 * un * HX + x + 2 * HVP + nof];
+                    for (int nb = 0; nb < 2; ++nb) acc[2 * u + x][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rs][x], bh[s][nb], acc[2 * u + x][nb], 0, 0, 0);
+                    al[rs][x] = xb[abase + 2 * un * HX + x + 2 * HVP + nof];
                     UP2C_SB();
                 }
             }
-        }
         }
         wk = wnext;
         if (cs.cg == NCG - 1) {
@@ -674,7 +645,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
                     const bool zy = zshell || oy == 0 || oy == OH - 1;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float v = acc[j][nb][r] * (SINGLE ? 1.0f : 1.0f / UP2C_SPLIT_SCALE) + bv;
+                        const float v = acc[j][nb][r] * (1.0f / UP2C_SPLIT_SCALE) + bv;
                         base[(size_t)(4 * r) * sX] = v;
                         float mv = v;
                         if (border_brick) {
@@ -1582,7 +1553,7 @@ __global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, 
 
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad) {
     return nm_ls().up2c && ks == 3 && stride == 1 && pad == 1 && ID % BZ == 0 && IH % BY == 0 && IW % BX == 0 && Cin % CG == 0 && Cout % 32 == 0 &&
-           ((Cin == 64 && Cout == 32) || ((nm_ls().up2c_all || (nm_ls().up2y >= 2 && !nm_conv_single())) && Cin <= 128 && Cout <= 64));      // (the one-product modes keep the wider layers on conv_f16s)
+           ((Cin == 64 && Cout == 32) || (nm_ls().up2y && !nm_conv_single() && Cin <= 128 && Cout <= 64));      // (the wider layer: in the product form only - the one-product modes and NM355_UP2Y=0 keep it on conv_f16s)
 }
 
 bool nm_up2y_active() { return nm_ls().up2y != 0 && nm_ls().conv_mode == 1 && nm_conv_single() == 0; }
@@ -1606,14 +1577,23 @@ int nm_up2c_blocks_per_frame(int ID, int IH, int IW) {
     return 8 * (ID / BZ) * (IH / BY) * (IW / BX) + 4 * face_groups(ID, IH, IW) + edge_items(ID, IH, IW);
 }
 
+// The one-product instantiations of the main / face / edge kernels by storage combination io (bit 0 bfloat16 input, bit 1 bfloat16
+// output); launch_io runs `split` in the split-fp16 mode (fp32 storage only) and one[io] in the one-product modes.
+static void (*const MAIN_ONE[4])(Up2cParams) = {conv_up2c_kernel<0>, conv_up2c_kernel<1>, conv_up2c_kernel<2>, conv_up2c_kernel<3>};
+static void (*const FACE_ONE[4])(Up2cParams, int, int) = {conv_up2c_face_kernel<true, 0>, conv_up2c_face_kernel<true, 1>, conv_up2c_face_kernel<true, 2>, conv_up2c_face_kernel<true, 3>};
+static void (*const EDGE_ONE[4])(Up2cParams, int, int, int, int) = {conv_up2c_edge_kernel<true, 0>, conv_up2c_edge_kernel<true, 1>, conv_up2c_edge_kernel<true, 2>, conv_up2c_edge_kernel<true, 3>};
+template <typename... P, typename... A>
+static void launch_io(void (*split)(P...), void (*const (&one)[4])(P...), bool single, int io, dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(single ? one[io] : split, grid, dim3(threads), lds, s, args...);
+}
+
 int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bias, float* out, int Cout, int Co_pad, float* part,
                         hipStream_t s, int out_h) {
     if (!nm_up2c_eligible(in.D, in.H, in.W, in.C, Cout, 3, 1, 1) || !packed) { nm_set_error("conv_up2c: shape not eligible"); return NM_ERR_ARG; }
     if ((in.scale == nullptr) != (in.shift == nullptr)) { nm_set_error("conv_up2c: scale/shift must come together"); return NM_ERR_ARG; }
     static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_up2c)", &conv_up2c_kernel<false>, &conv_up2c_kernel<true>,
-                                    &conv_up2c_kernel<true, 3>, &conv_up2c_kernel<true, 2>, &conv_up2c_kernel<true, 1>, &conv_up2c_kernel<false, 0, true>,
-                                    &conv_up2c_x16_kernel<false>, &conv_up2c_x16_kernel<true>, &conv_up2y_kernel<false>, &conv_up2y_kernel<true>,
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_up2c)", MAIN_ONE[0], MAIN_ONE[1], MAIN_ONE[2], MAIN_ONE[3],
+                                    &conv_up2c_x16_kernel, &conv_up2y_kernel<false>, &conv_up2y_kernel<true>,
                                     &conv_up2c_face_r_kernel<2, 9>, &conv_up2c_face_r_kernel<4, 6>)) return rc;
     const bool single = nm_conv_single() != 0;
     const bool io16 = in.h || out_h;
@@ -1630,7 +1610,6 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     p.Cout = Cout; p.Co_pad = Co_pad;
     p.nbz = in.D / BZ; p.nby = in.H / BY; p.nbx = in.W / BX;
     p.nblk = nm_up2c_blocks_per_frame(in.D, in.H, in.W);
-    p.diag = nm_ls().up2c_diag;
     const int bricks = p.nbz * p.nby * p.nbx, total = p.N * bricks;
     // conv_up2y_kernel: whole columns of bricks along y per workgroup where that leaves no CU without one (NM355_UP2Y_MARCH=2: always),
     // zero padding along y in its epilogue (NM355_UP2Y_YPAD)
@@ -1640,21 +1619,12 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     const long long tiles_bricks = (long long)((total + cus - 1) / cus) * YT, tiles_columns = (long long)((columns + cus - 1) / cus) * (YT + (YT - 2) * (p.nby - 1));
     p.march = y_main && p.nby > 1 && (nm_ls().up2y_march >= 2 || (nm_ls().up2y_march == 1 && columns >= cus && tiles_columns < tiles_bricks));
     p.ypad = y_main && nm_ls().up2y_ypad != 0;
-    if (io == 3) hipLaunchKernelGGL((conv_up2c_kernel<true, 3>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (io == 2) hipLaunchKernelGGL((conv_up2c_kernel<true, 2>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (io == 1) hipLaunchKernelGGL((conv_up2c_kernel<true, 1>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    // (the one-product modes keep the 32x32x16 kernel in fp32 storage too: their bfloat16-storage instantiations are bit-compared with
-    //  it, tests/test_storage16_gpu.py; NM355_UP2C_X16=2 forces the 16x16x32 form there as well - A/B)
-    else if (y_main && p.march) hipLaunchKernelGGL(conv_up2y_kernel<true>, dim3((unsigned)min(columns, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (y_main) hipLaunchKernelGGL(conv_up2y_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_x16 >= 2 && single) hipLaunchKernelGGL(conv_up2c_x16_kernel<true>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_x16 && !single) hipLaunchKernelGGL(conv_up2c_x16_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (single) hipLaunchKernelGGL(conv_up2c_kernel<true>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else if (nm_ls().up2c_diag & 64) hipLaunchKernelGGL((conv_up2c_kernel<false, 0, true>), dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
-    else hipLaunchKernelGGL(conv_up2c_kernel<false>, dim3((unsigned)min(total, cus)), dim3(512), LDS_BYTES, s, p);
+    // (the one-product modes keep ONE kernel in fp32 and in bfloat16 storage: the instantiations are bit-compared with one another,
+    //  tests/test_storage16_gpu.py)
+    void (*const main_split)(Up2cParams) = !y_main ? conv_up2c_x16_kernel : p.march ? conv_up2y_kernel<true> : conv_up2y_kernel<false>;
+    launch_io(main_split, MAIN_ONE, single, io, dim3((unsigned)min(p.march ? columns : total, cus)), 512, LDS_BYTES, s, p);
     int rc = nm_check_hip(hipGetLastError(), "conv_up2c launch");
     if (rc) return rc;
-    if (nm_ls().up2c_diag & 4) return NM_OK;
     int TZ, TY, TX; shell_tiles(in.D, in.H, in.W, TZ, TY, TX);
     const int fg = face_groups(in.D, in.H, in.W), ei = edge_items(in.D, in.H, in.W);
     const size_t face_lds = (size_t)(in.C / 16 * 4) * FPV * 16;
@@ -1671,21 +1641,13 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
         if (R == 2) hipLaunchKernelGGL((conv_up2c_face_r_kernel<2, 9>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<2>() * 16, s, p, TY, TX);
         else hipLaunchKernelGGL((conv_up2c_face_r_kernel<4, 6>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<4>() * 16, s, p, TY, TX);
     }
-    else if (io == 3) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 3>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
-    else if (io == 2) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 2>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
-    else if (io == 1) hipLaunchKernelGGL((conv_up2c_face_kernel<true, 1>), dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
-    else if (single) hipLaunchKernelGGL(conv_up2c_face_kernel<true>, dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
-    else hipLaunchKernelGGL(conv_up2c_face_kernel<false>, dim3((unsigned)(p.N * fg)), dim3(256), face_lds, s, p, TY, TX);
+    else launch_io(conv_up2c_face_kernel<false>, FACE_ONE, single, io, dim3((unsigned)(p.N * fg)), 256, face_lds, s, p, TY, TX);
     rc = nm_check_hip(hipGetLastError(), "conv_up2c_face launch");
     if (rc) return rc;
     const long long items = (long long)p.N * ei;
     // (one output half: the ring's registers leave one wave per SIMD, and 1.5 items per SIMD then run in two rounds - measured
     //  slower than conv_up2c_edge_kernel on the 64 -> 32 layer, which keeps it)
     if (edge_p && Cout == 64) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else if (io == 3) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 3>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else if (io == 2) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 2>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else if (io == 1) hipLaunchKernelGGL((conv_up2c_edge_kernel<true, 1>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else if (single) hipLaunchKernelGGL(conv_up2c_edge_kernel<true>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else hipLaunchKernelGGL(conv_up2c_edge_kernel<false>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+    else launch_io(conv_up2c_edge_kernel<false>, EDGE_ONE, single, io, dim3((unsigned)((items + 3) / 4)), 256, 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
     return nm_check_hip(hipGetLastError(), "conv_up2c_edge launch");
 }

@@ -52,7 +52,11 @@ FWD_CASES = [
     (32, 64, 1, 1, 0, 32, 2, 0, 1, 1, "conv_f16s k1, two N tiles"),
     (64, 32, 1, 1, 0, 32, 2, 0, 1, 1, "conv_f16s k1, one N tile"),
     (128, 64, 3, 1, 1, 8, 2, 1, 0, 1, "conv_f16s fused upsample, fp32 in / bf16 out"),
-    (64, 32, 3, 1, 1, 16, 2, 1, 1, 1, "conv_up2c + face + edge"),
+    (64, 32, 3, 1, 1, 16, 2, 1, 1, 1, "conv_up2c<3> + face + edge"),
+    # size 8 is the smallest cube the family takes: every brick touches the shell, three frames put line groups across frame boundaries
+    # (fp32 in / bf16 out, conv_up2c<2>, is not here: at this size a third of the voxels are shell cells, whose sums the face / edge
+    #  kernels take from the twice-rounded values, and the GroupNorm scale then differs by 1.5e-5 from the fp32-storage run's)
+    (64, 32, 3, 1, 1, 8, 3, 1, 1, 0, "conv_up2c<1> + face + edge: bf16 in / fp32 out"),
     (32, 32, 2, 2, 0, 32, 2, 0, 1, 1, "conv_pool_f16q bf16 -> bf16"),
     (64, 64, 2, 2, 0, 32, 2, 0, 1, 0, "conv_pool_f16q bf16 -> fp32, two N tiles"),
     (32, 32, 2, 2, 0, 20, 2, 0, 1, 1, "conv_pool_f16q ragged bricks"),
@@ -86,9 +90,10 @@ def test_conv3d_storage16_is_bit_identical_to_fp32_storage(ctx, case):
         _set(ctx, 1, 0, 0)
     assert torch.isfinite(got.float()).all()
     want = ref.to(BF).float() if oh else ref
-    if up2 and ih:
-        # conv_up2c: the shell cells (a fine voxel on the volume border) are the main kernel's rounded value plus the face / edge
-        # kernels' correction, rounded again: exact inside, two roundings on the shell
+    if up2 and oh and (Cin, Cout) == (64, 32):
+        # conv_up2c (the one-product modes give it the 64 -> 32 layer only) with a bfloat16 output: the shell cells (a fine voxel on
+        # the volume border) are the main kernel's rounded value plus the face / edge kernels' correction, rounded again: exact
+        # inside, two roundings on the shell.  (An fp32 output is read-modify-written in fp32: exact everywhere, the branch below.)
         inner = (slice(None), slice(1, -1), slice(1, -1), slice(1, -1))
         assert torch.equal(got.float()[inner], want[inner]), "interior of the fused-upsample layer"
         e = (got.float() - ref).abs().max().item() / ref.abs().max().item()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Alternating A/B of the headline forward step (bench.py --no-extras --no-cpu-baseline, 64^3 T=16 B=4) under NM355_* switches, ONE gpurun call.
-# usage: bash tools/ab_forward_env.sh "<env A>" "<env B>" [rounds]      e.g. "NM355_UP2C_ALL=0" "NM355_UP2C_ALL=1"
+# usage: bash tools/ab_forward_env.sh "<env A>" "<env B>" [rounds]      e.g. "NM355_UP2Y=0" "NM355_UP2Y=1"
 cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 A="$1"; B="$2"; R=${3:-3}
 for i in $(seq $R); do

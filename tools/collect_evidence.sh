@@ -45,9 +45,8 @@ python3 tools/pmc_mfma.py $(find $E/pm -name "*.db" | head -1) $E/${R}_pmc_mfma.
 TBCMD="python3 bench.py --workload train --conv-mode bf16 --steps 2 --warmup 1 --no-extras --no-cpu-baseline"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $E/pmb -- $TBCMD > $E/pmb.log 2>&1
 python3 tools/pmc_mfma.py $(find $E/pmb -name "*.db" | head -1) $E/${R}_pmc_mfma_train_bf16.json > $E/pmc_mfma_train_bf16_summary.txt 2>&1
-# same-call A/Bs of the round (r06): MFMA shape of conv_up2c, hand-off latency by placement / store flavour, the rollout chain's forms +
-# where a step's time goes, encode, forward-step switches, R processes on one GPU
-bash tools/ab_mfma_shape.sh 7 > $E/${R}_mfma_shape_ab.txt 2>&1
+# same-call A/Bs of the round (r06): hand-off latency by placement / store flavour, the rollout chain's forms + where a step's time
+# goes, encode, forward-step switches, R processes on one GPU
 (hipcc -O3 -w --offload-arch=gfx950 tools/calib/hop_latency.hip -o /tmp/hop_latency && timeout 120 /tmp/hop_latency) > $E/${R}_hop_latency.txt 2>&1
 # conv_f16p2's deferred epilogue (built, slower, opt-in) against the shipped exposed one; in-kernel stamps of both (libnm355_stamps.so: make stamps)
 { bash tools/ab_p2_defer.sh; if [ -f neural_marionette_amd/libnm355_stamps.so ]; then for D in 0 1; do echo "in-kernel stamps, NM355_P2_DEFER=$D (tools/diag_f16p2_steps.py):"; NM355_P2_DEFER=$D python3 tools/diag_f16p2_steps.py 2>&1 | grep -v amdgpu.ids | head -5; done; fi; } > $E/${R}_p2_defer_ab.txt 2>&1
@@ -65,9 +64,8 @@ bash tools/ab_mfma_shape.sh 7 > $E/${R}_mfma_shape_ab.txt 2>&1
 python3 tools/time_encode_ab.py 2>&1 | grep -v amdgpu.ids > $E/${R}_encode_ab.txt
 {
   echo "headline forward step (bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline), alternating runs in one call on one device:"
-  bash tools/ab_forward_env.sh "NM355_UP2C_X16=0" "NM355_UP2C_X16=1" 3
+  bash tools/ab_forward_env.sh "NM355_UP2Y=0" "NM355_UP2Y=1" 3
   bash tools/ab_forward_env.sh "NM355_VRNN_POST_CHAIN=1" "NM355_VRNN_POST_CHAIN=2" 3
-  bash tools/ab_forward_env.sh "NM355_UP2C_ALL=0" "NM355_UP2C_ALL=1" 2
   bash tools/ab_forward_env.sh "NM355_FAST_DECODE=0" "NM355_FAST_DECODE=1" 3
 } > $E/${R}_forward_ab.txt 2>&1
 {
