@@ -45,7 +45,6 @@ NmLaunchState::NmLaunchState()
       lazy_res(env_int("NM355_LAZY_RES", 1)),         // 0: every residual sum is materialised by apply2 (A/B)
       adjust_split(env_int("NM355_ADJUST_SPLIT", 1)), // 0: the decoder's first 1x1 conv runs over the materialised 184-channel tensor in inference too (A/B)
       hg_core(env_int("NM355_HG_CORE", 1)),           // 0: the two lowest hourglass levels as separate launches in inference too (A/B)
-      f16p_dma(env_int("NM355_F16P_DMA", 0)),         // 1: conv_f16p2's producers copy the weights by LDS-DMA instead of through registers (A/B)
       clip_occ_mfma(env_int("NM355_CLIP_OCC_MFMA", 1)),  // 0: the clip-mean net's first-layer weight gradient as the dense all-frames kernel (A/B)
       vrnn_chain(env_int("NM355_VRNN_CHAIN", 1)),        // 0: the prior steps of a rollout as three launches per step instead of one persistent launch (A/B)
       wgrad_k2f16(env_int("NM355_WGRAD_K2F16", 1)),     // 0: the k2 s2 weight gradients on the fp32-MFMA kernel in every conv mode (A/B)
@@ -59,7 +58,6 @@ NmLaunchState::NmLaunchState()
       , f16r(env_int("NM355_F16R", 1))                      // 0: the one-product modes keep conv_f16p<SINGLE> on the 32-output-channel layers instead of conv_f16r (resident weights; A/B)
       , up2_mat(env_int("NM355_UP2_MAT", 1))                // 0: the one-product training forward keeps the fused-upsample staging on its 32-output layer instead of materialising the upsampled input for conv_f16r (A/B)
       , conv_wgs(env_int("NM355_CONV_WGS", 0))              // > 0: the persistent producer / consumer convs launch at most this many workgroups (co-residency A/B: CUs left free for the other queues)
-      , p2_defer(env_int("NM355_P2_DEFER", 0))              // 1: conv_f16p2 with one accumulator per tile and the epilogue deferred into the next brick's first step (A/B: slower)
       , fast_decode(env_int("NM355_FAST_DECODE", 1))        // 0: the persistent convs decode a brick's position with integer divisions instead of host-made reciprocal multiplications (A/B)
       , up2y(env_int("NM355_UP2Y", 1))                      // 0: the split-fp16 mode keeps the composite-weight kernel in all three axes (conv_up2c_x16_kernel) on the 64 -> 32 fused-upsample layer and conv_f16s on the 128 -> 64 one (A/B, the tests' reference); else: conv_up2y_kernel (products on the coarse grid, interpolated along y) on both
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)

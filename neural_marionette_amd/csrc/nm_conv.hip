@@ -53,7 +53,6 @@ struct ConvParams {
     unsigned st_m_sx, st_m_sy, st_m_pf;   // decode as multiplications (round 6); st_pf = 0: the host could not prove them exact, plain divisions
     const float* in_alt; const unsigned char* in_map;   // brick-sparse input (TensorRef::alt / brickmap), conv_pool_f16s only
     const float* in2; const float* in2_scale; const float* in2_shift; float in2_slope;   // un-materialised residual sum (TensorRef::p2 ...), conv_pool_f16s only
-    int wdma;                     // conv_f16p2: the producers copy the weights global -> LDS by LDS-DMA instead of through registers (A/B switch)
     int in_h, out_h;              // 16-bit storage (conv mode 4): the input / output tensor is bfloat16 (kernels take it as the IO template bits 1 / 2)
 #ifdef NM_DIAG
     unsigned long long* stamps;   // diagnostic build only: per-block phase timestamps
@@ -2189,22 +2188,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 //     the barrier that publishes them; operands one tap (12 MFMAs) ahead, double buffered.
 //   LDS: halo [2][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [2][9 taps][4 planes][64] x 16 B, GroupNorm scratch, bias.
 // IO: bit 0 = bfloat16 input (a producer piece is then an 8-byte load of the same four channels), bit 1 = bfloat16 output
-// DEFER (round 6; NM355_P2_DEFER=1, NOT the default - built, correct, slower): in-kernel stamps (tools/diag_f16p2_steps.py) put the
-// exposed epilogue at 7 800 of a 64-channel brick's 58 000 cycles (24 % at Cin = 32) - 128 values per lane to combine, store, square,
-// sum over 32 lanes (320 DPP adds) and park, all on the vector ALU with the matrix pipe idle.  With ONE accumulator per tile
-// (conv_up2c_x16's identity x w 2^11 = x_hi (2^11 w_hi) + x_hi w_lo' + x_lo' w_hi, w_hi scaled in place behind its unscaled uses) the
-// accumulators are 64 registers, the finished brick's outputs move to 64 others (one v_pk_fma per pair with the bias, exposed: ~700
-// cycles) and conv_f16p's gap-interleaved epilogue runs inside the NEXT brick's first step (second copy of the tap stream, zero C operand
-// for its first MFMAs, no extra barrier per brick).  Same results as the two-accumulator form to the op tests' 2e-5.  Measured
-// (profiles/r06_p2_defer_ab.txt): 64 -> 64 @32^3 1.31-1.33 -> 1.36-1.43 ms, 128 -> 128 @16^3 0.63 -> 0.68: the interleaved pieces are only 40 %
-// hidden (the first step of a brick grows by 4 650 cycles for 7 400 saved: the MFMA wave issues in order, its stores and DPP adds
-// share the SIMD's issue with a producer wave), the single-accumulator stream itself is 1-2 % slower per tap group, and at 256
-// registers the brick decode's hoisted division constants spill (a scratch reload per step).  What would be left after moving the
-// decode to the producers (an LDS ring of brick origins): <= 5 % of this kernel.  The exposed epilogue got the cheap part instead:
-// its arithmetic on value pairs (v_pk_*), 8 900 -> 8 160 stamped cycles.
-template <bool SINGLE = false, int IO = 0, bool DEFER = false>
+// The epilogue stays exposed (7 800 of a 64-channel brick's 58 000 cycles).  A variant with one accumulator per tile and the finished
+// brick's epilogue interleaved into the next brick's first step was built (round 6) and was slower, 1.31-1.33 -> 1.36-1.43 ms at
+// 64 -> 64 @32^3; it is retired, the account and the evidence's place are in DESIGN_HISTORY.md.
+template <bool SINGLE = false, int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
-    static_assert(!DEFER || !SINGLE, "the deferred epilogue exists for the three-product form");
     constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
     constexpr unsigned EB = IH ? 2u : 4u;                           // bytes per input element
     constexpr int HV = 600, ZP = 100, HX = 10;
@@ -2347,27 +2335,20 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             w_src[i] = (unsigned)(((size_t)t * C16 * 4 + r) * plane + lane) * 16u;
             w_dst[i] = (unsigned)(t * 256 + r * 64 + lane) * 16u;
         }
-        // (wdma: the same nine 1-KiB pieces by LDS-DMA straight into weight buffer `buf` - no registers, no ds_write; the counted waits
-        // are the same, a DMA instruction counts on vmcnt like the load it replaces.  The target buffer is free at issue time: it was
-        // read during the previous tap group, which ended at the barrier just passed.)
-        const bool wdma = p.wdma != 0;
-        auto load_b_group = [&](int cg, int cb, int g, int buf) {
-            const float* base = reinterpret_cast<const float*>(w8 + ((size_t)(9 * g) * C16 * 4 + (size_t)cb * 4) * plane + cg * 64);
-            if (wdma) {
+        auto load_b_group = [&](int cg, int cb, int g) {
+            const char* base = reinterpret_cast<const char*>(w8 + ((size_t)(9 * g) * C16 * 4 + (size_t)cb * 4) * plane + cg * 64);
+            // the addresses first, then the loads back to back, and nothing scheduled across the group or into the stores below: with the
+            // address additions between the loads the three-product layers measured 0.5-1 % slower (profiles/p2_retire_ab.txt)
+            const float* src[NW];
 #pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    const int j = SINGLE ? min(pw + 4 * i, 17) : pw + 4 * i;
-                    const int t = SINGLE ? j >> 1 : j >> 2, r = SINGLE ? j & 1 : j & 3;
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(base) + w_src[i]),
-                                                     (__attribute__((address_space(3))) void*)(ldb + buf * GB + t * 256 + r * 64), 16, 0, 0);
-                }
-            } else {
+            for (int i = 0; i < NW; ++i) src[i] = reinterpret_cast<const float*>(base + w_src[i]);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < NW; ++i) wreg[i] = load16_untracked(base, w_src[i]);
-            }
+            for (int i = 0; i < NW; ++i) wreg[i] = load16_untracked(src[i]);
+            __builtin_amdgcn_sched_barrier(0);
         };
         auto store_b_group = [&](int buf) {
-            if (wdma) return;
+            __builtin_amdgcn_sched_barrier(0);
             char* lbase = reinterpret_cast<char*>(ldb + buf * GB);
 #pragma unroll
             for (int i = 0; i < NW; ++i) *reinterpret_cast<f32x4*>(lbase + w_dst[i]) = wreg[i];
@@ -2380,7 +2361,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
         unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first weight group in the open, loads of the second tile in flight
-        load_b_group(cur.w.cg, 0, 0, 0);
+        load_b_group(cur.w.cg, 0, 0);
         load_affine(cur.w, 0);
         { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         NM_PRODUCER2_WAIT(0);
@@ -2402,7 +2383,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             // tap group 0: weights of this step's group 1 (into the buffer group 2 of the last step was read from); pieces 0-2.
             // Everything older than the 9 weight loads has landed after the first wait.
             NM_PSTAMP(0);
-            load_b_group(cur.w.cg, cur.cb, 1, gpar ^ 1);
+            load_b_group(cur.w.cg, cur.cb, 1);
             if constexpr (SINGLE) { NM_PRODUCER2_WAIT(5); } else { NM_PRODUCER2_WAIT(9); }      // (NW weight loads are the youngest)
             NM_PSTAMP(1);
             static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
@@ -2412,7 +2393,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             lds_barrier(); gpar ^= 1;
             NM_PSTAMP(3);
             // tap group 1: weights of this step's group 2; pieces 3-7
-            load_b_group(cur.w.cg, cur.cb, 2, gpar ^ 1);
+            load_b_group(cur.w.cg, cur.cb, 2);
             static_for<5>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 3>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 3>{}); });
             NM_PSTAMP(4);
             NM_PRODUCER2_WAIT(5);                                   // the weight loads: 5 piece loads are younger
@@ -2421,7 +2402,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             lds_barrier(); gpar ^= 1;
             NM_PSTAMP(6);
             // tap group 2: weights of the next step's group 0; pieces 8-9; the halo tile is complete at this barrier
-            load_b_group(s1.w.cg, s1.cb, 0, gpar ^ 1);
+            load_b_group(s1.w.cg, s1.cb, 0);
             static_for<2>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 8>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 8>{}); });
             load_affine(s2.w, s2.cb);                               // (sc / sh are free: piece 9 was their last user)
             NM_PRODUCER2_WAIT(0);
@@ -2432,7 +2413,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 #ifdef NM_DIAG
             ++step_no;
 #endif
-            if constexpr (!DEFER) { if (cur.cb == C16 - 1) lds_barrier(); }      // the MFMA waves' epilogue barrier of a finished brick
+            if (cur.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
             if (!has1) break;
             cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
             m_cvt = m_ld; hb ^= 1;
@@ -2450,181 +2431,6 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
         arow0 = z * ZP + (2 * wave) * HX + x;
     }
     const int vx = ((((0x96 >> (l31 >> 2)) & 1) << 2) + (l31 & 3)), vz = l31 >> 3;
-    if constexpr (DEFER) {
-        // ---- one accumulator per tile, the finished brick's epilogue inside the next brick's first step ----------------------------
-        constexpr int LO = 2 * HV * 16, YO = HX * 16;
-        f32x16 acc[2][2], outv[2][2];                               // outv: the pending brick's outputs, then its partial sums in place
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { acc[mt][nt][r] = 0.f; outv[mt][nt][r] = 0.f; }
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        size_t esb = 0;                                             // pending brick: element index of (its first voxel, cout group) - wave-uniform
-        const unsigned lane_off = (unsigned)(((vz * p.OH + 2 * wave) * p.OW + vx) * p.Cout + 4 * h);   // this lane's voxel and channel quad inside a brick
-        size_t epart = 0, ppart = 0;                      // pending brick: its outputs' place / its partial sums' place; ppart: of the sums red[] holds
-                                            // element index of (pending brick, this lane's voxel, mt = 0, nt = 0, k4 = 0)
-        const size_t erow = (size_t)p.OW * p.Cout;                  // mt = 0 -> 1
-        auto epi_store = [&](auto E) {                              // store e = (2 nt + mt) * 4 + k4 of the 16 per lane
-            constexpr int e = decltype(E)::value, nt = e >> 3, mt = (e >> 2) & 1, k4 = e & 3;
-            unsigned lo = lane_off;
-            asm volatile("" : "+v"(lo));                            // (the 16 addresses are loop invariants: hoisted, they are spilled and reloaded in the gaps)
-            nm_st4<OH>(p.out, esb + (mt ? erow : (size_t)0) + (size_t)(lo + (unsigned)(nt * 32 + 8 * k4)),
-                       f32x4{outv[mt][nt][4 * k4], outv[mt][nt][4 * k4 + 1], outv[mt][nt][4 * k4 + 2], outv[mt][nt][4 * k4 + 3]});
-        };
-        auto epi_sum_local = [&](auto R) {                          // pair R of tile column nt: sums / sums of squares over the two row tiles, in place
-            constexpr int nt = decltype(R)::value >> 3, r = 2 * (decltype(R)::value & 7);
-            const f32x2 a = f32x2{outv[0][nt][r], outv[0][nt][r + 1]}, b = f32x2{outv[1][nt][r], outv[1][nt][r + 1]};
-            const f32x2 s = a + b, q = a * a + b * b;
-            outv[0][nt][r] = s[0]; outv[0][nt][r + 1] = s[1]; outv[1][nt][r] = q[0]; outv[1][nt][r + 1] = q[1];
-        };
-        auto epi_sum_lanes = [&](auto I) {                          // DPP step (i >> 6) of value (i & 63) = 32 m + 16 nt + r
-            constexpr int i = decltype(I)::value, st = i >> 6, v = i & 63, m = v >> 5, nt = (v >> 4) & 1, r = v & 15;
-            constexpr int ctrl = st == 0 ? 0xB1 : st == 1 ? 0x4E : st == 2 ? 0x141 : st == 3 ? 0x140 : 0x142;
-            constexpr int rows = st == 4 ? 0xa : 0xf;
-            const float x = outv[m][nt][r];
-            outv[m][nt][r] = x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rows, 0xf, true));
-        };
-        auto epi_red = [&](auto R) {                                // lanes 16 / 48 park (sum, sum of squares) of channel c(nt, r, h)
-            constexpr int nt = decltype(R)::value >> 4, r = decltype(R)::value & 15;
-            int ln = lane;
-            asm volatile("" : "+v"(ln));                            // (addresses made here: as loop invariants they are hoisted, and then spilled)
-            if (p.part && (ln & 31) == 16) *reinterpret_cast<f32x2*>(red + (wave * 64 + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5)) * 2) = f32x2{outv[0][nt][r], outv[1][nt][r]};
-        };
-        auto epi_part = [&]() {                                     // behind a barrier: 64 threads sum the four wave partials
-            int tq = tid;
-            asm volatile("" : "+v"(tq));
-            if (p.part && tq < 64) {
-                float a = 0.f, b = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { a += red[(q * 64 + tq) * 2]; b += red[(q * 64 + tq) * 2 + 1]; }
-                float* dp = p.part + ppart + tq * 2;
-                dp[0] = a; dp[1] = b;
-            }
-        };
-        auto epi_take = [&](const Work& w) {                        // outputs of the brick just accumulated (exposed: 64 packed FMAs)
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-            const float* lb = lbias + w.cg * 64 + 4 * (ln >> 5);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4) {
-                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(lb + nt * 32 + 8 * k4);
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int e = 0; e < 4; e += 2) {
-                            const f32x2 a2 = f32x2{acc[mt][nt][4 * k4 + e], acc[mt][nt][4 * k4 + e + 1]};
-                            const f32x2 v2 = __builtin_elementwise_fma(a2, f32x2{1.0f / NM_SPLIT_SCALE, 1.0f / NM_SPLIT_SCALE}, f32x2{b4[e], b4[e + 1]});
-                            outv[mt][nt][4 * k4 + e] = v2[0]; outv[mt][nt][4 * k4 + e + 1] = v2[1];
-                        }
-                }
-            epart = (((size_t)w.n * nbr + ((w.oz0 >> 2) * nby + (w.oy0 >> 3)) * nbx + (w.ox0 >> 3)) * p.Cout + w.cg * 64) * 2;
-            esb = ((((size_t)w.n * p.OD + w.oz0) * p.OH + w.oy0) * p.OW + w.ox0) * (size_t)p.Cout + w.cg * 64;
-        };
-
-        Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
-        int hb = 0, gpar = 0;
-        lds_barrier();                                              // the producers' prologue
-        const unsigned vb0 = (unsigned)(size_t)(ldb + h * 64 + l31);
-        half8 ah0[2], al0[2], ah1[2], al1[2], bh0[2], bh1[2], bl0[2], bl1[2];
-        {
-            const unsigned va = (unsigned)(size_t)(ldh + h * HV + arow0);
-            ah0[0] = lds_read16_untracked<0>(va); al0[0] = lds_read16_untracked<LO>(va);
-            ah1[0] = lds_read16_untracked<YO>(va); al1[0] = lds_read16_untracked<LO + YO>(va);
-        }
-        bool pending = false, part_due = false;
-        for (;;) {
-            Step nxt = cur;
-            const bool has_next = advance(nxt);
-            if (part_due) { epi_part(); part_due = false; }
-            const bool run_epi = pending;
-            const unsigned va = (unsigned)(size_t)(ldh + hb * 4 * HV + h * HV + arow0);
-            const unsigned van = (unsigned)(size_t)(ldh + (hb ^ 1) * 4 * HV + h * HV + arow0);
-            const unsigned vbe = vb0 + (unsigned)(gpar * GB * 16), vbo = vb0 + (unsigned)((gpar ^ 1) * GB * 16);
-            NM_PSTAMP(0);
-            auto stream = [&](auto EPI) {
-                constexpr bool with_epi = decltype(EPI)::value;
-                static_for<27>([&](auto TT) {
-                    constexpr int tt = decltype(TT)::value, g = tt / 9, t = tt % 9, i = tt & 1, j = i ^ 1;
-                    const unsigned vb = (g & 1) ? vbo : vbe;
-                    constexpr int BT = t * 256 * 16;
-                    if constexpr (t == 0) {
-                        bh0[i] = lds_read16_untracked<BT>(vb); bh1[i] = lds_read16_untracked<BT + 32 * 16>(vb);
-                        bl0[i] = lds_read16_untracked<BT + 128 * 16>(vb); bl1[i] = lds_read16_untracked<BT + 160 * 16>(vb);
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)"
-                                 : "+v"(ah0[i]), "+v"(al0[i]), "+v"(ah1[i]), "+v"(al1[i]), "+v"(bh0[i]), "+v"(bh1[i]), "+v"(bl0[i]), "+v"(bl1[i]) :: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    constexpr int u = tt + 1, ug = (u < 27) ? u / 9 : 0, ut = (u < 27) ? u % 9 : 0;
-                    constexpr int AO = (ug * ZP + (ut / 3) * HX + (ut % 3)) * 16;
-                    constexpr bool anext = u < 27, bnext = t < 8;
-                    constexpr int BN = (t + 1) * 256 * 16;
-                    constexpr bool z = with_epi && tt == 0;         // a new brick: C = 0 instead of cleared accumulators
-                    auto gap = [&](auto SUB) {
-                        constexpr int q = tt * 12 + decltype(SUB)::value;
-                        if constexpr (with_epi) {
-                            if constexpr (q >= 4 && q < 36 && (q & 1) == 0) epi_store(ic<((q - 4) >> 1) & 15>{});
-                            if constexpr (q >= 36 && q < 52) epi_sum_local(ic<(q - 36) & 15>{});
-                            if constexpr (q >= 52 && q < 212) { epi_sum_lanes(ic<(2 * (q - 52)) % 320>{}); epi_sum_lanes(ic<(2 * (q - 52) + 1) % 320>{}); }
-                            if constexpr (q >= 214 && q < 246) epi_red(ic<(q - 214) & 31>{});
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    };
-#define NM_MFMA3(ACC, B, A, Z) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(B, A, (Z) ? zero16 : ACC, 0, 0, 0); __builtin_amdgcn_sched_barrier(0)
-                    // the cross products first: 2^11 w_hi of this tap is made in their gaps
-                    // the products with the unscaled w_hi first; it becomes 2^11 w_hi IN PLACE behind them (exact for |w| < 32; larger
-                    // weights overflow into the range guard like any fp16 overflow), in the gaps of the cross products
-                    NM_MFMA3(acc[0][0], bh0[i], al0[i], z); if constexpr (anext) ah0[j] = lds_read16_untracked<AO>(va); gap(ic<0>{});
-                    NM_MFMA3(acc[0][1], bh1[i], al0[i], z); if constexpr (anext) al0[j] = lds_read16_untracked<AO + LO>(va); gap(ic<1>{});
-                    NM_MFMA3(acc[1][0], bh0[i], al1[i], z); if constexpr (anext) ah1[j] = lds_read16_untracked<AO + YO>(va); gap(ic<2>{});
-                    NM_MFMA3(acc[1][1], bh1[i], al1[i], z); if constexpr (anext) al1[j] = lds_read16_untracked<AO + LO + YO>(va); gap(ic<3>{});
-                    NM_MFMA3(acc[0][0], bl0[i], ah0[i], false); if constexpr (bnext) bh0[j] = lds_read16_untracked<BN>(vb); gap(ic<4>{});
-                    NM_MFMA3(acc[0][1], bl1[i], ah0[i], false); if constexpr (bnext) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb); gap(ic<5>{});
-                    NM_MFMA3(acc[1][0], bl0[i], ah1[i], false); if constexpr (bnext) bl0[j] = lds_read16_untracked<BN + 128 * 16>(vb); bh0[i] = bh0[i] * (_Float16)NM_SPLIT_SCALE; gap(ic<6>{});
-                    NM_MFMA3(acc[1][1], bl1[i], ah1[i], false); if constexpr (bnext) bl1[j] = lds_read16_untracked<BN + 160 * 16>(vb); bh1[i] = bh1[i] * (_Float16)NM_SPLIT_SCALE; gap(ic<7>{});
-                    NM_MFMA3(acc[0][0], bh0[i], ah0[i], false); gap(ic<8>{});
-                    NM_MFMA3(acc[0][1], bh1[i], ah0[i], false); gap(ic<9>{});
-                    NM_MFMA3(acc[1][0], bh0[i], ah1[i], false); gap(ic<10>{});
-                    NM_MFMA3(acc[1][1], bh1[i], ah1[i], false); gap(ic<11>{});
-                    if constexpr (t == 8) {
-                        NM_PSTAMP(1 + 2 * g);
-                        asm volatile("s_barrier" ::: "memory");
-                        __builtin_amdgcn_sched_barrier(0);
-                        NM_PSTAMP(2 + 2 * g);
-                    }
-                });
-            };
-            if (run_epi) stream(std::true_type{}); else stream(std::false_type{});
-            gpar ^= 1;
-            if (run_epi) { pending = false; part_due = true; ppart = epart; }
-            if (cur.cb == C16 - 1) { NM_PSTAMP(8); epi_take(cur.w); pending = true; NM_PSTAMP(13); }
-            // the next step's tile is complete since the barrier that ended tap group 2: its first tap's A operands (slot 0)
-            if (has_next) {
-                ah0[0] = lds_read16_untracked<0>(van); al0[0] = lds_read16_untracked<LO>(van);
-                ah1[0] = lds_read16_untracked<YO>(van); al1[0] = lds_read16_untracked<LO + YO>(van);
-            }
-            NM_PSTAMP(7);
-#ifdef NM_DIAG
-            ++step_no;
-#endif
-            if (!has_next) break;
-            cur = nxt; hb ^= 1;
-        }
-        // ---- drain: the last brick's epilogue in the open (the producers have left)
-        if (part_due) epi_part();
-        lds_barrier();
-        static_for<16>([&](auto E) { epi_store(E); });
-        static_for<16>([&](auto R) { epi_sum_local(R); });
-        static_for<320>([&](auto I) { epi_sum_lanes(I); });
-        static_for<32>([&](auto R) { epi_red(R); });
-        lds_barrier();
-        ppart = epart;
-        epi_part();
-        return;
-    }
     f32x16 acc[2][2], accl[2][2];
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -2781,9 +2587,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 //   * the MFMA waves keep operands two taps ahead (three register sets, counted lgkmcnt waits): a tap is only four MFMAs.
 // Arithmetic per output element (k order: channel chunk outer, tap inner; epilogue) is conv_f16p2<SINGLE>'s: bit-identical results.
 //   LDS: halo [2][h0 | h1][600] x 16 B, weights [2][27 taps][h0 | h1][64] x 16 B, GroupNorm scratch, bias: 148 KB + bias.
-// DBG (diagnostic instantiations, NM355_Q2_DBG): 1 no MFMAs, 2 producers only keep the barriers, 3 no epilogue stores, 4 no weight copies, 5 no input staging,
-// 6 = 2 + no operand reads inside the tap loop, 7 = 2 + no epilogue, 8 input pieces loaded but not converted / stored, 9 converted / stored but not loaded
-template <int IO = 0, int DBG = 0>
+template <int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
     constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
     constexpr unsigned EB = IH ? 2u : 4u;                           // bytes per input element
@@ -2858,7 +2662,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         // two register sets for the input pieces (and their affine): a tile's loads are issued TWO producer iterations before its
         // conversion - one full step of cover.  (With one set the loads of step s + 2 were issued between the conversions of step
         // s + 1 and consumed at the top of the next iteration: half a step of cover for an HBM round trip; loads alone or conversions
-        // alone cost the kernel nothing, together +0.15 ms on 64 -> 64 @32^3 - tools/diag_f16q2.py variants 8 / 9.)
+        // alone cost the kernel nothing, together +0.15 ms on 64 -> 64 @32^3 - DESIGN 5.)
         f32x4 raw[2][NP], sc[2][NA / 2], sh[2][NA / 2], wreg[NWL];
 #pragma unroll
         for (int i = 0; i < NWL; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -2949,25 +2753,14 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         const unsigned wst_t = (unsigned)((size_t)C16 * 4 * plane * 16), wst_r = (unsigned)(plane * 16);
         const unsigned wsrc0 = (unsigned)(pw >> 1) * wst_t + (unsigned)(pw & 1) * wst_r + (unsigned)lane * 16u, wstep = 2u * wst_t;
         const int ilast = pw < 2 ? 13 : 12;
-        const bool wdma = p.wdma != 0;
-        auto load_w = [&](int cg, int cb, int buf) {
+        auto load_w = [&](int cg, int cb) {
             const float* base = reinterpret_cast<const float*>(w8 + ((size_t)cb * 4) * plane + cg * 64);
-            if (wdma) {
-                static_for<NWL>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    const int ii = i < 13 ? i : ilast;
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(base) + wsrc0 + (unsigned)ii * wstep),
-                                                     (__attribute__((address_space(3))) void*)(ldb + buf * WB + pw * 64 + ii * 256), 16, 0, 0);
-                });
-            } else {
-                static_for<NWL>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    wreg[i] = load16_untracked(base, wsrc0 + (unsigned)(i < 13 ? i : ilast) * wstep);
-                });
-            }
+            static_for<NWL>([&](auto I) {
+                constexpr int i = decltype(I)::value;
+                wreg[i] = load16_untracked(base, wsrc0 + (unsigned)(i < 13 ? i : ilast) * wstep);
+            });
         };
         auto store_w = [&](int buf) {
-            if (wdma) return;
             half8* dst0 = ldb + buf * WB + pw * 64 + lane;
             static_for<13>([&](auto I) {
                 constexpr int i = decltype(I)::value;
@@ -2984,7 +2777,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         unsigned m1 = inside_mask(cur.w), m2, m3;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first step's weights in the open; the tiles of steps s1 (set 0) and s2 (set 1) in flight
-        load_w(cur.w.cg, 0, 0);
+        load_w(cur.w.cg, 0);
         load_affine(cur.w, 0, ic<0>{});
         { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
         NM_Q2_WAIT_SET(0, 0, 0);
@@ -3006,19 +2799,17 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
             m3 = (s3.w.n != s2.w.n || s3.w.oz0 != s2.w.oz0 || s3.w.oy0 != s2.w.oy0 || s3.w.ox0 != s2.w.ox0) ? inside_mask(s3.w) : m2;
             const float* b3 = tile_base(s3.w, s3.cb);
             // weights of step s1 into the other buffer (read last during the step before this one)
-            if constexpr (DBG != 2 && DBG != 4 && DBG < 6) load_w(s1.w.cg, s1.cb, hb ^ 1);
+            load_w(s1.w.cg, s1.cb);
             // in order: [tile s1 -> this set][tile s2 -> other set][these NWL weight loads]: this set has landed once only the
             // other set's loads and the weight loads are outstanding
             NM_Q2_WAIT_SET(set, 23, 26);
             fix_affine(SET);
-            if constexpr (DBG != 2 && DBG != 5 && DBG < 6) {
-                static_for<NP>([&](auto K) { if constexpr (DBG != 8) convert(hb ^ 1, m1, K, SET); if constexpr (DBG != 9) load_piece(b3, m3, K, SET); });
-                if constexpr (DBG != 9) load_affine(s3.w, s3.cb, SET);
-            }
+            static_for<NP>([&](auto K) { convert(hb ^ 1, m1, K, SET); load_piece(b3, m3, K, SET); });
+            load_affine(s3.w, s3.cb, SET);
             NM_Q2_WAIT_WP(9, 12);                                   // the weight loads: only this iteration's NP + NA loads are younger
-            if constexpr (DBG != 2 && DBG != 4 && DBG < 6) store_w(hb ^ 1);
+            store_w(hb ^ 1);
             lds_barrier();                                          // publishes tile + weights of s1; the MFMA waves are done with `cur`
-            if (cur.cb == C16 - 1 && DBG != 7) lds_barrier();       // the MFMA waves' epilogue barrier of a finished brick
+            if (cur.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
             if (!has1) return false;
             cur = s1; s1 = s2; has1 = has2; s2 = s3; has2 = has3; has3 = has3 && advance(s3);
             m1 = m2; m2 = m3; hb ^= 1;
@@ -3065,21 +2856,20 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         static_for<27>([&](auto TT) {
             constexpr int tt = decltype(TT)::value, i = tt % 3, u = tt + 2, j = u % 3;
             // in-order LDS returns: at most the four reads of tap tt + 1 may still be outstanding
-            if constexpr (tt < 26 && DBG != 6) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a0[i]), "+v"(a1[i]), "+v"(b0[i]), "+v"(b1[i]) :: "memory");
+            if constexpr (tt < 26) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(a0[i]), "+v"(a1[i]), "+v"(b0[i]), "+v"(b1[i]) :: "memory");
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0[i]), "+v"(a1[i]), "+v"(b0[i]), "+v"(b1[i]) :: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            constexpr bool more = u < 27 && DBG != 6;
+            constexpr bool more = u < 27;
             constexpr int AO = more ? ((u / 9) * ZP + ((u % 9) / 3) * HX + (u % 3)) * 16 : 0;
             constexpr int BO = more ? u * 128 * 16 : 0;
-#define NM_Q2_MFMA(ACC, B, A) if constexpr (DBG != 1) { NM_MFMA2(ACC, B, A); } else { asm volatile("" :: "v"(B), "v"(A)); __builtin_amdgcn_sched_barrier(0); }
-            NM_Q2_MFMA(acc[0][0], b0[i], a0[i]); if constexpr (more) a0[j] = lds_read16_untracked<AO>(va);
-            NM_Q2_MFMA(acc[0][1], b1[i], a0[i]); if constexpr (more) a1[j] = lds_read16_untracked<AO + YO>(va);
-            NM_Q2_MFMA(acc[1][0], b0[i], a1[i]); if constexpr (more) b0[j] = lds_read16_untracked<BO>(vb);
-            NM_Q2_MFMA(acc[1][1], b1[i], a1[i]); if constexpr (more) b1[j] = lds_read16_untracked<BO + 32 * 16>(vb);
+            NM_MFMA2(acc[0][0], b0[i], a0[i]); if constexpr (more) a0[j] = lds_read16_untracked<AO>(va);
+            NM_MFMA2(acc[0][1], b1[i], a0[i]); if constexpr (more) a1[j] = lds_read16_untracked<AO + YO>(va);
+            NM_MFMA2(acc[1][0], b0[i], a1[i]); if constexpr (more) b0[j] = lds_read16_untracked<BO>(vb);
+            NM_MFMA2(acc[1][1], b1[i], a1[i]); if constexpr (more) b1[j] = lds_read16_untracked<BO + 32 * 16>(vb);
         });
         asm volatile("s_barrier" ::: "memory");                     // the producers publish the next step's tile and weights
         __builtin_amdgcn_sched_barrier(0);
-        if (cur.cb == C16 - 1 && (DBG != 7 || acc[0][0][0] == 12345.678f)) {
+        if (cur.cb == C16 - 1) {
             // ---- epilogue of the finished brick (exposed): transposed accumulators -> 16-byte stores, DPP partial sums
             const Work& w = cur.w;
 #pragma unroll
@@ -3106,8 +2896,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
                             }
                             acc[mt][nt][4 * k4 + e] = 0.f; acc[mt][nt][4 * k4 + e + 1] = 0.f;
                         }
-                        if constexpr (DBG != 3) nm_st4<OH>(p.out, dst + 8 * k4, v);
-                        else if (v[0] == 12345.678f) nm_st4<OH>(p.out, dst + 8 * k4, v);
+                        nm_st4<OH>(p.out, dst + 8 * k4, v);
                     }
                 }
                 if (p.part) {
@@ -3659,17 +3448,17 @@ int launch_f16p(const ConvParams& p, int work_items, hipStream_t s) {
     return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s) : launch_f16p_impl<false>(p, work_items, s);
 }
 
-template <bool SINGLE, int IO = 0, bool DEFER = false>
+template <bool SINGLE, int IO = 0>
 int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s) {
     const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO, DEFER>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s);
 }
 // the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
-template <int IO, int DBG = 0>
+template <int IO>
 int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s) {
     const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)2 * 27 * 2 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
     if (lds_bytes > 160 * 1024) { nm_set_error("conv_f16q2: %d output channels exceed the LDS budget", p.Cout); return NM_ERR_UNSUPPORTED; }
-    return launch_persistent<&conv_f16q2_kernel<IO, DBG>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16q2_kernel<IO>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s);
 }
 // the one-product modes' kernel for the 32-output-channel layers (conv_f16r_kernel: resident weights); Cin = 16 C16T
 template <int IO, int C16T>
@@ -3680,16 +3469,6 @@ int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s) {
 int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
     if (nm_ls().single && nm_ls().f16q2 && (io == 0 || io == 3) && p.Cout <= 1024) {
-#ifdef NM_Q2_DIAG
-        static const int dbg = getenv("NM355_Q2_DBG") ? atoi(getenv("NM355_Q2_DBG")) : 0;      // ablations of tools/diag_f16q2.py (diagnostic build only)
-        if (io == 3) switch (dbg) {
-            case 1: return launch_f16q2_impl<3, 1>(p, work_items, s); case 2: return launch_f16q2_impl<3, 2>(p, work_items, s);
-            case 3: return launch_f16q2_impl<3, 3>(p, work_items, s); case 4: return launch_f16q2_impl<3, 4>(p, work_items, s);
-            case 5: return launch_f16q2_impl<3, 5>(p, work_items, s); case 6: return launch_f16q2_impl<3, 6>(p, work_items, s);
-            case 7: return launch_f16q2_impl<3, 7>(p, work_items, s); case 8: return launch_f16q2_impl<3, 8>(p, work_items, s);
-            case 9: return launch_f16q2_impl<3, 9>(p, work_items, s); default: break;
-        }
-#endif
         return io ? launch_f16q2_impl<3>(p, work_items, s) : launch_f16q2_impl<0>(p, work_items, s);
     }
     if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
@@ -3697,7 +3476,6 @@ int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s) {
         return launch_f16p2_impl<true, 3>(p, work_items, s);
     }
     if (nm_ls().single) return launch_f16p2_impl<true>(p, work_items, s);
-    if (nm_ls().p2_defer) return launch_f16p2_impl<false, 0, true>(p, work_items, s);      // (A/B: the deferred epilogue, slower)
     return launch_f16p2_impl<false>(p, work_items, s);
 }
 
@@ -3892,7 +3670,6 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
     p.st_sx = p.st_sy = p.st_pf = p.st_m_sx = p.st_m_sy = p.st_m_pf = 0;
     p.in_alt = in.alt; p.in_map = in.brickmap;
     p.in2 = in.p2; p.in2_scale = in.scale2; p.in2_shift = in.shift2; p.in2_slope = in.slope2;
-    p.wdma = nm_ls().f16p_dma;
     p.in_h = in.h; p.out_h = out_h;
     if (in.p2 && !(nm_conv_pool16_eligible(in.C, g.OD, g.OH, g.OW, w_packed16 != nullptr) && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2 && !in.brickmap)) {
         nm_set_error("conv: an un-materialised residual sum can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG;

@@ -259,21 +259,6 @@ def _forward_body(ctx, case):
         assert es <= 1.0 and eh <= 1.0, f"{_fid(case)}: gamma = 1, beta = 0: scale {es:.2f} ulp from float(rstd), shift {eh:.2f} of its bound"
 
 
-def test_forward_bits_and_statistics_deferred_epilogue_variant():
-    """NM355_P2_DEFER=1 (conv_f16p2 with the finished brick's epilogue inside the next brick's first step; read when a context is
-    created): a partial dropped or written twice by the deferred epilogue moves the statistics by a few items - the brick-aligned and
-    the ragged 64-output-channel cases again, split-fp16 modes, on the offset sets."""
-    with TG._switches({"NM355_P2_DEFER": "1"}):
-        c = TG._fresh_ctx()
-    try:
-        for spec in CONV_SPECS:
-            if spec[2] == 64 and spec[3] == 3:
-                for data in ("sa", "r8", "r30"):
-                    _forward_body(c, (spec, data, 0, 0, (1, 2)))
-    finally:
-        c.close()
-
-
 @pytest.mark.parametrize("G,Cout,N", OCC_CASES)
 def test_first_layer_bits_and_statistics(ctx, G, Cout, N):
     """conv5 on cat[occ, coords] with integer weights on the occupancy channel and zero weights on the coordinate channels (the

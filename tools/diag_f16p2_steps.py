@@ -45,8 +45,6 @@ for (Cin, Cout, size, N) in [(64, 64, 32, 64), (32, 64, 32, 64), (32, 32, 64, 16
     dp = lambda a, b_: ((pr[:, :, b_] - pr[:, :, a])[okp]).mean()
     print(f"  producer 4: wait weights {dp(0,1):6.0f} cvt 0-3 + store {dp(1,2):6.0f} barrier {dp(2,3):6.0f} | cvt 4-9 {dp(3,4):6.0f} wait+store {dp(4,5):6.0f} barrier {dp(5,6):6.0f} | group 2 {dp(6,7):6.0f} barrier {dp(7,8):6.0f}")
     e = s[:, 4:40, 0, :]; oke = (e[:, :, 8] > 0) & (e[:, :, 13] > 0) & (e[:, :, 7] > 0)
-    if oke.any() and not (e[:, :, 9][oke] > 0).any():      # deferred epilogue (NM355_P2_DEFER=1): only the take is exposed
-        print(f"  deferred epilogue: exposed take (combine + bias into the pending set) {((e[:, :, 13] - e[:, :, 8])[oke]).mean():6.0f}")
-    elif oke.any():
+    if oke.any():
         de = lambda a, b_: ((e[:, :, b_] - e[:, :, a])[oke]).mean()
         print(f"  epilogue of a finished brick: stores nt0 {de(8,9):6.0f} sums nt0 {de(9,10):6.0f} | stores nt1 {de(10,11):6.0f} sums nt1 {de(11,12):6.0f} | barrier {de(12,13):6.0f} | reduce + part {de(13,7):6.0f} | total {de(8,7):6.0f}")
