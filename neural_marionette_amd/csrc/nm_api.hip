@@ -63,6 +63,10 @@ NmLaunchState::NmLaunchState()
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
       , up2c_shell(env_int("NM355_UP2C_SHELL", 1))          // the shell of the fused-upsample layers (split-fp16 mode, fp32 storage): 0: one line per face workgroup (A/B); 1: R lines per face workgroup (conv_up2c_face_r_kernel); 2: that and the edge items of the two-half layer with their loads in a ring (conv_up2c_edge_p_kernel: not the default, it does not clear the bar on the step); 3: the edge form alone; + 20 / 40: R = 2 / 4 at every layer (nm_up2c.hip)
+      // Encoder schedule of the inference forward (nm_net.hip hourglass(); profiles/encoder_schedule_ab.txt)
+      , enc_sched(env_int("NM355_ENC_SCHED", 1))            // 0: the serial schedule - every launch of the per-frame net on the main stream (A/B, the tests' reference)
+      , enc_s1(env_int("NM355_ENC_S1", 1))                  // 0: the hourglass skip branch s1 stays in front of the interior's launch chain instead of running beside it on the third stream (A/B)
+      , enc_s1_wgs(env_int("NM355_ENC_S1_WGS", -1))         // workgroup cap of s1's persistent convs while they run beside the chain: -1 (default) CUs - 2 x frames, at least half the CUs (128 at 64 frames, 224 at 16; nm_net.hip hourglass()); > 0: this value, rounded down to a multiple of 8; 0: none
 { store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_backoff = env_int("NM355_CHAIN_BACKOFF", 0); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
   chain_wgpoll = env_int("NM355_CHAIN_WGPOLL", 1);      // 0: every wave of the cross-XCD rollout chain polls for itself (round 5; A/B)
   chain_xcd_nogo = env_int("NM355_CHAIN_XCD_NOGO", 0);  // test hook: the one-XCD chain never starts (its fallback must do the work)
@@ -228,6 +232,8 @@ int nm_ctx_create(nm_ctx** out, const nm_config* cfg) try {
         hipEventCreateWithFlags(&c->ev_clip, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_kp, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_s1_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_s1_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[2], hipEventDisableTiming) != hipSuccess ||
@@ -260,7 +266,7 @@ int nm_ctx_destroy(nm_ctx* ctx) try {
     nm_vrnn_free_tape(ctx);
     if (ctx->stream2 || ctx->stream3) release_side_streams(ctx->cfg.device, ctx->stream2, ctx->stream3, ctx->side_shared);
     if (ctx->wside) (void)hipFree(ctx->wside);
-    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin, ctx->ev_k5}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_s1_fork, ctx->ev_s1_join, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin, ctx->ev_k5}) if (e) (void)hipEventDestroy(e);
     for (const NmProfRec& r : ctx->ls.prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : ctx->ls.event_pool) (void)hipEventDestroy(e);
     delete ctx;

@@ -197,7 +197,7 @@ struct NmLaunchState {
     unsigned* nf_flag = nullptr;           // sticky device word gn_finalize ORs a 1 into (null: no reporting)
     // A/B and diagnostic switches (NM355_SUPERTILE, _SMALL16, _KSPLIT, _OCC16, _POOL16, _F16P2, _F16P, _WGRAD_TR, _UP2C,
     // _VRNN_MID, _VRNN_GEMM, _VRNN_GRAPH, _SPARSE_FIRST, ..., _UP2Y_YPAD, _UP2C_SHELL)
-    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, tail_rank1, up2c, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell;
+    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, tail_rank1, up2c, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell, enc_sched, enc_s1, enc_s1_wgs;
     NmLaunchState();
 };
 NmLaunchState& nm_ls();        // the state of the context whose ABI call runs on this thread
@@ -213,7 +213,8 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
                    const ConvGeom& g, float* part /*[N][nblk][Cout][2] or null*/, hipStream_t s,
                    int cin_real = 0 /* un-padded Cin, for the profiler's FLOP count */,
                    const void* w_packed16 = nullptr /* split-fp16 weights; enables the fp16-split kernel */,
-                   int out_h = 0 /* 1: `out` is bfloat16 (16-bit storage, conv mode 4); the input's type is in.h */);
+                   int out_h = 0 /* 1: `out` is bfloat16 (16-bit storage, conv mode 4); the input's type is in.h */,
+                   int wgs_cap = 0 /* > 0: this launch's own workgroup cap, read by the persistent kernels (conv_f16p, _f16p2, _f16q2, _f16r) only */);
 // conv arithmetic: 0 = exact fp32 MFMA, 1 = split-fp16 MFMA (3 products, fp32 accumulate) where Cin % 16 == 0
 void nm_conv_set_mode(int mode);
 int nm_conv_get_mode();

@@ -3418,16 +3418,22 @@ int launch_pool_f16s(const ConvParams& p, dim3 grid, hipStream_t s) {
 
 // The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks, 512 threads): one
 // workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues), the bricks in XCD
-// super-tile order where a brick is one work item
+// super-tile order where a brick is one work item.  wgs_cap > 0 is the cap of THIS launch (nm_launch_conv's argument: a conv that runs
+// beside another stream's chain of small dependent launches leaves it CUs), rounded down to a multiple of 8 so that every XCD keeps
+// the same number of workgroups; a workgroup walks a contiguous run of ceil(items / grid) work items, whatever the grid.  The XCD
+// super-tile exists for grids of 256 and 512 only (choose_super_tile: grid / 8 = 32 or 64), so a capped launch walks its bricks in
+// linear order - part of what the cap costs the capped conv itself.
 template <auto KERNEL>
 int launch_persistent(const char* what_attr, const char* what_launch, int variant, bool super_tile, const ConvParams& p_in,
-                      size_t lds_bytes, int work_items, hipStream_t s) {
+                      size_t lds_bytes, int work_items, hipStream_t s, int wgs_cap) {
     static NmDeviceOnce attr_set;
     if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, what_attr, KERNEL)) return rc;
     const int cus = nm_num_cus();
     if (!cus) return NM_ERR_HIP;
     ConvParams p = p_in;
-    dim3 grid((unsigned)min(work_items, nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, cus) : cus));
+    int wgs = nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, cus) : cus;
+    if (wgs_cap > 0 && wgs_cap < wgs) wgs = min(wgs, max(8, wgs_cap & ~7));     // (never above the global cap)
+    dim3 grid((unsigned)min(work_items, wgs));
     if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);
     NmProfScope prof(s, conv_flops(p, 27.0), variant);
     hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds_bytes, s, p);
@@ -3435,48 +3441,48 @@ int launch_persistent(const char* what_attr, const char* what_launch, int varian
 }
 
 template <bool SINGLE, int IO = 0>
-int launch_f16p_impl(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16p_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)3 * 9 * 4 * 32 * 16 + (size_t)(256 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, lds_bytes, work_items, s, wgs_cap);
 }
-int launch_f16p(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16p(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
     if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
         if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p", p);
-        return launch_f16p_impl<true, 3>(p, work_items, s);
+        return launch_f16p_impl<true, 3>(p, work_items, s, wgs_cap);
     }
-    return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s) : launch_f16p_impl<false>(p, work_items, s);
+    return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s, wgs_cap) : launch_f16p_impl<false>(p, work_items, s, wgs_cap);
 }
 
 template <bool SINGLE, int IO = 0>
-int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
 }
 // the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
 template <int IO>
-int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)2 * 27 * 2 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
     if (lds_bytes > 160 * 1024) { nm_set_error("conv_f16q2: %d output channels exceed the LDS budget", p.Cout); return NM_ERR_UNSUPPORTED; }
-    return launch_persistent<&conv_f16q2_kernel<IO>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16q2_kernel<IO>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
 }
 // the one-product modes' kernel for the 32-output-channel layers (conv_f16r_kernel: resident weights); Cin = 16 C16T
 template <int IO, int C16T>
-int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)27 * C16T * 64 * 16 + (size_t)(512 + 32) * sizeof(float) + 2048 + 256 + 1024;      // (+ the store slots of the lanes that hold no total)
-    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, lds_bytes, work_items, s);
+    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, lds_bytes, work_items, s, wgs_cap);
 }
-int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s) {
+int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
     if (nm_ls().single && nm_ls().f16q2 && (io == 0 || io == 3) && p.Cout <= 1024) {
-        return io ? launch_f16q2_impl<3>(p, work_items, s) : launch_f16q2_impl<0>(p, work_items, s);
+        return io ? launch_f16q2_impl<3>(p, work_items, s, wgs_cap) : launch_f16q2_impl<0>(p, work_items, s, wgs_cap);
     }
     if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
         if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p2", p);
-        return launch_f16p2_impl<true, 3>(p, work_items, s);
+        return launch_f16p2_impl<true, 3>(p, work_items, s, wgs_cap);
     }
-    if (nm_ls().single) return launch_f16p2_impl<true>(p, work_items, s);
-    return launch_f16p2_impl<false>(p, work_items, s);
+    if (nm_ls().single) return launch_f16p2_impl<true>(p, work_items, s, wgs_cap);
+    return launch_f16p2_impl<false>(p, work_items, s, wgs_cap);
 }
 
 #ifdef NM_DIAG
@@ -3634,7 +3640,7 @@ void nm_conv_prof_reset() {
 }
 
 int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias, float* out,
-                   const ConvGeom& g, float* part, hipStream_t s, int cin_real, const void* w_packed16, int out_h) {
+                   const ConvGeom& g, float* part, hipStream_t s, int cin_real, const void* w_packed16, int out_h, int wgs_cap) {
     if (in.C % 8 != 0 || g.Co_pad % 32 != 0 || g.Cout > g.Co_pad || g.Cout <= 0) {
         nm_set_error("conv: unsupported channels Cin=%d Cout=%d Co_pad=%d", in.C, g.Cout, g.Co_pad);
         return NM_ERR_ARG;
@@ -3702,20 +3708,20 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
     if (nm_ls().conv_mode == 1 && nm_ls().f16p2 && k3_bricks && g.Cout % 64 == 0) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 64);
         p.w = static_cast<const float*>(w_packed16);
-        return launch_f16p2(p, work, s);
+        return launch_f16p2(p, work, s, wgs_cap);
     }
     if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && nm_ls().f16p && k3_bricks && (in.C == 32 || in.C == 64) && g.Cout == 32 &&
         (p.in_h != 0) == (p.out_h != 0)) {
         // one-product modes, 32 output channels: the layer's weights stay in LDS (conv_f16r_kernel)
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8);
         p.w = static_cast<const float*>(w_packed16);
-        if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s) : launch_f16r_impl<0, 2>(p, work, s);
-        return p.in_h ? launch_f16r_impl<3, 4>(p, work, s) : launch_f16r_impl<0, 4>(p, work, s);
+        if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s, wgs_cap) : launch_f16r_impl<0, 2>(p, work, s, wgs_cap);
+        return p.in_h ? launch_f16r_impl<3, 4>(p, work, s, wgs_cap) : launch_f16r_impl<0, 4>(p, work, s, wgs_cap);
     }
     if (nm_ls().conv_mode == 1 && nm_ls().f16p && k3_bricks && g.Cout % 32 == 0 && (nm_ls().f16p == 1 || nm_ls().f16p_all || g.Cout == 32)) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 32);
         p.w = static_cast<const float*>(w_packed16);
-        return launch_f16p(p, work, s);
+        return launch_f16p(p, work, s, wgs_cap);
     }
     if (nm_ls().conv_mode == 1 && w_packed16 && in.C % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2 &&
         g.stride == 1 && (g.ks == 1 || g.ks == 3) && t.HZ == g.ks + 3 && t.HY * t.HX * 2 <= 256) {

@@ -92,6 +92,9 @@ struct nm_ctx {
     bool stream_bound = false;             // nm_ctx_set_stream has been called (nullptr = the legacy default stream is a valid choice)
     hipStream_t stream2 = nullptr;         // ctx-owned side stream: clip-mean net / VRNN run beside the frame stack
     hipEvent_t ev_fork = nullptr, ev_clip = nullptr, ev_kp = nullptr, ev_side = nullptr;
+    // inference forward: the per-frame net's hourglass skip branch s1 runs on stream3 beside the interior's launch chain (nm_net.hip
+    // hourglass()): fork (main stream -> stream3) and join (stream3 -> main stream), once per encoder chunk
+    hipEvent_t ev_s1_fork = nullptr, ev_s1_join = nullptr;
     // weight gradients of the training backward on a stream of their own (nm_net.hip conv_bwd): their inputs that must outlive the main
     // stream's arena frames (a ring of dY buffers, the re-materialised upsample + slot workspace, the operand-scale vectors) live in one
     // ctx-owned block sized by the sizing pass of nm_detector_forward_train

@@ -314,9 +314,14 @@ __global__ void pack_small_kernel(const float* a, int na, const float* b, int nb
 struct Net {
     nm_ctx* c; hipStream_t s; Arena& ws; int rc = NM_OK;
     bool keep = false;                 // training forward: nothing is released, every activation stays for the backward pass
+    int conv_wgs = 0;                  // > 0: workgroup cap of the persistent convs this Net launches (nm_launch_conv's wgs_cap)
+    bool s1_fork = false;              // inference, per-frame net: hourglass() runs the skip branch s1 on stream3 beside the interior
+    // a branch on another stream: its temporaries stay allocated until the enclosing frame is released.  (Not `keep`: that also
+    // selects bfloat16 storage in conv mode 4 - h16() below - and would change the branch's results.)
+    bool hold = false;
     explicit Net(nm_ctx* ctx) : c(ctx), s(ctx->stream), ws(ctx->ws) {}
     Net(nm_ctx* ctx, hipStream_t stream) : c(ctx), s(stream), ws(ctx->ws) {}
-    void release(size_t m) { if (!keep) ws.release(m); }
+    void release(size_t m) { if (!keep && !hold) ws.release(m); }
     bool ok() const { return rc == NM_OK; }
     bool live() const { return rc == NM_OK && !ws.dry; }
     void run(int r) { if (r && !rc) rc = r; }
@@ -372,7 +377,7 @@ TensorRef conv_gn(Net& n, const TensorRef& in, const ConvW& w, const NormW* gn, 
     if (n.live()) {
         if (in.C != w.Cin_pad) { nm_set_error("conv_gn: input has %d channels, layer expects %d", in.C, w.Cin_pad); n.rc = NM_ERR_STATE; }
         else {
-            n.run(nm_launch_conv(src, w.wp, w.bias, out, g, part, n.s, w.Cin, w.wp16, oh));
+            n.run(nm_launch_conv(src, w.wp, w.bias, out, g, part, n.s, w.Cin, w.wp16, oh, n.conv_wgs));
             if (gn) n.run(nm_launch_gn_finalize(part, in.N, nblk, w.Cout, gn->groups, (double)ov * (w.Cout / gn->groups),
                                                 gn->gamma, gn->beta, 1e-5f, scale, shift, n.s, chsum));
             if (gn && nm_ls().gn_diag && !oh) n.run(nm_launch_gn_direct(out, in.N, (int)ov, w.Cout, gn->groups, gn->gamma, gn->beta, 1e-5f, scale, shift, n.s, chsum));
@@ -505,16 +510,55 @@ TensorRef hourglass_core(Net& n, const TensorRef& a2, const HourglassW& w, int o
     return res(n, x, w.d2, nullptr, r ? &r->d2 : nullptr);
 }
 
+// A Res3DBlock of the inference forward as a branch on stream3 beside the caller's stream: fork event on n.s, the block through a Net
+// of its own (temporaries held, persistent convs capped at wgs_cap workgroups), join event on stream3.  Returns the block's output;
+// `forked` tells the caller to make n.s wait for `ev_join` before the first reader.
+static TensorRef res_on_stream3(Net& n, const TensorRef& x, const ResW& w, hipEvent_t ev_fork, hipEvent_t ev_join, int wgs_cap, bool& forked) {
+    nm_ctx* c = n.c;
+    Net n3(c, c->stream3);
+    n3.hold = true; n3.rc = n.rc; n3.conv_wgs = wgs_cap;
+    forked = false;
+    if (n.live()) {
+        n.run(nm_check_hip(hipEventRecord(ev_fork, n.s), "hourglass: skip-branch fork event"));
+        n.run(nm_check_hip(hipStreamWaitEvent(c->stream3, ev_fork, 0), "hourglass: skip-branch stream wait"));
+        n3.rc = n.rc; forked = n.ok();
+    }
+    TensorRef o = res(n3, x, w);
+    if (forked) n.run(nm_check_hip(hipEventRecord(ev_join, c->stream3), "hourglass: skip-branch join event"));
+    n.run(n3.rc);
+    return o;
+}
+
 TensorRef hourglass(Net& n, const TensorRef& x0, const HourglassW& w, int Ng, HgRec* r = nullptr) {
     const int op3 = (Ng / 4) % 2, op2 = (Ng / 2) % 2, op1 = Ng % 2;
-    TensorRef s1 = res(n, x0, w.s1, nullptr, r ? &r->s1 : nullptr);
+    // Inference, per-frame net (Net::s1_fork): the skip branch s1 - two convs and an apply2 that only the LAST add below reads - goes to
+    // stream3 and runs beside the interior (pool 1 ... up 1: ~45 launches of 4-70 us and one hg_core launch on 64 workgroups, a stretch
+    // that leaves most of the chip idle) instead of in front of it.  Its persistent convs are capped (NM355_ENC_S1_WGS): a full grid of
+    // them holds every CU's LDS and each link of the chain would wait for a workgroup to retire.
+    // SCRATCH: the branch shares the bump arena with the main stream.  Its output and temporaries are allocated first, in the serial
+    // schedule's host order, and held (Net::hold) until the enclosing feature_net frame is released - after the join below has been
+    // enqueued on the main stream, so whatever reuses the bytes is ordered behind the branch.  The measuring passes take the same
+    // path (the decision does not depend on Arena::dry) and see the same allocation sequence.
+    nm_ctx* c = n.c;
+    const bool fork = n.s1_fork && !r && c->stream3 && c->stream3 != n.s;
+    bool forked1 = false;
+    // The cap leaves the chain the CUs it can use: its kernels launch one or two workgroups per frame (hg_core one, the 8^3 convs
+    // two), so 2 N CUs stay free, at most half the chip.  64 frames: 128 workgroups (the A/B's pick); 16 frames at 96^3, where a cap
+    // of 128 made s1 outlast the chain and the step slower than the serial schedule: 224.  NM355_ENC_S1_WGS > 0 forces a value.
+    int cap = nm_ls().enc_s1_wgs;
+    if (fork && cap < 0) { const int cus = nm_num_cus(); cap = cus > 16 ? std::max(cus / 2, cus - 2 * x0.N) : 0; }
+    TensorRef s1 = fork ? res_on_stream3(n, x0, w.s1, c->ev_s1_fork, c->ev_s1_join, cap, forked1)
+                        : res(n, x0, w.s1, nullptr, r ? &r->s1 : nullptr);
     TensorRef x = res(n, pool(n, x0, w.p1, r ? &r->p1 : nullptr), w.e1, nullptr, r ? &r->e1 : nullptr);
     TensorRef s2 = res(n, x, w.s2, nullptr, r ? &r->s2 : nullptr);
     TensorRef a2 = pool(n, x, w.p2, r ? &r->p2 : nullptr);
     x = hourglass_core(n, a2, w, op3, r);
     TensorRef u = up(n, x, w.u2, op2, r ? &r->u2 : nullptr); x = add2(n, u, &s2);
     x = res(n, x, w.d1, nullptr, r ? &r->d1 : nullptr);
-    u = up(n, x, w.u1, op1, r ? &r->u1 : nullptr); x = add2(n, u, &s1);
+    u = up(n, x, w.u1, op1, r ? &r->u1 : nullptr);
+    // (the join is enqueued even behind an error: nothing of the branch may outlive the call's hold on the arena)
+    if (forked1) n.run(nm_check_hip(hipStreamWaitEvent(n.s, c->ev_s1_join, 0), "hourglass: join the skip branch"));
+    x = add2(n, u, &s1);
     return x;
 }
 
@@ -637,6 +681,7 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
                    const std::function<int()>* after_keypoints = nullptr, TrainTape* tape = nullptr) {
     Net n(c);
     n.keep = tape != nullptr;
+    n.s1_fork = !tape && nm_ls().enc_sched && nm_ls().enc_s1;       // inference only; the clip-mean net (n2, 4 frames) keeps its serial order
     const DetectorW& d = c->det;
     if (c->graph_none()) affinity_on = 0;       // keypoints_graph 'none': no affinity, every graph term is zero (kypt_detector.py:114-119)
     const int K = c->cfg.nkeypoints, G = c->cfg.grid_size, g = G / 4, F = B * T, N = c->cfg.nneighbor;
