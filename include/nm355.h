@@ -86,7 +86,7 @@ int nm_ctx_set_stream(nm_ctx* ctx, void* hip_stream);
  * with a message naming the call that produced the value and the remedy (nm_set_conv_mode(ctx, 0): exact fp32 MFMA, no range
  * limit): NM_ERR_RANGE for bit 1 (non-finite conv statistics), NM_ERR_STATE for bit 2 (a persistent rollout kernel gave up a bounded
  * wait - never a hang).  nm_ctx_check_nonfinite drains the pending slots synchronously with the same two codes, word cleared; 0
- * otherwise.  NM355_RANGE_CHECK=0 removes the copies.  The op-level entry point nm_op_conv3d is synchronous about it: it
+ * otherwise.  The op-level entry point nm_op_conv3d is synchronous about it: it
  * scans its result and re-runs the launch on the fp32 path by itself.  (The Python shells add set_conv_mode('auto').) */
 int nm_ctx_check_nonfinite(nm_ctx* ctx);
 /* Replaces NeuralMarionette.load_state_dict / .cuda() for the HIP path: copies every

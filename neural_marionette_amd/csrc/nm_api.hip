@@ -19,46 +19,24 @@ static thread_local char g_err[512] = "";
 thread_local NmLaunchState* nm_tls_ls = nullptr;
 static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 NmLaunchState::NmLaunchState()
-    : supertile(env_int("NM355_SUPERTILE", 1)),     // 0: linear brick order (diagnostic)
-      small16(env_int("NM355_SMALL16", 1)),         // 0: small volumes on the fp32 MFMA core (diagnostic)
-      ksplit(env_int("NM355_KSPLIT", 1)),           // 0: no tap split on the tiny volumes (diagnostic)
-      occ16(env_int("NM355_OCC16", 1)),             // 0: first layer on the fp32 MFMA kernel (diagnostic)
-      pool16(env_int("NM355_POOL16", 1)),           // 0: pool convs on the fp32 kernel (diagnostic)
-      f16p2(env_int("NM355_F16P2", 1)),             // 0: Cout % 64 == 0 layers stay on conv_f16s (diagnostic)
-      // conv_f16p use: 0 never (conv_f16s everywhere), 1 every eligible layer, 2 (default) only Cout == 32 layers - with more cout
-      // groups per brick it re-stages the input per group and measures a little slower than conv_f16s (A/B in one gpurun call)
-      f16p(env_int("NM355_F16P", 2)),
-      pool_q(env_int("NM355_POOL_Q", 1)),           // 0: conv_pool_f16s_kernel (conditional loads, one memory round trip per tap) instead of conv_pool_f16q_kernel
+    : pool_q(env_int("NM355_POOL_Q", 1)),           // 0: conv_pool_f16s_kernel (conditional loads, one memory round trip per tap) instead of conv_pool_f16q_kernel
       occ_flags(env_int("NM355_OCC_FLAGS", 2)),     // sparse first layer: 0 every brick tests its own halo; 1 per-brick occupancy flags as a pre-filter; 2 (default) also one workgroup per x-row of bricks
       gnb_apply4(env_int("NM355_GNB_APPLY4", 1)),   // 0: gnb_apply_kernel (one 16-byte item per iteration) for every channel count
       defer_sums(env_int("NM355_DEFER_SUMS", 1)),      // 0: the per-layer gamma / beta / bias gradient sums are launched inside each GroupNorm backward (A/B)
       wgrad_async(env_int("NM355_WGRAD_ASYNC", 1)),    // 0: the weight gradients of the training backward stay in the main stream's chain (A/B)
-      wgrad_wgs(env_int("NM355_WGRAD_WGS", 0)),       // workgroups of a split-fp16 weight-gradient launch (0: 224 beside the main stream's walk, else 256; plan_wgrad)
       wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: every split-fp16 k3 weight gradient on wgrad16_kernel (VALU transposition) instead of wgrad16z_kernel: the one A/B of the family (w16z_takes)
       tail_rank1(env_int("NM355_TAIL_RANK1", 1)),   // 0: the decoder tail's backward materialises its [F][G^3][32] gradient (A/B)
-      up2c(env_int("NM355_UP2C", 1)),               // 0: fused-upsample layers stay on conv_f16s (diagnostic / A-B)
       vrnn_mid(env_int("NM355_VRNN_MID", 1)),          // 0: prior steps as six launches instead of three (A/B)
       vrnn_gemm(env_int("NM355_VRNN_GEMM", 1)),    // 0: one wavefront per output row at every batch size (A/B)
       vrnn_graph(env_int("NM355_VRNN_GRAPH", 1)),       // 0: rollouts enqueue their launches one by one instead of replaying a captured graph (A/B)
       sparse_first(env_int("NM355_SPARSE_FIRST", 1)), // 0: the first layer writes its dense output in inference too (A/B)
       gn_diag(env_int("NM355_GN_DIAG", 0)),                 // 1: GroupNorm statistics recomputed from the stored tensor in fp64 (diagnostic)
       lazy_res(env_int("NM355_LAZY_RES", 1)),         // 0: every residual sum is materialised by apply2 (A/B)
-      adjust_split(env_int("NM355_ADJUST_SPLIT", 1)), // 0: the decoder's first 1x1 conv runs over the materialised 184-channel tensor in inference too (A/B)
       hg_core(env_int("NM355_HG_CORE", 1)),           // 0: the two lowest hourglass levels as separate launches in inference too (A/B)
-      clip_occ_mfma(env_int("NM355_CLIP_OCC_MFMA", 1)),  // 0: the clip-mean net's first-layer weight gradient as the dense all-frames kernel (A/B)
       vrnn_chain(env_int("NM355_VRNN_CHAIN", 1)),        // 0: the prior steps of a rollout as three launches per step instead of one persistent launch (A/B)
-      wgrad_k2f16(env_int("NM355_WGRAD_K2F16", 1)),     // 0: the k2 s2 weight gradients on the fp32-MFMA kernel in every conv mode (A/B)
-      convt_f16(env_int("NM355_CONVT_F16", 1)),         // 0: the transposed convs (and the pool convs' data gradient) on the fp32-MFMA kernel in every conv mode (A/B)
-      k5_two(env_int("NM355_K5_TWO", 0)),               // 1: the two halves of the first layer's weight gradient on two streams (A/B: 44.6 vs 44.7 / 73.3 vs 73.6 ms per step - the tail of one step already overlaps the head of the next)
-      clip_late(env_int("NM355_CLIP_LATE", 1)),         // 0: the clip-mean net is enqueued before the per-frame encoder instead of behind its first chunk(s) (A/B)
-      gnb_u8(env_int("NM355_GNB_U8", 1)),               // 0: four instead of eight items in flight in the bfloat16 GroupNorm-backward apply (A/B)
-      adj_zwalk(env_int("NM355_ADJ_ZWALK", 1)),        // 0: the trilinear upsample's adjoint on the 2 x 4 x 8 brick kernel (6 x 10 x 18 fine tile) instead of the z-walking one (A/B)
-      f16q2(env_int("NM355_F16Q2", 1)),                 // 0: the one-product modes (3 / 4) keep conv_f16p2<SINGLE> instead of their own kernel conv_f16q2 (A/B)
       vrnn_post_chain(env_int("NM355_VRNN_POST_CHAIN", 2))   // 0: the posterior steps of encode as six launches each; 1: one persistent launch (vrnn_post_chain_kernel) for a stand-alone encode only; 2 (default since round 6): inside nm_forward_fused too - 148 instead of 238 launches per forward step for +0.03 ... 0.13 ms (profiles/r06_forward_ab.txt)
       , f16r(env_int("NM355_F16R", 1))                      // 0: the one-product modes keep conv_f16p<SINGLE> on the 32-output-channel layers instead of conv_f16r (resident weights; A/B)
       , up2_mat(env_int("NM355_UP2_MAT", 1))                // 0: the one-product training forward keeps the fused-upsample staging on its 32-output layer instead of materialising the upsampled input for conv_f16r (A/B)
-      , conv_wgs(env_int("NM355_CONV_WGS", 0))              // > 0: the persistent producer / consumer convs launch at most this many workgroups (co-residency A/B: CUs left free for the other queues)
-      , fast_decode(env_int("NM355_FAST_DECODE", 1))        // 0: the persistent convs decode a brick's position with integer divisions instead of host-made reciprocal multiplications (A/B)
       , up2y(env_int("NM355_UP2Y", 1))                      // 0: the split-fp16 mode keeps the composite-weight kernel in all three axes (conv_up2c_x16_kernel) on the 64 -> 32 fused-upsample layer and conv_f16s on the 128 -> 64 one (A/B, the tests' reference); else: conv_up2y_kernel (products on the coarse grid, interpolated along y) on both
       , up2y_march(env_int("NM355_UP2Y_MARCH", 1))          // conv_up2y_kernel: 0: bricks x-fastest, every brick computes its own halo row tiles (A/B); 1: whole columns along y per workgroup with the two halo tiles carried from brick to brick, where there are at least as many columns as CUs; 2: at every shape (tests)
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
@@ -131,33 +109,21 @@ extern "C" {
 int nm_abi_version(void) { return NM_ABI_VERSION; }
 const char* nm_last_error(void) { return g_err; }
 
-// the weight-gradient stream; NM355_WGRAD_PRIO=1: at the lowest priority the device offers (A/B)
-static hipError_t create_wgrad_stream(hipStream_t* s) {
-    const char* e = getenv("NM355_WGRAD_PRIO");
-    if (e && atoi(e) != 0) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            return hipStreamCreateWithPriority(s, hipStreamNonBlocking, least);
-    }
-    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}
-
 // The two side streams (clip-mean net / VRNN beside the frame stack; weight gradients) are shared by all contexts of a process on a
 // device.  HIP maps streams onto a few hardware queues round-robin (4 by default): a SECOND context with streams of its own got queues
 // that the runtime arbitrates differently and its bf16 training step ran at 48 ms instead of 44 (same kernels, same durations when
 // alone; 53 ms with GPU_MAX_HW_QUEUES=8, 44 with 3: tools/time_train_steps.py) - bench.py's train_bf16, measured in a second context,
 // showed it.  Sharing adds ordering between contexts used concurrently from different threads, never a missing dependency (each
-// context keeps its own events).  NM355_OWN_STREAMS=1 / NM355_WGRAD_PRIO=1: streams per context as before.
+// context keeps its own events).  Only a device index beyond the table gets a pair of its own.
 #define NM_MAX_DEVICES 16
 static std::mutex g_side_mu;
 static hipStream_t g_side[NM_MAX_DEVICES][2];
 static int g_side_refs[NM_MAX_DEVICES];
-static bool own_streams() { const char* e = getenv("NM355_OWN_STREAMS"); const char* p = getenv("NM355_WGRAD_PRIO"); return (e && atoi(e) != 0) || (p && atoi(p) != 0); }
 static hipError_t acquire_side_streams(int dev, hipStream_t* s2, hipStream_t* s3, bool* shared) {
-    if (own_streams() || dev < 0 || dev >= NM_MAX_DEVICES) {
+    if (dev < 0 || dev >= NM_MAX_DEVICES) {
         *shared = false;
         hipError_t e = hipStreamCreateWithFlags(s2, hipStreamNonBlocking);
-        return e != hipSuccess ? e : create_wgrad_stream(s3);
+        return e != hipSuccess ? e : hipStreamCreateWithFlags(s3, hipStreamNonBlocking);
     }
     std::lock_guard<std::mutex> lk(g_side_mu);
     if (g_side_refs[dev] == 0) {
@@ -220,14 +186,12 @@ int nm_ctx_create(nm_ctx** out, const nm_config* cfg) try {
         return NM_ERR_HIP;
     }
     for (int i = 0; i < 4; ++i) c->nf_host[i] = 0;
-    { const char* e = getenv("NM355_RANGE_CHECK"); c->range_check = e ? atoi(e) : 1; }
     if (acquire_side_streams(cfg->device, &c->stream2, &c->stream3, &c->side_shared) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_w[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_w[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_w[2], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_dy, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_wjoin, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_k5, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_clip, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_kp, hipEventDisableTiming) != hipSuccess ||
@@ -266,7 +230,7 @@ int nm_ctx_destroy(nm_ctx* ctx) try {
     nm_vrnn_free_tape(ctx);
     if (ctx->stream2 || ctx->stream3) release_side_streams(ctx->cfg.device, ctx->stream2, ctx->stream3, ctx->side_shared);
     if (ctx->wside) (void)hipFree(ctx->wside);
-    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_s1_fork, ctx->ev_s1_join, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin, ctx->ev_k5}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_s1_fork, ctx->ev_s1_join, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin}) if (e) (void)hipEventDestroy(e);
     for (const NmProfRec& r : ctx->ls.prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : ctx->ls.event_pool) (void)hipEventDestroy(e);
     delete ctx;

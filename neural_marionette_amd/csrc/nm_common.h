@@ -179,7 +179,7 @@ struct NmProfRec { hipEvent_t a, b; int variant; double flops; };
 struct NmLaunchState {
     int conv_mode = 1;         // 0: exact fp32 MFMA everywhere, 1: split-fp16 MFMA where the layer shape allows
     bool f16p_all = false;     // mode 2: split-fp16 with conv_f16p on every eligible layer (parity tests of its multi-cout-group path)
-    bool single = false;       // mode 3 / 4: the split-fp16 kernels keep only the hi x hi product (SINGLE instantiations)
+    bool single = false;       // mode 3 / 4: the split-fp16 kernels keep only the hi x hi product (SINGLE instantiations, conv_f16q2, conv_f16r)
     bool store16 = false;      // mode 4 ('bf16'): mode 3's arithmetic + bfloat16 storage of the training path's large tensors
     int op_in_h = 0, op_out_h = 0;   // op-level entry points (nm_op_*): element type of the input-side / output-side tensors (nm_op_set_storage16)
     int store16_min = 32768;   // ... those with at least this many voxels per frame (NM355_STORE16_MIN; 32^3: everything above the hourglass)
@@ -195,9 +195,8 @@ struct NmLaunchState {
     std::vector<NmProfRec> prof;           // records of the current window
     std::vector<hipEvent_t> event_pool;
     unsigned* nf_flag = nullptr;           // sticky device word gn_finalize ORs a 1 into (null: no reporting)
-    // A/B and diagnostic switches (NM355_SUPERTILE, _SMALL16, _KSPLIT, _OCC16, _POOL16, _F16P2, _F16P, _WGRAD_TR, _UP2C,
-    // _VRNN_MID, _VRNN_GEMM, _VRNN_GRAPH, _SPARSE_FIRST, ..., _UP2Y_YPAD, _UP2C_SHELL)
-    int supertile, small16, ksplit, occ16, pool16, f16p2, f16p, pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_wgs, wgrad_tr, tail_rank1, up2c, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, adjust_split, hg_core, clip_occ_mfma, vrnn_chain, wgrad_k2f16, convt_f16, k5_two, clip_late, gnb_u8, adj_zwalk, f16q2, vrnn_post_chain, f16r, up2_mat, conv_wgs, fast_decode, up2y, up2y_march, up2y_ypad, up2c_shell, enc_sched, enc_s1, enc_s1_wgs;
+    // A/B and diagnostic switches: NM355_<NAME IN CAPITALS>, each described at its initialiser (nm_api.hip)
+    int pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_tr, tail_rank1, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, hg_core, vrnn_chain, vrnn_post_chain, f16r, up2_mat, up2y, up2y_march, up2y_ypad, up2c_shell, enc_sched, enc_s1, enc_s1_wgs;
     NmLaunchState();
 };
 NmLaunchState& nm_ls();        // the state of the context whose ABI call runs on this thread

@@ -2187,14 +2187,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 //   * LDS: two weight buffers (2 x 36 KB) instead of three, so the B operands of a tap group's first tap are read after
 //     the barrier that publishes them; operands one tap (12 MFMAs) ahead, double buffered.
 //   LDS: halo [2][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [2][9 taps][4 planes][64] x 16 B, GroupNorm scratch, bias.
-// IO: bit 0 = bfloat16 input (a producer piece is then an 8-byte load of the same four channels), bit 1 = bfloat16 output
+// Split-fp16 (three products), fp32 storage only: the one-product modes (3 / 4) have their own kernel, conv_f16q2, below.
 // The epilogue stays exposed (7 800 of a 64-channel brick's 58 000 cycles).  A variant with one accumulator per tile and the finished
 // brick's epilogue interleaved into the next brick's first step was built (round 6) and was slower, 1.31-1.33 -> 1.36-1.43 ms at
 // 64 -> 64 @32^3; it is retired, the account and the evidence's place are in DESIGN_HISTORY.md.
-template <bool SINGLE = false, int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
-    constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
-    constexpr unsigned EB = IH ? 2u : 4u;                           // bytes per input element
     constexpr int HV = 600, ZP = 100, HX = 10;
     constexpr int GB = 9 * 4 * 64;                                  // half8 slots of one weight group
     constexpr int NP = 10;                                          // 16-byte input pieces per producer thread and step (2400 / 256)
@@ -2261,12 +2258,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + 4 * quad;
             pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
         }
-        using RawT = std::conditional_t<IH, nm_u32x2, f32x4>;
-        RawT raw[NP]; f32x4 sc, sh, wreg[9];
+        f32x4 raw[NP], sc, sh, wreg[9];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};       // (SINGLE uses five of them; all nine are operands of the counted waits)
+        for (int i = 0; i < 9; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * EB;   // halo voxel (1,1,1): always inside
+        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * 4u;   // halo voxel (1,1,1): always inside (byte offset)
         auto inside_mask = [&](const Work& w) {
             unsigned m = 0;
 #pragma unroll
@@ -2279,12 +2275,11 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             return m;
         };
         auto tile_base = [&](const Work& w, int cb) {
-            return nm_eptr(p.in, (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16), IH);
+            return p.in + (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16);
         };
         auto load_piece = [&](const float* base, unsigned mask, auto K) {
             constexpr int k = decltype(K)::value;
-            if constexpr (IH) raw[k] = load8_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
-            else raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
+            raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * 4u : rel111);
         };
         auto load_affine = [&](const Work& w, int cb) {             // always two loads: the waits below count instructions
             const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
@@ -2302,36 +2297,29 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
 #pragma unroll
             for (int e = 0; e < 4; e += 2) {
-                float v0, v1;
-                if constexpr (IH) { const unsigned u = raw[k][e >> 1]; v0 = nm_bf_lo(u); v1 = nm_bf_hi(u); }
-                else { v0 = raw[k][e]; v1 = raw[k][e + 1]; }
+                float v0 = raw[k][e], v1 = raw[k][e + 1];
                 if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
                 v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
                 half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
                 asm volatile("" : "+v"(hv));
                 const float t0 = v0 * NM_SPLIT_SCALE, t1 = v1 * NM_SPLIT_SCALE;
                 hi4[e] = hv[0]; hi4[e + 1] = hv[1];
-                if constexpr (!SINGLE) {                            // (conv mode 3 has no use for the lo halves)
-                    lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
-                    lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
-                }
+                lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
+                lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
             }
             if (pc_pos[k] >= 0) {
                 half4v* dst = reinterpret_cast<half4v*>(ldh + buf * 4 * HV + pc_slot[k]) + (quad & 1);
                 dst[0] = hi4;
-                if constexpr (!SINGLE) dst[4 * HV] = lo4;
+                dst[4 * HV] = lo4;
             }
         };
         // tap group g of (cout group cg, chunk cb): 36 one-KiB wave pieces (tap t, plane r, 64 channels), nine per producer wave.
-        // SINGLE (conv modes 3 / 4): the MFMA waves never read the lo planes r = 2, 3 - only the 18 hi pieces are copied, five per wave
-        // (the last two of the 20 slots repeat piece 17: identical bytes to the same place).  The weight copies are three quarters of a
-        // producer wave's issue slots, and in the one-product modes the producers, not the MFMA pipe, bound the kernel.
-        constexpr int NW = SINGLE ? 5 : 9;
+        // The weight copies are three quarters of a producer wave's issue slots.
+        constexpr int NW = 9;
         unsigned w_src[NW], w_dst[NW];
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
-            const int j = SINGLE ? min(pw + 4 * i, 17) : pw + 4 * i;
-            const int t = SINGLE ? j >> 1 : j >> 2, r = SINGLE ? j & 1 : j & 3;
+            const int j = pw + 4 * i, t = j >> 2, r = j & 3;
             w_src[i] = (unsigned)(((size_t)t * C16 * 4 + r) * plane + lane) * 16u;
             w_dst[i] = (unsigned)(t * 256 + r * 64 + lane) * 16u;
         }
@@ -2384,7 +2372,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             // Everything older than the 9 weight loads has landed after the first wait.
             NM_PSTAMP(0);
             load_b_group(cur.w.cg, cur.cb, 1);
-            if constexpr (SINGLE) { NM_PRODUCER2_WAIT(5); } else { NM_PRODUCER2_WAIT(9); }      // (NW weight loads are the youngest)
+            NM_PRODUCER2_WAIT(9);                                   // (the NW weight loads are the youngest)
             NM_PSTAMP(1);
             static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
             NM_PRODUCER2_WAIT(3);                                   // the weight loads (older than the 3 new piece loads)
@@ -2449,8 +2437,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
     half8 ah0[2], al0[2], ah1[2], al1[2], bh0[2], bh1[2], bl0[2], bl1[2];      // operands, double buffered (index = tap & 1)
     {
         const unsigned va = (unsigned)(size_t)(ldh + h * HV + arow0);
-        ah0[0] = lds_read16_untracked<0>(va); al0[0] = SINGLE ? half8{} : lds_read16_untracked<LO>(va);
-        ah1[0] = lds_read16_untracked<YO>(va); al1[0] = SINGLE ? half8{} : lds_read16_untracked<LO + YO>(va);
+        ah0[0] = lds_read16_untracked<0>(va); al0[0] = lds_read16_untracked<LO>(va);
+        ah1[0] = lds_read16_untracked<YO>(va); al1[0] = lds_read16_untracked<LO + YO>(va);
     }
     for (;;) {
         Step nxt = cur;
@@ -2465,7 +2453,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             constexpr int BT = t * 256 * 16;                        // byte offset of this tap in its weight buffer
             if constexpr (t == 0) {                                 // first tap of a group: its weights were published by the barrier
                 bh0[i] = lds_read16_untracked<BT>(vb); bh1[i] = lds_read16_untracked<BT + 32 * 16>(vb);
-                bl0[i] = SINGLE ? half8{} : lds_read16_untracked<BT + 128 * 16>(vb); bl1[i] = SINGLE ? half8{} : lds_read16_untracked<BT + 160 * 16>(vb);
+                bl0[i] = lds_read16_untracked<BT + 128 * 16>(vb); bl1[i] = lds_read16_untracked<BT + 160 * 16>(vb);
             }
             // every operand of this tap has been requested (previous tap / just above): wait for all of them
             asm volatile("s_waitcnt lgkmcnt(0)"
@@ -2478,19 +2466,18 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             constexpr bool bnext = t < 8;                           // the next tap's weights are in this group's buffer
             constexpr int BN = (t + 1) * 256 * 16;
 #define NM_MFMA2(ACC, B, A) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(B, A, ACC, 0, 0, 0); __builtin_amdgcn_sched_barrier(0)
-#define NM_MFMA2L(ACC, B, A) ACC = nm_mfma_lo<SINGLE>(B, A, ACC); __builtin_amdgcn_sched_barrier(0)
             NM_MFMA2(acc[0][0], bh0[i], ah0[i]);  if constexpr (anext) ah0[j] = lds_read16_untracked<AO>(vau);
-            NM_MFMA2(acc[0][1], bh1[i], ah0[i]);  if constexpr (anext) al0[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO>(vau);
-            NM_MFMA2L(accl[0][0], bl0[i], ah0[i]); if constexpr (anext) ah1[j] = lds_read16_untracked<AO + YO>(vau);
-            NM_MFMA2L(accl[0][1], bl1[i], ah0[i]); if constexpr (anext) al1[j] = SINGLE ? half8{} : lds_read16_untracked<AO + LO + YO>(vau);
-            NM_MFMA2L(accl[0][0], bh0[i], al0[i]); if constexpr (bnext) bh0[j] = lds_read16_untracked<BN>(vb);
-            NM_MFMA2L(accl[0][1], bh1[i], al0[i]); if constexpr (bnext) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb);
-            NM_MFMA2(acc[1][0], bh0[i], ah1[i]);  if constexpr (bnext) bl0[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 128 * 16>(vb);
-            NM_MFMA2(acc[1][1], bh1[i], ah1[i]);  if constexpr (bnext) bl1[j] = SINGLE ? half8{} : lds_read16_untracked<BN + 160 * 16>(vb);
-            NM_MFMA2L(accl[1][0], bl0[i], ah1[i]);
-            NM_MFMA2L(accl[1][1], bl1[i], ah1[i]);
-            NM_MFMA2L(accl[1][0], bh0[i], al1[i]);
-            NM_MFMA2L(accl[1][1], bh1[i], al1[i]);
+            NM_MFMA2(acc[0][1], bh1[i], ah0[i]);  if constexpr (anext) al0[j] = lds_read16_untracked<AO + LO>(vau);
+            NM_MFMA2(accl[0][0], bl0[i], ah0[i]);  if constexpr (anext) ah1[j] = lds_read16_untracked<AO + YO>(vau);
+            NM_MFMA2(accl[0][1], bl1[i], ah0[i]);  if constexpr (anext) al1[j] = lds_read16_untracked<AO + LO + YO>(vau);
+            NM_MFMA2(accl[0][0], bh0[i], al0[i]);  if constexpr (bnext) bh0[j] = lds_read16_untracked<BN>(vb);
+            NM_MFMA2(accl[0][1], bh1[i], al0[i]);  if constexpr (bnext) bh1[j] = lds_read16_untracked<BN + 32 * 16>(vb);
+            NM_MFMA2(acc[1][0], bh0[i], ah1[i]);  if constexpr (bnext) bl0[j] = lds_read16_untracked<BN + 128 * 16>(vb);
+            NM_MFMA2(acc[1][1], bh1[i], ah1[i]);  if constexpr (bnext) bl1[j] = lds_read16_untracked<BN + 160 * 16>(vb);
+            NM_MFMA2(accl[1][0], bl0[i], ah1[i]);
+            NM_MFMA2(accl[1][1], bl1[i], ah1[i]);
+            NM_MFMA2(accl[1][0], bh0[i], al1[i]);
+            NM_MFMA2(accl[1][1], bh1[i], al1[i]);
             if constexpr (t == 8) {
                 // tap-group end: the producers publish the next group's weights (and, at the second barrier, the next tile)
                 NM_PSTAMP(1 + 2 * g);
@@ -2503,8 +2490,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
         // the next step's tile is complete since the barrier that ended tap group 2: request its first tap's A operands now (slot 0;
         // the step's first wait covers them)
         if (has_next) {
-            ah0[0] = lds_read16_untracked<0>(van); al0[0] = SINGLE ? half8{} : lds_read16_untracked<LO>(van);
-            ah1[0] = lds_read16_untracked<YO>(van); al1[0] = SINGLE ? half8{} : lds_read16_untracked<LO + YO>(van);
+            ah0[0] = lds_read16_untracked<0>(van); al0[0] = lds_read16_untracked<LO>(van);
+            ah1[0] = lds_read16_untracked<YO>(van); al1[0] = lds_read16_untracked<LO + YO>(van);
         }
         if (cur.cb == C16 - 1) {
             // ---- epilogue of the finished brick (exposed): transposed accumulators -> 16-byte stores, DPP partial sums
@@ -2538,7 +2525,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
                             }
                             acc[mt][nt][4 * k4 + e] = 0.f; acc[mt][nt][4 * k4 + e + 1] = 0.f; accl[mt][nt][4 * k4 + e] = 0.f; accl[mt][nt][4 * k4 + e + 1] = 0.f;
                         }
-                        nm_st4<OH>(p.out, dst + 8 * k4, v);
+                        *reinterpret_cast<f32x4*>(p.out + dst + 8 * k4) = v;
                     }
                 }
                 if (nt == 0) NM_PSTAMP(9); else NM_PSTAMP(11);
@@ -2574,10 +2561,10 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 }
 
 // ---- conv_f16q2: the one-product form (conv modes 3 / 4) of conv_f16p2, re-balanced (round 5) ---------------------------------------
-// In the one-product modes conv_f16p2<SINGLE> keeps the three-product kernel's schedule with two thirds of the MFMAs deleted: a tap
-// group is 36 MFMAs per wave (1 152 cycles) instead of 108, but the producers still fetch each group's weights one group ahead -
-// an L2 round trip plus the register -> LDS copy no longer fits under a group, and three workgroup barriers per step expose it
-// (stand-alone 64 -> 64 @32^3: 0.19-0.31 of the f16 peak, the producers' arrival at the barriers is the step).  Here the schedule is
+// conv_f16p2's schedule with two thirds of the MFMAs deleted (its one-product instantiation, retired: DESIGN_HISTORY.md) did not fit
+// these modes: a tap group is 36 MFMAs per wave (1 152 cycles) instead of 108, but the producers still fetched each group's weights
+// one group ahead - an L2 round trip plus the register -> LDS copy no longer fits under a group, and three workgroup barriers per step
+// exposed it (stand-alone 64 -> 64 @32^3: 0.19-0.31 of the f16 peak, the producers' arrival at the barriers was the step).  Here the schedule is
 // built for one MFMA per staged operand:
 //   * hi-only tiles halve the LDS footprint, so a WHOLE step's weights (27 taps x 16 channels x 64 outputs = 54 KB) are double
 //     buffered and fetched one full step ahead of their use; halo tile two steps ahead as before;
@@ -2585,7 +2572,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 //   * bfloat16 input (mode 4): a producer piece is a 16-byte load of EIGHT channels (one ds_write_b128 per piece, 5 pieces per
 //     thread and step instead of 10 eight-byte ones);
 //   * the MFMA waves keep operands two taps ahead (three register sets, counted lgkmcnt waits): a tap is only four MFMAs.
-// Arithmetic per output element (k order: channel chunk outer, tap inner; epilogue) is conv_f16p2<SINGLE>'s: bit-identical results.
+// Arithmetic per output element (k order: channel chunk outer, tap inner; epilogue) is conv_f16p2's with the two lo products left out.
 //   LDS: halo [2][h0 | h1][600] x 16 B, weights [2][27 taps][h0 | h1][64] x 16 B, GroupNorm scratch, bias: 148 KB + bias.
 template <int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
@@ -2886,7 +2873,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
 #pragma unroll
                         for (int e = 0; e < 4; e += 2) {
                             const f32x2 a2 = f32x2{acc[mt][nt][4 * k4 + e], acc[mt][nt][4 * k4 + e + 1]};
-                            const f32x2 v2 = (a2 + f32x2{0.f, 0.f} * (1.0f / NM_SPLIT_SCALE)) + f32x2{b4[e], b4[e + 1]};      // (conv_f16p2<SINGLE>'s expression: its correction accumulator is zero)
+                            const f32x2 v2 = (a2 + f32x2{0.f, 0.f} * (1.0f / NM_SPLIT_SCALE)) + f32x2{b4[e], b4[e + 1]};      // (conv_f16p2's expression with a zero correction accumulator)
                             const f32x2 q2 = v2 * v2;
                             v[e] = v2[0]; v[e + 1] = v2[1];
                             if (mt == 0) { s1[4 * k4 + e] = v2[0]; s1[4 * k4 + e + 1] = v2[1]; s2[4 * k4 + e] = q2[0]; s2[4 * k4 + e + 1] = q2[1]; }
@@ -3345,7 +3332,7 @@ int launch_t(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) {
 void choose_super_tile(ConvParams& p, int nblocks, int nbz, int nby, int nbx) {
     p.st_z = p.st_y = p.st_x = 0;
     p.st_sx = p.st_sy = p.st_pf = p.st_m_sx = p.st_m_sy = p.st_m_pf = 0;
-    if (!nm_ls().supertile || nblocks % 8) return;
+    if (nblocks % 8) return;
     const int gs = nblocks / 8;
     const int sz = gs == 64 ? 4 : gs == 32 ? 2 : 0;
     if (!sz || nbz % sz || nby % 4 || nbx % 4) return;
@@ -3356,7 +3343,7 @@ void choose_super_tile(ConvParams& p, int nblocks, int nbz, int nby, int nbx) {
     const unsigned SX = (unsigned)nbx / 4u, SY = (unsigned)nby / 4u, pf = SX * SY * (unsigned)(nbz / sz);
     const unsigned long long smax = 8ull * (unsigned long long)(((long long)p.N * nbz * nby * nbx + nblocks - 1) / nblocks) + 8ull;
     auto magic = [](unsigned d) { return d == 1u ? 0u : (unsigned)((0x100000000ull + d - 1ull) / d); };
-    if (nm_ls().fast_decode && smax * pf < 0x100000000ull) {
+    if (smax * pf < 0x100000000ull) {
         p.st_sx = SX; p.st_sy = SY; p.st_pf = pf; p.st_m_sx = magic(SX); p.st_m_sy = magic(SY); p.st_m_pf = magic(pf);
     }
 }
@@ -3417,8 +3404,7 @@ int launch_pool_f16s(const ConvParams& p, dim3 grid, hipStream_t s) {
 }
 
 // The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks, 512 threads): one
-// workgroup per CU (NM355_CONV_WGS caps the count: the co-residency A/B of DESIGN 5 - CUs left to the other queues), the bricks in XCD
-// super-tile order where a brick is one work item.  wgs_cap > 0 is the cap of THIS launch (nm_launch_conv's argument: a conv that runs
+// workgroup per CU, the bricks in XCD super-tile order where a brick is one work item.  wgs_cap > 0 is the cap of THIS launch (nm_launch_conv's argument: a conv that runs
 // beside another stream's chain of small dependent launches leaves it CUs), rounded down to a multiple of 8 so that every XCD keeps
 // the same number of workgroups; a workgroup walks a contiguous run of ceil(items / grid) work items, whatever the grid.  The XCD
 // super-tile exists for grids of 256 and 512 only (choose_super_tile: grid / 8 = 32 or 64), so a capped launch walks its bricks in
@@ -3431,8 +3417,7 @@ int launch_persistent(const char* what_attr, const char* what_launch, int varian
     const int cus = nm_num_cus();
     if (!cus) return NM_ERR_HIP;
     ConvParams p = p_in;
-    int wgs = nm_ls().conv_wgs > 0 ? min(nm_ls().conv_wgs, cus) : cus;
-    if (wgs_cap > 0 && wgs_cap < wgs) wgs = min(wgs, max(8, wgs_cap & ~7));     // (never above the global cap)
+    const int wgs = wgs_cap > 0 && wgs_cap < cus ? min(cus, max(8, wgs_cap & ~7)) : cus;
     dim3 grid((unsigned)min(work_items, wgs));
     if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);
     NmProfScope prof(s, conv_flops(p, 27.0), variant);
@@ -3454,10 +3439,9 @@ int launch_f16p(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap)
     return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s, wgs_cap) : launch_f16p_impl<false>(p, work_items, s, wgs_cap);
 }
 
-template <bool SINGLE, int IO = 0>
 int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p2_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
+    return launch_persistent<&conv_f16p2_kernel>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
 }
 // the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
 template <int IO>
@@ -3474,15 +3458,10 @@ int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs
 }
 int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    if (nm_ls().single && nm_ls().f16q2 && (io == 0 || io == 3) && p.Cout <= 1024) {
-        return io ? launch_f16q2_impl<3>(p, work_items, s, wgs_cap) : launch_f16q2_impl<0>(p, work_items, s, wgs_cap);
-    }
-    if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
-        if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p2", p);
-        return launch_f16p2_impl<true, 3>(p, work_items, s, wgs_cap);
-    }
-    if (nm_ls().single) return launch_f16p2_impl<true>(p, work_items, s, wgs_cap);
-    return launch_f16p2_impl<false>(p, work_items, s, wgs_cap);
+    // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients), one-product modes only
+    if (io && (io != 3 || !nm_ls().single)) return io16_unsupported("conv_f16p2", p);
+    if (nm_ls().single) return io ? launch_f16q2_impl<3>(p, work_items, s, wgs_cap) : launch_f16q2_impl<0>(p, work_items, s, wgs_cap);
+    return launch_f16p2_impl(p, work_items, s, wgs_cap);
 }
 
 #ifdef NM_DIAG
@@ -3576,7 +3555,7 @@ static bool use_up2c(const ConvGeom& g, int Cin) {
 
 // a k2 s2 p0 conv with tiling t goes to the pool kernels: split-fp16 weights, whole 16-channel chunks, 4 x 8 x 8 output bricks
 static bool pool16_case(const Tiling& t, int Cin, bool have_w16) {
-    return nm_ls().conv_mode == 1 && nm_ls().pool16 && have_w16 && Cin % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2;
+    return nm_ls().conv_mode == 1 && have_w16 && Cin % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2;
 }
 
 bool nm_conv_pool16_eligible(int Cin, int OD, int OH, int OW, bool have_w16) {
@@ -3684,10 +3663,10 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
                          in.alt && in.D % 4 == 0 && in.H % 8 == 0 && in.W % 8 == 0)) {
         nm_set_error("conv: a brick-sparse input tensor can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG;
     }
-    p.w16 = (nm_ls().conv_mode == 1 && nm_ls().small16 && w_packed16 && in.C % 8 == 0 && !g.up2 && t.MT == 1 && (t.KC % 16 == 0 || t.KC == in.C)) ? w_packed16 : nullptr;
+    p.w16 = (nm_ls().conv_mode == 1 && w_packed16 && in.C % 8 == 0 && !g.up2 && t.MT == 1 && (t.KC % 16 == 0 || t.KC == in.C)) ? w_packed16 : nullptr;
     if (p.w16) t.lds_bytes = max(t.lds_bytes, (size_t)(((t.KC + 15) & ~15) / 4) * (t.HVp + t.CVp) * 16);
     p.ksplit = 1;
-    if (p.w16 && nm_ls().ksplit) {       // tiny volumes: how many of the 4 row tiles (32 rows each) of the brick hold voxels at all
+    if (p.w16) {       // tiny volumes: how many of the 4 row tiles (32 rows each) of the brick hold voxels at all
         const int top = ((min(g.OD, 1 << t.bz_l2) - 1) << (t.bx_l2 + t.by_l2)) + ((min(g.OH, 1 << t.by_l2) - 1) << t.bx_l2) + min(g.OW, 1 << t.bx_l2) - 1;
         const int rw = top / 32 + 1;
         p.ksplit = rw == 1 ? 4 : (rw == 2 ? 2 : 1);
@@ -3705,12 +3684,14 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
     // the persistent producer / consumer kernels take k3 s1 p1 layers of whole 4 x 8 x 8 bricks, at least four of them along z
     const bool k3_bricks = w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
                            g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16;
-    if (nm_ls().conv_mode == 1 && nm_ls().f16p2 && k3_bricks && g.Cout % 64 == 0) {
+    // (conv_f16q2 keeps a whole step's weights in LDS: a one-product call with more than 1024 output channels - no layer has more
+    // than 256 - goes on to conv_f16s, which has no bfloat16 form for k3)
+    if (nm_ls().conv_mode == 1 && k3_bricks && g.Cout % 64 == 0 && !(nm_ls().single && g.Cout > 1024)) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 64);
         p.w = static_cast<const float*>(w_packed16);
         return launch_f16p2(p, work, s, wgs_cap);
     }
-    if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && nm_ls().f16p && k3_bricks && (in.C == 32 || in.C == 64) && g.Cout == 32 &&
+    if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && k3_bricks &&(in.C == 32 || in.C == 64) && g.Cout == 32 &&
         (p.in_h != 0) == (p.out_h != 0)) {
         // one-product modes, 32 output channels: the layer's weights stay in LDS (conv_f16r_kernel)
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8);
@@ -3718,7 +3699,9 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
         if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s, wgs_cap) : launch_f16r_impl<0, 2>(p, work, s, wgs_cap);
         return p.in_h ? launch_f16r_impl<3, 4>(p, work, s, wgs_cap) : launch_f16r_impl<0, 4>(p, work, s, wgs_cap);
     }
-    if (nm_ls().conv_mode == 1 && nm_ls().f16p && k3_bricks && g.Cout % 32 == 0 && (nm_ls().f16p == 1 || nm_ls().f16p_all || g.Cout == 32)) {
+    // (with more cout groups per brick conv_f16p re-stages the input per group and measures a little slower than conv_f16s: only
+    // conv mode 2, the parity tests of that path, sends every eligible layer here)
+    if (nm_ls().conv_mode == 1 && k3_bricks && g.Cout % 32 == 0 && (nm_ls().f16p_all || g.Cout == 32)) {
         const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 32);
         p.w = static_cast<const float*>(w_packed16);
         return launch_f16p(p, work, s, wgs_cap);
@@ -3773,14 +3756,14 @@ int nm_launch_conv_k5occ(const float* occ, int N, int G, const float* w_packed, 
         hipLaunchKernelGGL(occ_brick_flags_kernel, dim3((unsigned)(N * (G >> 2))), dim3(256), 0, s, occ, G, flags);
         p.flags = flags; p.row_walk = nm_ls().occ_flags >= 2 ? 1 : 0;
     }
-    if (brickmap && (!(nm_ls().conv_mode == 1 && nm_ls().occ16) || (part && !field_part))) {
+    if (brickmap && (nm_ls().conv_mode != 1 || (part && !field_part))) {
         nm_set_error("conv_k5occ: the brick-sparse output exists on the split-fp16 kernel only and needs the field's partial sums"); return NM_ERR_ARG;
     }
     const int NT = (Co_pad % 64 == 0) ? 2 : 1;
     dim3 grid((unsigned)(N * nm_occ_blocks_per_frame(G)), (unsigned)(Co_pad / (NT * 32)));
     if (p.row_walk) grid.x /= (unsigned)(G >> 3);         // one workgroup per x-row of bricks (conv_k5occ_f16_kernel)
     // 16-bit storage: the dense training form on the f16 MFMA kernel only
-    if (out_h && (!(nm_ls().conv_mode == 1 && nm_ls().occ16 && nm_ls().single) || brickmap || Cout % 4)) {
+    if (out_h && (!(nm_ls().conv_mode == 1 && nm_ls().single) || brickmap || Cout % 4)) {
         nm_set_error("conv_k5occ: bfloat16 output needs conv mode 4, the dense (training) form and Cout %% 4 == 0"); return NM_ERR_UNSUPPORTED;
     }
     NmProfScope prof(s, 2.0 * N * (double)G * G * G * Cout * 4.0 * 125.0, 4);   // the reference's dense k5 layer over 4 input channels
@@ -3788,10 +3771,10 @@ int nm_launch_conv_k5occ(const float* occ, int N, int G, const float* w_packed, 
         if (NT == 2) hipLaunchKernelGGL((conv_k5occ_f16_kernel<2, true, false, true>), grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, true, false, true>), grid, dim3(256), 0, s, p);
     } else
-    if (nm_ls().conv_mode == 1 && nm_ls().occ16 && p.row_walk) {
+    if (nm_ls().conv_mode == 1 && p.row_walk) {
         if (NT == 2) { if (nm_ls().single) hipLaunchKernelGGL((conv_k5occ_f16_kernel<2, true, true>), grid, dim3(256), 0, s, p); else hipLaunchKernelGGL((conv_k5occ_f16_kernel<2, false, true>), grid, dim3(256), 0, s, p); }
         else { if (nm_ls().single) hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, true, true>), grid, dim3(256), 0, s, p); else hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, false, true>), grid, dim3(256), 0, s, p); }
-    } else if (nm_ls().conv_mode == 1 && nm_ls().occ16) {
+    } else if (nm_ls().conv_mode == 1) {
         if (NT == 2) { if (nm_ls().single) hipLaunchKernelGGL((conv_k5occ_f16_kernel<2, true>), grid, dim3(256), 0, s, p); else hipLaunchKernelGGL((conv_k5occ_f16_kernel<2>), grid, dim3(256), 0, s, p); }
         else { if (nm_ls().single) hipLaunchKernelGGL((conv_k5occ_f16_kernel<1, true>), grid, dim3(256), 0, s, p); else hipLaunchKernelGGL((conv_k5occ_f16_kernel<1>), grid, dim3(256), 0, s, p); }
     } else if (NT == 2) hipLaunchKernelGGL((conv_k5occ_kernel<2>), grid, dim3(256), 0, s, p);

@@ -100,7 +100,7 @@ struct nm_ctx {
     // ctx-owned block sized by the sizing pass of nm_detector_forward_train
     hipStream_t stream3 = nullptr;
     bool side_shared = false;              // stream2 / stream3 are the process-wide pair of this device (nm_api.hip acquire_side_streams)
-    hipEvent_t ev_w[3] = {nullptr, nullptr, nullptr}, ev_dy = nullptr, ev_wjoin = nullptr, ev_k5 = nullptr;
+    hipEvent_t ev_w[3] = {nullptr, nullptr, nullptr}, ev_dy = nullptr, ev_wjoin = nullptr;
     float* wside = nullptr; size_t wside_floats = 0;                     // the block and its capacity
     size_t wside_slot = 0, wside_scratch = 0, wside_sc = 0;              // floats per ring slot / scratch / scale pool (last sizing pass)
     hipEvent_t ev_user_decoder = nullptr;  // caller's event, recorded by nm_detector_backward once the decoder's gradients are complete
@@ -115,7 +115,6 @@ struct nm_ctx {
     const char* nf_who[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t nf_calls = 0;                 // forward-type calls so far
     unsigned nf_last = 0;                  // status bits of the slot that tripped (1: non-finite conv statistics, 2: rollout time-out)
-    int range_check = 1;                   // NM355_RANGE_CHECK=0 switches the deferred guard off (A/B)
     int learn_sigma = 0;                   // options.fixed_sigma == 0 (kypt_detector.py:258-260): nm_ctx_set_learnable_sigma
     int gauss_cat = 0;                     // options.gaussian_cat_type (kypt_detector.py:396-401): 0 'none', 1 'max', 2 'sum' (nm_ctx_set_gaussian_cat)
     int affinity_ver = 3;                  // get_affinity version (kypt_detector.py:171-210): 3 = the shipped configurations; 0 / 1 / 2 by nm_ctx_set_affinity_ver

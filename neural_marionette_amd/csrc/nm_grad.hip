@@ -1528,7 +1528,7 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const float* __restrict_
 // once instead of per 16-byte item, and four items' tensor loads are in flight before the first is used.  The generic kernel's loop
 // is one item per iteration behind three dependent waits (tensor loads, scale / shift, coefficients) and runs at 4.9 TB/s on
 // occupancy alone.  Identity operands (scale 1 / shift 0, slope 1) leave the values as they are; same arithmetic per element.
-template <bool RANK1, bool COEF, bool H, unsigned U = 4u>
+template <bool RANK1, bool COEF, bool H>
 __global__ __launch_bounds__(256) void gnb_apply4_kernel(const float* __restrict__ dA, TensorRef y, const float* __restrict__ coef,
                                                          float* __restrict__ dy, unsigned* __restrict__ amax, const float* __restrict__ dmul,
                                                          const float* __restrict__ dv, const float* __restrict__ wv) {
@@ -1563,7 +1563,7 @@ __global__ __launch_bounds__(256) void gnb_apply4_kernel(const float* __restrict
         mx = fmaxf(fmaxf(mx, fmaxf(fabsf(d[0]), fabsf(d[1]))), fmaxf(fabsf(d[2]), fabsf(d[3])));
     };
     unsigned r = r0;
-    // U items in flight (bfloat16: eight 8-byte loads = the bytes of four fp32 ones; NM355_GNB_U8=0: four, A/B)
+    constexpr unsigned U = H ? 8u : 4u;       // items in flight (bfloat16: eight 8-byte loads = the bytes of four fp32 ones)
     for (; r + (U - 1u) * step < per_frame && r + (U - 1u) * step >= r; r += U * step) {
         f32x4 yy[U], dd[U];
 #pragma unroll
@@ -1925,8 +1925,8 @@ WgradPlan plan_wgrad(int N, int OD, int OH, int OW, int M, int Nc, int ks, int s
         // workgroups of a launch: one per CU, or - when the weight gradients run on their own stream beside the main stream's walk
         // (nm_net.hip conv_bwd) - 224, which leaves 32 CUs to the GroupNorm passes and small kernels of the walk: a whole-CU kernel on
         // every CU admits nothing beside it until it ends (73.0 -> 71.3 ms per training step; 208: 71.7, 240: 72.9, 192: 72.7; in the
-        // reduced-precision mode 256 stays better: 53.4 vs 53.9).  NM355_WGRAD_WGS overrides.
-        const int wgs = nm_ls().wgrad_wgs > 0 ? nm_ls().wgrad_wgs : (nm_ls().wgrad_async == 1 && !nm_ls().single ? 224 : 256);
+        // reduced-precision mode 256 stays better: 53.4 vs 53.9).
+        const int wgs = nm_ls().wgrad_async == 1 && !nm_ls().single ? 224 : 256;
         p.S = max(1, min(total, max(tiles, wgs) / tiles));
         // wgrad16z_kernel hands out whole (frame, y, x) columns: no more workgroups per tile pair than columns
         const bool z = w16z_takes(N, p.nbz, false);
@@ -2054,7 +2054,7 @@ static bool k1_wide_eligible(int OD, int OH, int OW, int M, int Nc, int ks, int 
 
 // wgrad16k2_kernel: k2 s2 p0 layers whose fine grid is exactly twice the coarse one, whole 8 x 8 coarse (y, x) bricks, <= 128 dY channels
 static bool k2f16_shape_eligible(int OD, int OH, int OW, int M, int ks, int stride) {
-    return nm_ls().wgrad_k2f16 && ks == 2 && stride == 2 && OH % 8 == 0 && OW % 8 == 0 && OD > 0 && M <= 128;
+    return ks == 2 && stride == 2 && OH % 8 == 0 && OW % 8 == 0 && OD > 0 && M <= 128;
 }
 static int k2f16_slots(int N, int OD, int OH, int OW, int Nc) {
     const int n_tiles = (Nc + 31) / 32, total = N * OD * (OH / 8) * (OW / 8);
@@ -2132,8 +2132,7 @@ int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride
     return run_wgrad(q, ws, dW, cin_real, ks * ks * ks, s, mul);
 }
 
-int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, float* dW, hipStream_t s, int sparse_occ,
-                          hipStream_t s_coord, hipEvent_t ev_fork, hipEvent_t ev_join) {
+int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, float* dW, hipStream_t s, int sparse_occ) {
     if (dy.C % 4 || dy.D != G) { nm_set_error("wgrad_k5occ: bad dy"); return NM_ERR_ARG; }
     TensorRef in; in.p = occ; in.scale = in.shift = nullptr; in.slope = 1.0f; in.N = N; in.D = in.H = in.W = G; in.C = 1;
     const bool sparse = sparse_occ && (dy.C == 32 || dy.C == 64) && !dy.scale && dy.slope == 1.0f;
@@ -2147,24 +2146,14 @@ int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, f
     float* dysum = ws; float* zocc = dysum + G3 * C; float* dense_ws = zocc + ((G3 + 63) & ~(size_t)63);
     WgradPlan q = plan_wgrad(1, G, G, G, C, 4, 5, 1, true);
     float* part = dense_ws + ((q.ws_floats + 63) & ~(size_t)63);
-    // coordinate channels: one frame holding the sum of dy over the frames, empty occupancy.  s_coord (with its two events): that part
-    // on a second stream beside the occupancy channel's kernel below - the two are the serial tail of the backward pass (0.41 + 0.68 ms
-    // at 64^3 x 64 frames with nothing else left to run); the occupancy channel's final reduce waits for both.
-    const bool two = s_coord && ev_fork && ev_join && s_coord != s && sparse_occ == 1 && G % 8 == 0;
-    hipStream_t sc = two ? s_coord : s;
-    int rc;
-    if (two) {
-        if ((rc = nm_check_hip(hipEventRecord(ev_fork, s), "wgrad_k5occ: fork event"))) return rc;
-        if ((rc = nm_check_hip(hipStreamWaitEvent(sc, ev_fork, 0), "wgrad_k5occ: fork wait"))) return rc;
-    }
-    hipLaunchKernelGGL(sum_frames4_kernel, dim3(grid_for(G3 * C / 4)), dim3(256), 0, sc, dy.p, N, G3 * C / 4, dysum, dy.h);
-    rc = nm_check_hip(hipMemsetAsync(zocc, 0, G3 * sizeof(float), sc), "wgrad_k5occ: memset");
+    // coordinate channels: one frame holding the sum of dy over the frames, empty occupancy
+    hipLaunchKernelGGL(sum_frames4_kernel, dim3(grid_for(G3 * C / 4)), dim3(256), 0, s, dy.p, N, G3 * C / 4, dysum, dy.h);
+    int rc = nm_check_hip(hipMemsetAsync(zocc, 0, G3 * sizeof(float), s), "wgrad_k5occ: memset");
     if (rc) return rc;
     TensorRef in1 = in; in1.p = zocc; in1.N = 1;
     TensorRef dy1 = dy; dy1.p = dysum; dy1.N = 1; dy1.h = 0;         // (the frame sum is fp32)
     q.p.in = in1; q.p.dy = dy1; q.p.pad = 2;
-    if ((rc = run_wgrad(q, dense_ws, dW, 4, 125, sc))) return rc;
-    if (two && (rc = nm_check_hip(hipEventRecord(ev_join, sc), "wgrad_k5occ: join event"))) return rc;
+    if ((rc = run_wgrad(q, dense_ws, dW, 4, 125, s))) return rc;
     // occupancy channel: matrix cores over the non-empty bricks (sparse_occ 1, grids that are whole 4x8x8 bricks), else the gather
     if (sparse_occ == 1 && G % 8 == 0) {
         static NmDeviceOnce attr_set;
@@ -2179,7 +2168,6 @@ int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, f
         } else
         if (C == 32) hipLaunchKernelGGL((wgrad_k5occ_mfma_kernel<32>), dim3(blocks), dim3(256), ldsb, s, occ, dy.p, N, G, part);
         else hipLaunchKernelGGL((wgrad_k5occ_mfma_kernel<64>), dim3(blocks), dim3(256), ldsb, s, occ, dy.p, N, G, part);
-        if (two && (rc = nm_check_hip(hipStreamWaitEvent(s, ev_join, 0), "wgrad_k5occ: join wait"))) return rc;
         hipLaunchKernelGGL(wgrad_k5occ_sparse_reduce_kernel, dim3((125 * C + 255) / 256), dim3(256), 0, s, part, blocks, C, dW);
         return nm_check_hip(hipGetLastError(), "wgrad_k5occ mfma launch");
     }
@@ -2248,8 +2236,7 @@ int nm_launch_gnb_apply(const float* dA, const TensorRef& y, const float* coef, 
     const unsigned bx = (unsigned)min((frame4 + 255) / 256, (size_t)max(1, 4096 / max(y.N, 1)));
     if (nm_ls().gnb_apply4 && 1024 % y.C == 0) {
         const dim3 g(bx, y.N);
-#define NM_GNB_APPLY4(R, Cf) do { if (y.h && nm_ls().gnb_u8) hipLaunchKernelGGL((gnb_apply4_kernel<R, Cf, true, 8u>), g, dim3(256), 0, s, dA, y, coef, dy, amax, dA_mul, dv, wv); \
-                                 else if (y.h) hipLaunchKernelGGL((gnb_apply4_kernel<R, Cf, true>), g, dim3(256), 0, s, dA, y, coef, dy, amax, dA_mul, dv, wv); \
+#define NM_GNB_APPLY4(R, Cf) do { if (y.h) hipLaunchKernelGGL((gnb_apply4_kernel<R, Cf, true>), g, dim3(256), 0, s, dA, y, coef, dy, amax, dA_mul, dv, wv); \
                                  else hipLaunchKernelGGL((gnb_apply4_kernel<R, Cf, false>), g, dim3(256), 0, s, dA, y, coef, dy, amax, dA_mul, dv, wv); } while (0)
         if (dv) { if (coef) NM_GNB_APPLY4(true, true); else NM_GNB_APPLY4(true, false); }
         else if (coef) NM_GNB_APPLY4(false, true);
@@ -2281,7 +2268,7 @@ int nm_launch_scale_by(float* x, size_t n, const float* mul, hipStream_t s, int 
 int nm_launch_upsample2_adjoint(const float* dfine, int N, int D, int H, int W, int C, float* dcoarse, hipStream_t s, const float* mul, int hf, int hc) {
     if (C % 4) { nm_set_error("upsample2_adjoint: C %% 4 != 0"); return NM_ERR_ARG; }
     const size_t total = (size_t)N * D * H * W * (C / 4);
-    if (nm_ls().adj_zwalk && C % (hf ? 64 : 32) == 0 && H % UZ_BY == 0 && W % UZ_BX == 0 && D >= 2 && (size_t)4 * H * W * C < ((size_t)1 << 31) && total >= 16384) {
+    if (C % (hf ? 64 : 32) == 0 && H % UZ_BY == 0 && W % UZ_BX == 0 && D >= 2 && (size_t)4 * H * W * C < ((size_t)1 << 31) && total >= 16384) {
         const unsigned cols = (unsigned)(N * (H / UZ_BY) * (W / UZ_BX)), chunks = (unsigned)(C / (hf ? 64 : 32));
         unsigned zs = 1;
         while (zs < 4 && cols * chunks * zs < 2048 && D % (2 * zs) == 0 && D / (2 * zs) >= 4) zs *= 2;

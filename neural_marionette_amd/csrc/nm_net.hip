@@ -288,7 +288,7 @@ struct Loader {
         // the field's own GroupNorm partial sums per brick, by the first-layer kernel itself on the empty frame (bit-identical to what
         // it computes for an empty brick of any frame): what the sparse first layer reports for the bricks it skips
         f.field_part = nullptr;
-        if (!r && !c->training && nm_conv_get_mode() == 1 && nm_ls().occ16 && nm_ls().sparse_first) {
+        if (!r && !c->training && nm_conv_get_mode() == 1 && nm_ls().sparse_first) {
             const int nblk = nm_occ_blocks_per_frame(G);
             f.field_part = nm_ctx_weight_alloc(c, (size_t)nblk * Cout * 2);
             float* scratch = nm_ctx_weight_alloc(c, G3 * Cout);           // (dense output of that one launch; reused at the next update)
@@ -574,7 +574,7 @@ TensorRef first_layer(Net& n, const float* occ, int N, int G, const FeatNetW& w,
     // inference: bricks with an empty occupancy halo (most of the grid around one figure) are neither computed nor written; the pool
     // conv - this tensor's only consumer - reads the constant field there (TensorRef::alt / brickmap).  Training keeps the dense
     // tensor (the backward pass reads it).
-    const bool sparse = !rec && w.field_part && nm_conv_get_mode() == 1 && nm_ls().occ16 && nm_ls().sparse_first &&
+    const bool sparse = !rec && w.field_part && nm_conv_get_mode() == 1 && nm_ls().sparse_first &&
                         nm_conv_pool16_eligible(Cout, G / 2, G / 2, G / 2, w.p1.c.wp16 != nullptr);
     unsigned char* bmap = sparse ? reinterpret_cast<unsigned char*>(n.alloc(((size_t)N * nblk + 3) / 4)) : nullptr;
     unsigned char* bflags = sparse ? reinterpret_cast<unsigned char*>(n.alloc(((size_t)N * nblk + 3) / 4)) : nullptr;
@@ -741,8 +741,7 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
     };
     (void)n.ws.alloc_bytes(clip_need);                          // reserve [clip_r0, clip_r0 + clip_need)
     n.ws.top = clip_r0 + clip_need;
-    const int clip_after = nm_ls().clip_late ? (tape ? 1 : 2) : 0;     // per-frame chunks enqueued before the clip block
-    if (clip_after == 0) run_clip_block();
+    const int clip_after = tape ? 1 : 2;     // per-frame chunks enqueued before the clip block
     const size_t chunk = tape ? (size_t)F : FRAME_CHUNK;       // training keeps every activation: one pass over all frames
     int chunks_done = 0;
     for (size_t f0 = 0; f0 < (size_t)F; f0 += chunk) {   // per-frame encoder (kypt_detector.py:330-336)
@@ -980,7 +979,7 @@ float* conv_bwd(Bwd& b, const ConvRec& r, const float* dA, bool need_din, const 
     const bool split = nm_conv_get_mode() != 0;          // split-fp16 kernels: dy is read pre-scaled by a power of two
     DyScale ds;
     // (the k2 s2 pool convs: their weight gradient runs on the f16 matrix cores as well, wgrad16k2_kernel)
-    ds.prepare(b, split && ((r.stride == 1 && (w.ks == 3 || (need_din && w.wd16))) || (r.stride == 2 && w.ks == 2 && nm_ls().wgrad_k2f16)), r.out.N * r.out.C, sc2_keep);
+    ds.prepare(b, split && ((r.stride == 1 && (w.ks == 3 || (need_din && w.wd16))) || (r.stride == 2 && w.ks == 2)), r.out.N * r.out.C, sc2_keep);
     const bool padded = w.Cout_src > 0 && w.Cout_src < w.Cout;      // output channels padded inside the library (the heat-map heads)
     if (padded && r.gn && !b.rc) { nm_set_error("detector_backward: a padded layer with GroupNorm"); b.rc = NM_ERR_STATE; }
     const float* dy = norm_bwd(b, r.out, r.gn, r.fpart, r.nblk, r.chsum, w.key + ".bias", dA, ds.amax, dA_mul, dA_dv, dA_wv, padded ? w.Cout_src : 0);
@@ -1131,7 +1130,7 @@ float* hourglass_bwd(Bwd& b, const HgRec& h, const float* dOut) {
     return d_x0;
 }
 
-void feature_net_bwd(Bwd& b, const FeatRec& r, const float* dFeat, bool sparse_occ) {
+void feature_net_bwd(Bwd& b, const FeatRec& r, const float* dFeat) {
     const size_t m = b.ws.mark();
     float* d_hg = res_bwd(b, r.r5, dFeat);
     float* d_p3 = hourglass_bwd(b, r.hg, d_hg);
@@ -1143,10 +1142,7 @@ void feature_net_bwd(Bwd& b, const FeatRec& r, const float* dFeat, bool sparse_o
     const float* dy = norm_bwd(b, r.first, &w.n0, r.fpart0, r.nblk0, r.chsum0, w.c0.key + ".bias", d_first);
     float* wsb = b.alloc(nm_wgrad_k5occ_ws_floats(r.N, r.G, w.c0.Cout));
     float* gw = b.grad(w.c0.key + ".weight", (int64_t)w.c0.Cout * 4 * 125);
-    // (the main walk's first layer is the last thing the backward pass does: its two halves on two streams, nm_launch_wgrad_k5occ)
-    const bool two = b.async_w && nm_ls().k5_two && b.s == b.c->stream && b.c->stream3 && b.c->stream3 != b.s;
-    if (b.live()) b.run(nm_launch_wgrad_k5occ(r.occ, r.N, r.G, plain(dy, r.first), wsb, gw, b.s, sparse_occ ? 1 : 0,
-                                               two ? b.c->stream3 : nullptr, b.c->ev_dy, b.c->ev_k5));
+    if (b.live()) b.run(nm_launch_wgrad_k5occ(r.occ, r.N, r.G, plain(dy, r.first), wsb, gw, b.s));
     b.ws.release(m);
 }
 
@@ -1286,7 +1282,7 @@ int backward_graph(nm_ctx* c, const TrainTape& t, const float* dloss, const std:
         // (the clip-mean grid is the union of T frames, 15-30 % dense: the gather form of the sparse first-layer gradient loses there, but
         //  the matrix-core form - frame-summed dY for the coordinate channels, non-empty bricks for the occupancy channel, exact fp32
         //  products - does not depend on 0 / 1 occupancies)
-        feature_net_bwd(b2, t.clip, dfclip, nm_ls().clip_occ_mfma != 0);
+        feature_net_bwd(b2, t.clip, dfclip);
         const size_t local_peak = b2.ws.peak;
         b2.ws.peak = saved_peak > local_peak ? saved_peak : local_peak;
         b2.ws.top = local_peak;
@@ -1294,7 +1290,7 @@ int backward_graph(nm_ctx* c, const TrainTape& t, const float* dloss, const std:
         if (b2.live()) b2.run(nm_check_hip(hipEventRecord(c->ev_side, c->stream2), "backward: side event"));
         b.run(b2.rc);
     }
-    feature_net_bwd(b, t.frame, dfeat, true);
+    feature_net_bwd(b, t.frame, dfeat);
     b.flush_sums();
     if (b.live()) b.run(nm_check_hip(hipStreamWaitEvent(b.s, c->ev_side, 0), "backward: join side stream"));
     if (b.async_w) {
@@ -1343,7 +1339,7 @@ int check_ready(nm_ctx* c, const char* who) {
 // A set slot clears the device word, drops the younger slots (they saw the same sticky word) and fails the CURRENT call with
 // NM_ERR_RANGE naming the call that overflowed: its outputs, handed out earlier, hold NaN / inf.
 int nm_nf_poll(nm_ctx* c) {
-    if (!c->range_check || !c->nf_host) return NM_OK;
+    if (!c->nf_host) return NM_OK;
     int bad = -1;
     for (int i = 0; i < 4; ++i) {
         if (!c->nf_busy[i]) continue;
@@ -1382,7 +1378,7 @@ int nm_nf_poll(nm_ctx* c) {
 }
 void nm_nf_post(nm_ctx* c, const char* who) {
     ++c->nf_calls;
-    if (!c->range_check || !c->nf_host) return;
+    if (!c->nf_host) return;
     int k = -1;
     for (int i = 0; i < 4; ++i) if (!c->nf_busy[i]) { k = i; break; }
     if (k < 0) return;                     // (cannot happen: nf_poll retires every slot two calls old)
@@ -1430,7 +1426,7 @@ int nm_net_set_weights(nm_ctx* c, const std::map<std::string, std::pair<const fl
         w = ConvW(); w.Cin = Cr; w.Cout = FEAT; w.ks = 1; w.Cin_pad = (Cr + 7) & ~7; w.Co_pad = (FEAT + 31) & ~31; w.key = key;
         d.adjust_wg = nullptr;
         const float* src = L.get(key + ".weight", (int64_t)FEAT * Cin);
-        if (src && !c->training && nm_ls().adjust_split) {
+        if (src && !c->training) {
             w.wp = nm_ctx_weight_alloc(c, nm_packed_weight_floats(1, w.Cin_pad, w.Co_pad));
             d.adjust_wg = nm_ctx_weight_alloc(c, (size_t)K * FEAT);
             if (!w.wp || !d.adjust_wg) { if (!L.rc) { nm_set_error("set_weights: hipMalloc failed"); L.rc = NM_ERR_HIP; } }

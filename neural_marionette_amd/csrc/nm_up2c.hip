@@ -1552,7 +1552,7 @@ __global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, 
 }  // namespace
 
 bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad) {
-    return nm_ls().up2c && ks == 3 && stride == 1 && pad == 1 && ID % BZ == 0 && IH % BY == 0 && IW % BX == 0 && Cin % CG == 0 && Cout % 32 == 0 &&
+    return ks == 3 && stride == 1 && pad == 1 && ID % BZ == 0 && IH % BY == 0 && IW % BX == 0 && Cin % CG == 0 && Cout % 32 == 0 &&
            ((Cin == 64 && Cout == 32) || (nm_ls().up2y && !nm_conv_single() && Cin <= 128 && Cout <= 64));      // (the wider layer: in the product form only - the one-product modes and NM355_UP2Y=0 keep it on conv_f16s)
 }
 

@@ -141,6 +141,31 @@ def test_conv3d(ctx, case, mode):
         assert e < REL, f"fused GroupNorm rel err {e:.3e}"
 
 
+def test_conv3d_one_product_mode_beyond_1024_output_channels(ctx):
+    """conv_f16q2 keeps a whole step's weights in LDS and takes up to 1024 output channels (no layer has more than 256).  Beyond that a
+    one-product call with fp32 storage goes on to the next eligible kernel and meets test_conv3d's bounds; with bfloat16 storage it is
+    refused, like every k3 shape without a bfloat16 kernel.  The split-fp16 mode runs the same shape on conv_f16p2 (17 cout groups)."""
+    from neural_marionette_amd import _lib
+    case = (16, 1088, 3, 1, 1, 16, 1, True, 34)
+    test_conv3d(ctx, case, 1)
+    test_conv3d(ctx, case, 3)
+    Cin, Cout, ks, stride, pad, size, N = case[:7]
+    x = torch.zeros(N, size, size, size, Cin, dtype=torch.bfloat16, device="cuda")
+    out = torch.zeros(N, size, size, size, Cout, dtype=torch.bfloat16, device="cuda")
+    w = torch.zeros(Cout, Cin, ks, ks, ks, device="cuda"); b = torch.zeros(Cout, device="cuda")
+    _lib.check(ctx.lib.nm_set_conv_mode(ctx.handle, 4), "set_conv_mode")
+    _lib.check(ctx.lib.nm_op_set_storage16(ctx.handle, 1, 1), "op_set_storage16")
+    try:
+        rc = ctx.lib.nm_op_conv3d(ctx.handle, _lib.ptr(x), N, size, size, size, Cin, None, None, 1.0, _lib.ptr(w), _lib.ptr(b),
+                                  Cout, ks, stride, pad, _lib.ptr(out), 0, None, None, None, None, 0)
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(ctx.lib.nm_op_set_storage16(ctx.handle, 0, 0), "op_set_storage16")
+        _lib.check(ctx.lib.nm_set_conv_mode(ctx.handle, 1), "set_conv_mode")
+    assert rc == _lib.NM_ERR_UNSUPPORTED, (rc, ctx.lib.nm_last_error())
+    assert not out.any(), "a refused call wrote its output"
+
+
 @pytest.mark.parametrize("mode", [0, 1, 3], ids=["fp32mfma", "split16", "f16"])
 @pytest.mark.parametrize("Cin,Cout,size,prologue,N", [(128, 64, 8, False, 2), (64, 32, 12, True, 2), (16, 32, 5, True, 2),
                                                        (32, 32, 16, True, 5), (48, 32, 8, False, 40), (64, 64, 16, True, 3)])

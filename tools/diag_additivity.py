@@ -17,6 +17,6 @@ for k, v in g_ab.items():
     scale = max(avg.abs().max().item(), 1e-6 * gmax)
     rows.append(((v.double() - avg).abs().max().item() / scale, k, avg.abs().max().item(), g_a[k].abs().max().item(), g_b[k].abs().max().item()))
 rows.sort(reverse=True)
-print("env K2F16=%s CONVT_F16=%s mode %s gmax %.3e" % (os.environ.get("NM355_WGRAD_K2F16"), os.environ.get("NM355_CONVT_F16"), mode, gmax))
+print("mode %s gmax %.3e" % (mode, gmax))
 for r in rows[:8]:
     print("  %.3e  %-60s |avg|max %.3e  |a| %.3e |b| %.3e" % r)

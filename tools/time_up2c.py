@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the fused-upsample 64 -> 32 layer at the bench shape (64 frames, 32^3 -> 64^3) through nm_op_conv3d.
-usage: time_up2c.py [reps]   (NM355_UP2C / NM355_UP2Y / NM355_UP2C_SHELL select the kernels, NM355_TIME_MODE the conv mode)"""
+usage: time_up2c.py [reps]   (NM355_UP2Y / NM355_UP2C_SHELL select the kernels, NM355_TIME_MODE the conv mode)"""
 import sys, os, torch, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neural_marionette_amd import _lib
@@ -26,5 +26,5 @@ for _ in range(reps):
     a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record(); call(); e.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(e))
 ts.sort()
-print("UP2C=%s UP2Y=%s  median %.3f ms  min %.3f ms  (whole op: compose + pack + conv + shell + gn_finalize)" % (
-    os.environ.get("NM355_UP2C", "1"), os.environ.get("NM355_UP2Y", "1"), ts[len(ts) // 2], ts[0]))
+print("UP2Y=%s  median %.3f ms  min %.3f ms  (whole op: compose + pack + conv + shell + gn_finalize)" % (
+    os.environ.get("NM355_UP2Y", "1"), ts[len(ts) // 2], ts[0]))
