@@ -22,6 +22,7 @@
 //   sum / sum-of-squares partials for the following GroupNorm (deterministic: no float
 //   atomics).
 #include "nm_common.h"
+#include "nm_f16p8_plan.h"
 #include "nm_up2c.h"
 #include <type_traits>
 #include <utility>
@@ -2560,6 +2561,370 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
     }
 }
 
+// ---- conv_f16p8: conv_f16p2's skeleton on 8 x 8 x 8 bricks for the 32-output-channel layers ---------------------------------------
+// conv_f16p2 gets twice the MFMAs per staged step from a second column block of output channels; a 32-channel layer has none, so
+// this kernel takes the factor two spatially: a brick is 8(z) x 8(y) x 8(x), and wave w owns brick rows y = 2w, 2w + 1 in BOTH z halves -
+// four 32-row tiles x one 32-channel column block, 27 taps x 12 MFMAs per step, 8 A reads + 2 B reads per tap.  Per step the producers
+// stage one 10 x 10 x 10 halo tile (1.95 staged voxels per output voxel, 2.34 on 4 x 8 x 8 bricks) and the same 27 x 2 KB of weights
+// as conv_f16p, now for twice the MFMAs.  Everything else is conv_f16p2's: one persistent 512-thread workgroup per CU, MFMA waves 0-3
+// and producer waves 4-7, halo tile double buffered and two steps ahead, operands one tap ahead, exposed epilogue with one extra
+// workgroup barrier per brick, counted producer waits.
+//   LDS: the two halo tiles take 128 000 B, so the taps are cut 7 / 7 / 7 / 6 into two 7-tap weight buffers (group g in buffer g & 1):
+//   four barriers per 324-MFMA step.  halo [2][hi h0 | hi h1 | lo h0 | lo h1][1000] x 16 B, weights [2][7 taps][4 planes][32] x 16 B,
+//   GroupNorm scratch [2 z halves][4 waves][32][2], bias: 158 848 B.
+//   Barriers: both roles take theirs from nm_f16p8_plan.h (group ends, brick end); tests/cpp/f16p8_barrier_walk.cpp walks both.
+// Arithmetic per output element is conv_f16p's, operation for operation (chunks ascending, taps 0 ... 26, per tile acc += bh ah,
+// accl += bl ah, accl += bh al; (acc + accl 2^-11) + bias), and a brick writes the two GroupNorm partial rows of the two 4 x 8 x 8
+// bricks it covers exactly as conv_f16p would: stored outputs, partial sums and everything downstream are bit-identical.
+// Split-fp16 (three products), fp32 storage, Cout == 32, OD % 8 == 0; conv_f16p keeps every other case.
+__global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
+    namespace pl = nm_f16p8;
+    constexpr int HV = pl::kHaloVoxels, ZP = 100, HX = 10;
+    constexpr int GB = pl::kWeightBufSlots;                         // half8 slots of one weight buffer
+    constexpr int NP = pl::kPieces;
+    static_assert(HV == 10 * ZP && ZP == 10 * HX, "10 x 10 x 10 halo tile");                                 // 16-byte input pieces per producer thread and step (4000 / 256)
+    static_assert(NP * 256 >= 4 * HV && (NP - 1) * 256 < 4 * HV, "pieces cover the tile");
+    extern __shared__ f32x4 lds[];
+    half8* ldh = reinterpret_cast<half8*>(lds);                     // [2][4][HV]
+    half8* ldb = ldh + pl::kHaloSlots;                              // [2][GB]
+    float* red = reinterpret_cast<float*>(ldb + pl::kWeightSlots);  // [2 z halves][4 waves][32 channels][2]
+    float* lbias = red + pl::kRedFloats;                            // [32] bias (zeros without one), written once by the producers; the layout is nm_f16p8_plan.h's (kLdsBytes)
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, l31 = lane & 31;
+    const int C16 = p.Cin >> 4;
+    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 3, nbr = nbx * nby * nbz;
+    const int total = p.N * nbr;
+    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
+    if (id_first >= id_last) return;
+    const int items = id_last - id_first;
+
+    struct Work { int n, oz0, oy0, ox0; };
+    const bool tiled = p.st_x != 0;                                 // XCD super-tile order on 8 x 8 x 8 bricks, see super_tile_item
+    auto decode = [&](int id) {
+        Work w;
+        if (tiled) {
+            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
+            w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 3;
+            return w;
+        }
+        w.n = id / nbr; const int br = id % nbr;
+        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 3;
+        return w;
+    };
+    auto next_work = [&](Work w, int id) {
+        if (tiled) return decode(id);
+        if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 8) == p.OD) { w.oz0 = 0; ++w.n; } } }
+        return w;
+    };
+    struct Step { Work w; pl::Cursor c; };
+    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
+        const int item = st.c.item;
+        if (!pl::next_step(st.c, items, C16)) return false;
+        if (st.c.item != item) st.w = next_work(st.w, id_first + st.c.item);
+        return true;
+    };
+
+    if (wave >= 4) {
+        // =========================== producer waves ===========================================================
+        const int pt = tid - 256, pw = wave - 4;
+        const half8* __restrict__ w8 = reinterpret_cast<const half8*>(p.w);
+        const size_t plane = (size_t)p.Co_pad;
+        const int lane_off = h * (int)plane + l31;
+        const int quad = pt & 3;
+        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int v = (pt >> 2) + 64 * k, vc = min(v, HV - 1);
+            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
+            pc_slot[k] = (quad >> 1) * HV + hz * ZP + hy * HX + hx;    // half8 slot of the hi part in a halo buffer (lo: + 2 HV)
+            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + 4 * quad;
+            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
+        }
+        f32x4 raw[NP], sc, sh, wreg[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const bool has_affine = p.in_scale != nullptr;
+        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * 4u;   // halo voxel (1,1,1): always inside (byte offset)
+        auto inside_mask = [&](const Work& w) {
+            unsigned m = 0;
+#pragma unroll
+            for (int k = 0; k < NP; ++k) {
+                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
+                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
+                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
+                m |= (in ? 1u : 0u) << k;
+            }
+            return m;
+        };
+        auto tile_base = [&](const Work& w, int cb) {
+            return p.in + (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16);
+        };
+        auto load_piece = [&](const float* base, unsigned mask, auto K) {      // outside pieces fetch an inside voxel (zeroed later)
+            constexpr int k = decltype(K)::value;
+            raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * 4u : rel111);
+        };
+        auto load_affine = [&](const Work& w, int cb) {             // always two loads: the waits below count instructions
+            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
+            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
+            sc = load16_untracked(ps, 16u * quad);
+            sh = load16_untracked(ph, 16u * quad);
+        };
+        // wait until all but the N youngest vector-memory operations are done; ties every load destination to the wait
+#define NM_PRODUCER8_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" \
+            : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]), "+v"(raw[6]), "+v"(raw[7]), \
+              "+v"(raw[8]), "+v"(raw[9]), "+v"(raw[10]), "+v"(raw[11]), "+v"(raw[12]), "+v"(raw[13]), "+v"(raw[14]), "+v"(raw[15]), \
+              "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]) :: "memory")
+        auto convert = [&](int buf, unsigned mask, auto K) {        // activate, split, write piece k into halo buffer buf
+            constexpr int k = decltype(K)::value;
+            half4v hi4, lo4;
+            const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
+#pragma unroll
+            for (int e = 0; e < 4; e += 2) {
+                float v0 = raw[k][e], v1 = raw[k][e + 1];
+                if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
+                v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
+                half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
+                asm volatile("" : "+v"(hv));
+                const float t0 = v0 * NM_SPLIT_SCALE, t1 = v1 * NM_SPLIT_SCALE;
+                hi4[e] = hv[0]; hi4[e + 1] = hv[1];
+                lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
+                lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
+            }
+            if (pc_pos[k] >= 0) {
+                half4v* dst = reinterpret_cast<half4v*>(ldh + buf * 4 * HV + pc_slot[k]) + (quad & 1);
+                dst[0] = hi4;
+                dst[4 * HV] = lo4;                                  // + 2 HV half8 slots
+            }
+        };
+        // tap group g of chunk cb: group_taps(g) x 2 one-KiB wave pieces (tap t, hi | lo; lanes = plane half h x 32 channels).  Every
+        // producer wave issues four loads per group so that the counted waits are the same in all of them: 14 pieces (12 in the six-tap
+        // group) dealt round robin, the surplus slots repeat the group's last piece.
+        constexpr int NW = 4;
+        unsigned w_src[NW], w_dst[NW], w_src6, w_dst6;
+        {
+            auto piece = [&](int j, unsigned& src, unsigned& dst) {
+                const int t = j >> 1, lo = j & 1;
+                src = (unsigned)(((size_t)t * C16 * 4 + lo * 2) * plane + lane_off) * 16u;
+                dst = (unsigned)(t * 128 + lo * 64 + lane) * 16u;
+            };
+#pragma unroll
+            for (int i = 0; i < NW; ++i) piece(min(pw + 4 * i, 2 * pl::group_taps(0) - 1), w_src[i], w_dst[i]);
+            piece(min(pw + 4 * (NW - 1), 2 * pl::group_taps(pl::kGroups - 1) - 1), w_src6, w_dst6);
+        }
+        static_assert(4 * NW >= 2 * pl::kGroupTaps && 4 * (NW - 1) <= 2 * pl::group_taps(pl::kGroups - 1), "only the last slot of a wave can pass a group's end");
+        auto load_b_group = [&](int cb, auto G) {
+            constexpr int g = decltype(G)::value;
+            constexpr bool short_group = pl::group_taps(g) < pl::kGroupTaps;
+            const char* base = reinterpret_cast<const char*>(w8 + ((size_t)pl::group_first(g) * C16 * 4 + (size_t)cb * 4) * plane);
+            const float* src[NW];
+#pragma unroll
+            for (int i = 0; i < NW; ++i) src[i] = reinterpret_cast<const float*>(base + ((short_group && i == NW - 1) ? w_src6 : w_src[i]));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < NW; ++i) wreg[i] = load16_untracked(src[i]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto store_b_group = [&](auto G) {                          // group g -> weight buffer g & 1
+            constexpr int g = decltype(G)::value;
+            constexpr bool short_group = pl::group_taps(g) < pl::kGroupTaps;
+            __builtin_amdgcn_sched_barrier(0);
+            char* lbase = reinterpret_cast<char*>(ldb + (g & 1) * GB);
+#pragma unroll
+            for (int i = 0; i < NW; ++i) *reinterpret_cast<f32x4*>(lbase + ((short_group && i == NW - 1) ? w_dst6 : w_dst[i])) = wreg[i];
+        };
+
+        Step cur; cur.w = decode(id_first); cur.c.item = 0; cur.c.cb = 0;
+        int hb = 0;                                                 // halo buffer of the step the MFMA waves run
+        Step s1 = cur; bool has1 = advance(s1);                     // step s+1 (= cur on the last step: staged, never read)
+        Step s2 = s1;  bool has2 = has1 && advance(s2);
+        unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
+        for (int c = pt; c < 32; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
+        // prologue: first tile + first weight group in the open, loads of the second tile in flight
+        load_b_group(0, ic<0>{});
+        load_affine(cur.w, 0);
+        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        NM_PRODUCER8_WAIT(0);
+        store_b_group(ic<0>{});
+        static_for<NP>([&](auto K) { convert(0, m_cvt, K); });
+        m_cvt = inside_mask(s1.w);
+        load_affine(s1.w, s1.c.cb);
+        { const float* b = tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        lds_barrier();
+        for (;;) {
+            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = inside_mask(s2.w);
+            else m_ld = m_cvt;
+            const float* b2 = tile_base(s2.w, s2.c.cb);
+            // One stage per tap group g: fetch the weights of the group after it (this step's g + 1, or the next step's group 0) into
+            // the buffer group g - 1 was read from, convert this stage's pieces of the tile of step s + 1 and refill their registers
+            // with the loads for step s + 2, store the weights, meet the MFMA waves at the group's barrier.  The tile of step s + 1 is
+            // complete at the step's LAST barrier (conv_f16p2's deal: the MFMA waves fetch a step's first operands after it).
+            static_for<pl::kGroups>([&](auto G) {
+                constexpr int g = decltype(G)::value, gn = (g + 1) % pl::kGroups;
+                constexpr int k0 = pl::piece_first(g), nk = pl::piece_first(g + 1) - k0;
+                constexpr bool last = g == pl::kGroups - 1;
+                if constexpr (last) load_b_group(s1.c.cb, ic<gn>{}); else load_b_group(cur.c.cb, ic<gn>{});
+                if constexpr (g == 0) { NM_PRODUCER8_WAIT(4); }     // everything older than the NW weight loads: the tile of step s + 1, its affine
+                static_for<nk>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + k0>{}); load_piece(b2, m_ld, ic<decltype(K)::value + k0>{}); });
+                if constexpr (last) load_affine(s2.w, s2.c.cb);     // (sc / sh are free: piece 15 was their last user)
+                // the weight loads: nk piece loads (+ 2 affine loads) are younger
+                static_assert((nk == 4 && !last) || (nk == 5 && !last) || (nk == 2 && last), "the counted waits below are written for this deal");
+                if constexpr (nk == 5) { NM_PRODUCER8_WAIT(5); } else { NM_PRODUCER8_WAIT(4); }
+                store_b_group(ic<gn>{});
+                lds_barrier();                                      // group end (pl::group_end in the MFMA waves)
+            });
+            if (pl::brick_end(cur.c.cb, C16)) lds_barrier();        // the MFMA waves' epilogue barrier of a finished brick
+            if (!has1) break;
+            cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
+            m_cvt = m_ld; hb ^= 1;
+        }
+        NM_PRODUCER8_WAIT(0);                                       // loads still in flight for a step that does not exist
+        return;
+    }
+
+    // =============================== MFMA waves ===============================================================
+    __builtin_amdgcn_s_setprio(3);
+    // MFMA rows of this wave: tile m = 2 zh + my is the 8(x) x 4(z) slab of brick row y = 2 wave + my in z half zh
+    int arow0;
+    {
+        const int c = l31 >> 2;
+        const int x = (((0x96 >> c) & 1) << 2) + (l31 & 3), z = c >> 1;
+        arow0 = z * ZP + (2 * wave) * HX + x;
+    }
+    const int vx = ((((0x96 >> (l31 >> 2)) & 1) << 2) + (l31 & 3)), vz = l31 >> 3;
+    f32x16 acc[4], accl[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[m][r] = 0.f; accl[m][r] = 0.f; }
+
+    Step cur; cur.w = decode(id_first); cur.c.item = 0; cur.c.cb = 0;
+    int hb = 0;
+    lds_barrier();                                                  // the producers' prologue
+
+    constexpr int LO = 2 * HV * 16;                                 // hi -> lo plane of a halo tile, bytes
+    constexpr int YO = HX * 16;                                     // brick row 2 wave -> 2 wave + 1
+    constexpr int ZO = 4 * ZP * 16;                                 // z half 0 -> 1
+    const unsigned vb = (unsigned)(size_t)(ldb + h * 32 + l31);     // weight buffer 0: plane h (hi), channel l31
+    half8 ah0[2], ah1[2], ah2[2], ah3[2], al0[2], al1[2], al2[2], al3[2], bh[2], bl[2];        // operands, double buffered (index = tap & 1)
+    {
+        const unsigned va = (unsigned)(size_t)(ldh + h * HV + arow0);
+        ah0[0] = lds_read16_untracked<0>(va); ah1[0] = lds_read16_untracked<YO>(va);
+        ah2[0] = lds_read16_untracked<ZO>(va); ah3[0] = lds_read16_untracked<ZO + YO>(va);
+        al0[0] = lds_read16_untracked<LO>(va); al1[0] = lds_read16_untracked<LO + YO>(va);
+        al2[0] = lds_read16_untracked<LO + ZO>(va); al3[0] = lds_read16_untracked<LO + ZO + YO>(va);
+    }
+    const int nbr4 = nbx * nby * (p.OD >> 2);                       // GroupNorm partial rows per frame: one per 4 x 8 x 8 brick
+    for (;;) {
+        Step nxt = cur;
+        const bool has_next = advance(nxt);
+        const unsigned va = (unsigned)(size_t)(ldh + hb * 4 * HV + h * HV + arow0);          // this step's halo tile
+        const unsigned van = (unsigned)(size_t)(ldh + (hb ^ 1) * 4 * HV + h * HV + arow0);   // the next step's
+        static_for<pl::kTaps>([&](auto TT) {
+            constexpr int tt = decltype(TT)::value, g = pl::group_of(tt), t = pl::tap_in_group(tt), i = tt & 1, j = i ^ 1;
+            constexpr int BT = ((g & 1) * GB + t * 128) * 16;       // byte offset of this tap's weights
+            if constexpr (t == 0) {                                 // first tap of a group: its weights were published by the barrier
+                bh[i] = lds_read16_untracked<BT>(vb); bl[i] = lds_read16_untracked<BT + 64 * 16>(vb);
+            }
+            // every operand of this tap has been requested (previous tap / just above): wait for all of them
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(ah0[i]), "+v"(ah1[i]), "+v"(ah2[i]), "+v"(ah3[i]), "+v"(al0[i]), "+v"(al1[i]), "+v"(al2[i]), "+v"(al3[i]),
+                           "+v"(bh[i]), "+v"(bl[i]) :: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            constexpr int u = tt + 1, uz = (u < pl::kTaps) ? u / 9 : 0, ut = (u < pl::kTaps) ? u % 9 : 0;
+            constexpr int AO = (uz * ZP + (ut / 3) * HX + (ut % 3)) * 16;           // A byte offset of tap tt + 1
+            constexpr bool anext = u < pl::kTaps;                   // (tap 26 requests nothing: the next tile is complete only at the step's last barrier)
+            constexpr bool bnext = !pl::group_end(tt);              // the next tap's weights are in this group's buffer
+            constexpr int BN = BT + 128 * 16;
+            // per accumulator the order is conv_f16p's: acc += bh ah; accl += bl ah, then accl += bh al
+            NM_MFMA2(acc[0], bh[i], ah0[i]);   if constexpr (bnext) bh[j] = lds_read16_untracked<BN>(vb);
+                                               if constexpr (anext) ah0[j] = lds_read16_untracked<AO>(va);
+            NM_MFMA2(acc[1], bh[i], ah1[i]);   if constexpr (bnext) bl[j] = lds_read16_untracked<BN + 64 * 16>(vb);
+                                               if constexpr (anext) ah1[j] = lds_read16_untracked<AO + YO>(va);
+            NM_MFMA2(acc[2], bh[i], ah2[i]);   if constexpr (anext) ah2[j] = lds_read16_untracked<AO + ZO>(va);
+            NM_MFMA2(acc[3], bh[i], ah3[i]);   if constexpr (anext) ah3[j] = lds_read16_untracked<AO + ZO + YO>(va);
+            NM_MFMA2(accl[0], bl[i], ah0[i]);  if constexpr (anext) al0[j] = lds_read16_untracked<AO + LO>(va);
+            NM_MFMA2(accl[1], bl[i], ah1[i]);  if constexpr (anext) al1[j] = lds_read16_untracked<AO + LO + YO>(va);
+            NM_MFMA2(accl[2], bl[i], ah2[i]);  if constexpr (anext) al2[j] = lds_read16_untracked<AO + LO + ZO>(va);
+            NM_MFMA2(accl[3], bl[i], ah3[i]);  if constexpr (anext) al3[j] = lds_read16_untracked<AO + LO + ZO + YO>(va);
+            NM_MFMA2(accl[0], bh[i], al0[i]);
+            NM_MFMA2(accl[1], bh[i], al1[i]);
+            NM_MFMA2(accl[2], bh[i], al2[i]);
+            NM_MFMA2(accl[3], bh[i], al3[i]);
+            if constexpr (pl::group_end(tt)) {
+                // tap-group end: the producers publish the next group's weights (and, at the last barrier, the next tile).  No lgkmcnt
+                // wait: every read these waves issued was waited for at this tap's start, and they write no LDS here.
+                asm volatile("s_barrier" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        });
+        // the next step's tile is complete since the step's last barrier: request its first tap's A operands now (slot 0; tap 26
+        // used slot 0 and is done with it; the step's first wait covers them)
+        static_assert(((pl::kTaps - 1) & 1) == 0, "tap 26 computes from slot 0, tap 0 of the next step reads into it");
+        if (has_next) {
+            ah0[0] = lds_read16_untracked<0>(van); ah1[0] = lds_read16_untracked<YO>(van);
+            ah2[0] = lds_read16_untracked<ZO>(van); ah3[0] = lds_read16_untracked<ZO + YO>(van);
+            al0[0] = lds_read16_untracked<LO>(van); al1[0] = lds_read16_untracked<LO + YO>(van);
+            al2[0] = lds_read16_untracked<LO + ZO>(van); al3[0] = lds_read16_untracked<LO + ZO + YO>(van);
+        }
+        if (pl::brick_end(cur.c.cb, C16)) {
+            // ---- epilogue of the finished brick (exposed): transposed accumulators -> 16-byte stores, DPP partial sums; one z half
+            // (= one 4 x 8 x 8 brick of conv_f16p: tiles 2 zh, 2 zh + 1) after the other
+            const Work& w = cur.w;
+#pragma unroll
+            for (int zh = 0; zh < 2; ++zh) {
+                float s1[16], s2[16];
+#pragma unroll
+                for (int my = 0; my < 2; ++my) {
+                    const int m = 2 * zh + my;
+                    const size_t dst = ((((size_t)w.n * p.OD + w.oz0 + 4 * zh + vz) * p.OH + w.oy0 + 2 * wave + my) * p.OW + w.ox0 + vx) * (size_t)32 + 4 * h;
+#pragma unroll
+                    for (int k4 = 0; k4 < 4; ++k4) {
+                        const f32x4 b4 = *reinterpret_cast<const f32x4*>(lbias + 8 * k4 + 4 * h);
+                        f32x4 v;
+#pragma unroll
+                        for (int e = 0; e < 4; e += 2) {
+                            const f32x2 a2 = f32x2{acc[m][4 * k4 + e], acc[m][4 * k4 + e + 1]};
+                            const f32x2 l2 = f32x2{accl[m][4 * k4 + e], accl[m][4 * k4 + e + 1]};
+                            const f32x2 v2 = (a2 + l2 * (1.0f / NM_SPLIT_SCALE)) + f32x2{b4[e], b4[e + 1]};
+                            const f32x2 q2 = v2 * v2;
+                            v[e] = v2[0]; v[e + 1] = v2[1];
+                            // conv_f16p's sums: (tile 0 + tile 1), (tile 0 ^2 + tile 1 ^2)
+                            if (my == 0) { s1[4 * k4 + e] = v2[0]; s1[4 * k4 + e + 1] = v2[1]; s2[4 * k4 + e] = q2[0]; s2[4 * k4 + e + 1] = q2[1]; }
+                            else {
+                                const f32x2 t1 = f32x2{s1[4 * k4 + e], s1[4 * k4 + e + 1]} + v2, t2 = f32x2{s2[4 * k4 + e], s2[4 * k4 + e + 1]} + q2;
+                                s1[4 * k4 + e] = t1[0]; s1[4 * k4 + e + 1] = t1[1]; s2[4 * k4 + e] = t2[0]; s2[4 * k4 + e + 1] = t2[1];
+                            }
+                            acc[m][4 * k4 + e] = 0.f; acc[m][4 * k4 + e + 1] = 0.f; accl[m][4 * k4 + e] = 0.f; accl[m][4 * k4 + e + 1] = 0.f;
+                        }
+                        *reinterpret_cast<f32x4*>(p.out + dst + 8 * k4) = v;
+                    }
+                }
+                if (p.part) {
+                    dpp_sum32_many(s1); dpp_sum32_many(s2);
+                    if (l31 == 16) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            *reinterpret_cast<f32x2*>(red + ((zh * 4 + wave) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 2) = f32x2{s1[r], s2[r]};
+                    }
+                }
+            }
+            lds_barrier();                                          // brick end (matched by the producers)
+            if (p.part && tid < 64) {                               // the four wave partials in order 0 ... 3, one row per z half
+                const int zh = tid >> 5, c = tid & 31;
+                float a = 0.f, b = 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { a += red[((zh * 4 + q) * 32 + c) * 2]; b += red[((zh * 4 + q) * 32 + c) * 2 + 1]; }
+                const int br = (((w.oz0 >> 2) + zh) * nby + (w.oy0 >> 3)) * nbx + (w.ox0 >> 3);
+                float* dp = p.part + (((size_t)w.n * nbr4 + br) * 32 + c) * 2;
+                dp[0] = a; dp[1] = b;
+            }
+        }
+        if (!has_next) break;
+        cur = nxt; hb ^= 1;
+    }
+}
+
 // ---- conv_f16q2: the one-product form (conv modes 3 / 4) of conv_f16p2, re-balanced (round 5) ---------------------------------------
 // conv_f16p2's schedule with two thirds of the MFMAs deleted (its one-product instantiation, retired: DESIGN_HISTORY.md) did not fit
 // these modes: a tap group is 36 MFMAs per wave (1 152 cycles) instead of 108, but the producers still fetched each group's weights
@@ -3403,13 +3768,14 @@ int launch_pool_f16s(const ConvParams& p, dim3 grid, hipStream_t s) {
     return nm_ls().single ? launch_pool_f16s_impl<NT, true>(p, grid, s) : launch_pool_f16s_impl<NT, false>(p, grid, s);
 }
 
-// The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks, 512 threads): one
+// The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks; conv_f16p8 on
+// 8 x 8 x 8 bricks, BRICK_Z = 8: its work items and its super-tile count bricks of that depth; 512 threads): one
 // workgroup per CU, the bricks in XCD super-tile order where a brick is one work item.  wgs_cap > 0 is the cap of THIS launch (nm_launch_conv's argument: a conv that runs
 // beside another stream's chain of small dependent launches leaves it CUs), rounded down to a multiple of 8 so that every XCD keeps
 // the same number of workgroups; a workgroup walks a contiguous run of ceil(items / grid) work items, whatever the grid.  The XCD
 // super-tile exists for grids of 256 and 512 only (choose_super_tile: grid / 8 = 32 or 64), so a capped launch walks its bricks in
 // linear order - part of what the cap costs the capped conv itself.
-template <auto KERNEL>
+template <auto KERNEL, int BRICK_Z = 4>                             // BRICK_Z: z extent of the kernel's brick (conv_f16p8: 8)
 int launch_persistent(const char* what_attr, const char* what_launch, int variant, bool super_tile, const ConvParams& p_in,
                       size_t lds_bytes, int work_items, hipStream_t s, int wgs_cap) {
     static NmDeviceOnce attr_set;
@@ -3419,7 +3785,7 @@ int launch_persistent(const char* what_attr, const char* what_launch, int varian
     ConvParams p = p_in;
     const int wgs = wgs_cap > 0 && wgs_cap < cus ? min(cus, max(8, wgs_cap & ~7)) : cus;
     dim3 grid((unsigned)min(work_items, wgs));
-    if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / 4, p.OH / 8, p.OW / 8);
+    if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / BRICK_Z, p.OH / 8, p.OW / 8);
     NmProfScope prof(s, conv_flops(p, 27.0), variant);
     hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds_bytes, s, p);
     return nm_check_hip(hipGetLastError(), what_launch);
@@ -3437,6 +3803,12 @@ int launch_f16p(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap)
         return launch_f16p_impl<true, 3>(p, work_items, s, wgs_cap);
     }
     return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s, wgs_cap) : launch_f16p_impl<false>(p, work_items, s, wgs_cap);
+}
+
+// the 32-output-channel layers on 8 x 8 x 8 bricks (conv_f16p8_kernel); the caller has checked three products, fp32 storage, OD % 8 == 0.
+// Profiler variant 7: the kernel files under the conv_f16p family (all 16 variant slots are taken).
+int launch_f16p8(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
+    return launch_persistent<&conv_f16p8_kernel, 8>("hipFuncSetAttribute(conv_f16p8)", "conv_f16p8 launch", 7, true, p, (size_t)nm_f16p8::kLdsBytes, work_items, s, wgs_cap);
 }
 
 int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
@@ -3681,7 +4053,10 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
         p.w = static_cast<const float*>(w_packed16);
         return t.NT == 2 ? launch_pool_f16s<2>(p, grid, s) : launch_pool_f16s<1>(p, grid, s);
     }
-    // the persistent producer / consumer kernels take k3 s1 p1 layers of whole 4 x 8 x 8 bricks, at least four of them along z
+    // the persistent producer / consumer kernels take k3 s1 p1 layers of whole 4 x 8 x 8 bricks, at least four of them along z.
+    // Routing, in this order: Cout % 64 == 0 -> conv_f16p2 (one-product modes: conv_f16q2); Cout == 32 in the one-product modes ->
+    // conv_f16r; Cout == 32 with three products, fp32 storage and OD % 8 == 0 -> conv_f16p8 (8 x 8 x 8 bricks); what is left of
+    // Cout == 32 (OD % 8 == 4, bfloat16 storage, conv_f16r switched off) and conv mode 2's Cout % 32 == 0 -> conv_f16p
     const bool k3_bricks = w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
                            g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16;
     // (conv_f16q2 keeps a whole step's weights in LDS: a one-product call with more than 1024 output channels - no layer has more
@@ -3698,6 +4073,13 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
         p.w = static_cast<const float*>(w_packed16);
         if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s, wgs_cap) : launch_f16r_impl<0, 2>(p, work, s, wgs_cap);
         return p.in_h ? launch_f16r_impl<3, 4>(p, work, s, wgs_cap) : launch_f16r_impl<0, 4>(p, work, s, wgs_cap);
+    }
+    // three products, fp32 in and out, exactly 32 output channels, whole 8 x 8 x 8 bricks: conv_f16p8 (twice the MFMAs per staged step;
+    // bit-identical to conv_f16p, which keeps OD % 8 == 4, the one-product / bfloat16 forms and conv mode 2's several cout groups)
+    if (nm_ls().conv_mode == 1 && !nm_ls().single && k3_bricks && g.Cout == 32 && g.OD % 8 == 0 && !p.in_h && !p.out_h) {
+        const int work = in.N * (g.OD / 8) * (g.OH / 8) * (g.OW / 8);
+        p.w = static_cast<const float*>(w_packed16);
+        return launch_f16p8(p, work, s, wgs_cap);
     }
     // (with more cout groups per brick conv_f16p re-stages the input per group and measures a little slower than conv_f16s: only
     // conv mode 2, the parity tests of that path, sends every eligible layer here)
