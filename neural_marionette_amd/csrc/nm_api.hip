@@ -42,7 +42,15 @@ NmLaunchState::NmLaunchState()
       , up2y_ypad(env_int("NM355_UP2Y_YPAD", 1))            // 0: conv_up2y_kernel ignores the fine conv's zero padding along y and the shell kernels correct the y faces too (A/B)
       , up2c_shell(env_int("NM355_UP2C_SHELL", 1))          // the shell of the fused-upsample layers (split-fp16 mode, fp32 storage): 0: one line per face workgroup (A/B); 1: R lines per face workgroup (conv_up2c_face_r_kernel); 2: that and the edge items of the two-half layer with their loads in a ring (conv_up2c_edge_p_kernel: not the default, it does not clear the bar on the step); 3: the edge form alone; + 20 / 40: R = 2 / 4 at every layer (nm_up2c.hip)
       // Encoder schedule of the inference forward (nm_net.hip hourglass(); profiles/encoder_schedule_ab.txt)
-      , enc_sched(env_int("NM355_ENC_SCHED", 1))            // 0: the serial schedule - every launch of the per-frame net on the main stream (A/B, the tests' reference)
+      // 0: the serial schedule - every launch of the inference forward on the main stream or where the training forward has it (A/B).
+      // Any other value: the per-frame net's encoder schedule, refined by NM355_ENC_S1 / NM355_ENC_S1_WGS below (as before the decoder's
+      // bits existed; the value 1 is that schedule alone and the reference of the decoder's tests).  On top of it, bit 2: the edge kernel
+      // of the two fused-upsample layers of the decoder on the third stream beside their face kernel (nm_up2c.hip nm_launch_conv_up2c);
+      // bit 4: clip_loss_kernel on the third stream beside the decoder (nm_net.hip detector_graph; profiles/decoder_schedule_ab.txt).
+      // The decoder's bits live in this switch, not in one of their own: the set of switches is pinned
+      // (tests/test_switch_inventory_cpu.py).  The training forward and backward, and a context without a third stream of its own,
+      // keep the serial order.
+      , enc_sched(env_int("NM355_ENC_SCHED", 7))
       , enc_s1(env_int("NM355_ENC_S1", 1))                  // 0: the hourglass skip branch s1 stays in front of the interior's launch chain instead of running beside it on the third stream (A/B)
       , enc_s1_wgs(env_int("NM355_ENC_S1_WGS", -1))         // workgroup cap of s1's persistent convs while they run beside the chain: -1 (default) CUs - 2 x frames, at least half the CUs (128 at 64 frames, 224 at 16; nm_net.hip hourglass()); > 0: this value, rounded down to a multiple of 8; 0: none
 { store16_min = env_int("NM355_STORE16_MIN", 32768); chain_spin = env_int("NM355_CHAIN_SPIN", 1 << 20); chain_backoff = env_int("NM355_CHAIN_BACKOFF", 0); chain_drop = env_int("NM355_CHAIN_DROP_WG", 0); chain_stat_delay = env_int("NM355_CHAIN_STAT_DELAY", 0);
@@ -198,6 +206,10 @@ int nm_ctx_create(nm_ctx** out, const nm_config* cfg) try {
         hipEventCreateWithFlags(&c->ev_side, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_s1_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_s1_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_shell_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_shell_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_loss_fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_loss_join, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_nf[2], hipEventDisableTiming) != hipSuccess ||
@@ -230,7 +242,7 @@ int nm_ctx_destroy(nm_ctx* ctx) try {
     nm_vrnn_free_tape(ctx);
     if (ctx->stream2 || ctx->stream3) release_side_streams(ctx->cfg.device, ctx->stream2, ctx->stream3, ctx->side_shared);
     if (ctx->wside) (void)hipFree(ctx->wside);
-    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_s1_fork, ctx->ev_s1_join, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_clip, ctx->ev_kp, ctx->ev_side, ctx->ev_s1_fork, ctx->ev_s1_join, ctx->ev_shell_fork, ctx->ev_shell_join, ctx->ev_loss_fork, ctx->ev_loss_join, ctx->ev_w[0], ctx->ev_w[1], ctx->ev_w[2], ctx->ev_dy, ctx->ev_wjoin}) if (e) (void)hipEventDestroy(e);
     for (const NmProfRec& r : ctx->ls.prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (hipEvent_t e : ctx->ls.event_pool) (void)hipEventDestroy(e);
     delete ctx;
@@ -324,7 +336,8 @@ int nm_prof_enable(nm_ctx* ctx, int32_t on) try { NmScope nm_scope_(ctx);
 } catch (...) { return nm_abi_catch("nm_prof_enable"); }
 
 int nm_prof_read(nm_ctx* ctx, int32_t variant, double* ms_total, double* flops_total, int64_t* launches) try { NmScope nm_scope_(ctx);
-    if (!ctx || !ms_total || !flops_total || !launches || variant < 0 || variant > 15) { nm_set_error("prof_read: bad argument"); return NM_ERR_ARG; }
+    if (!ctx || !ms_total || !flops_total || !launches || variant < 0 || variant > 16) { nm_set_error("prof_read: bad argument"); return NM_ERR_ARG; }
+    if (variant == 16) { *ms_total = 0.0; *flops_total = 0.0; *launches = ctx->ls.side_launches; return NM_OK; }       // a count, not a timed family
     long long n = 0;
     int rc = nm_conv_prof_collect(variant, ms_total, flops_total, &n);
     if (rc) { nm_set_error("prof_read: event query failed"); return rc; }
@@ -337,7 +350,7 @@ const char* nm_prof_kernel_name(int32_t variant) {
                                    "conv_k5occ_kernel", "conv_f16s_kernel<2,1>", "conv_f16s_kernel<2,2>", "conv_f16p_kernel",
                                    "conv_pool_f16s_kernel", "conv_f16p2_kernel", "conv_f16s_kernel<2,1,3,up2>", "conv_f16s_kernel<2,2,3,up2>",
                                    "conv_up2c_kernel", "wgrad16_kernel", "conv_f16q2_kernel", "conv_f16r_kernel"};
-    return (variant >= 0 && variant < 16) ? names[variant] : "";
+    return (variant >= 0 && variant < 16) ? names[variant] : variant == 16 ? "third-stream launches of the decoder schedule" : "";
 }
 
 int nm_host_linspace(int32_t n, float* out) try {

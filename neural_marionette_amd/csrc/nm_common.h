@@ -197,6 +197,12 @@ struct NmLaunchState {
     unsigned* nf_flag = nullptr;           // sticky device word gn_finalize ORs a 1 into (null: no reporting)
     // A/B and diagnostic switches: NM355_<NAME IN CAPITALS>, each described at its initialiser (nm_api.hip)
     int pool_q, occ_flags, gnb_apply4, defer_sums, wgrad_async, wgrad_tr, tail_rank1, vrnn_mid, vrnn_gemm, vrnn_graph, sparse_first, gn_diag, lazy_res, hg_core, vrnn_chain, vrnn_post_chain, f16r, up2_mat, up2y, up2y_march, up2y_ypad, up2c_shell, enc_sched, enc_s1, enc_s1_wgs;
+    // side lane of the fused-upsample layers' shell (NM355_ENC_SCHED bit 2): while set, nm_launch_conv_up2c launches its edge kernel on
+    // this stream beside the face kernel and joins it before it returns.  Set by decode_frames (nm_net.hip) around the decoder's two
+    // up layers of the inference forward, null everywhere else: every other caller keeps the serial order.
+    hipStream_t shell_lane = nullptr;
+    hipEvent_t shell_fork = nullptr, shell_join = nullptr;
+    long long side_launches = 0;           // launches the decoder schedule sent to the third stream while the profiler was on (nm_prof_read variant 16)
     NmLaunchState();
 };
 NmLaunchState& nm_ls();        // the state of the context whose ABI call runs on this thread

@@ -3988,6 +3988,7 @@ void nm_conv_prof_reset() {
     NmLaunchState& l = nm_ls();
     for (const NmProfRec& r : l.prof) { l.event_pool.push_back(r.a); l.event_pool.push_back(r.b); }
     l.prof.clear();
+    l.side_launches = 0;
 }
 
 int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias, float* out,

@@ -95,6 +95,10 @@ struct nm_ctx {
     // inference forward: the per-frame net's hourglass skip branch s1 runs on stream3 beside the interior's launch chain (nm_net.hip
     // hourglass()): fork (main stream -> stream3) and join (stream3 -> main stream), once per encoder chunk
     hipEvent_t ev_s1_fork = nullptr, ev_s1_join = nullptr;
+    // inference forward, decoder (NM355_ENC_SCHED bits 2 and 4; nm_net.hip decode_frames / detector_graph): the fused-upsample layers' edge kernel on
+    // stream3 beside their face kernel (fork / join inside nm_launch_conv_up2c, once per up layer and decoder pass), and clip_loss_kernel
+    // on stream3 beside the decoder (fork behind the affinity launch, join in front of loss_finalize)
+    hipEvent_t ev_shell_fork = nullptr, ev_shell_join = nullptr, ev_loss_fork = nullptr, ev_loss_join = nullptr;
     // weight gradients of the training backward on a stream of their own (nm_net.hip conv_bwd): their inputs that must outlive the main
     // stream's arena frames (a ring of dY buffers, the re-materialised upsample + slot workspace, the operand-scale vectors) live in one
     // ctx-owned block sized by the sizing pass of nm_detector_forward_train

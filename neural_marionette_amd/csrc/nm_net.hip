@@ -660,9 +660,23 @@ void decode_frames(Net& n, const float* keypoints, const float* feat_cl, int fea
             x = mk(comb, nf, g, g, g, Cc);
             x = conv_gn(n, x, d.adjust, nullptr, 1, 0, LRELU, nullptr, false, tape ? &tape->adjust : nullptr);
         }
-        x = conv_gn(n, x, d.d1, &d.dn2, 1, 1, LRELU, nullptr, true, tape ? &tape->d1 : nullptr);    // Upsample(x2, trilinear) fused into the staging
+        // inference (NM355_ENC_SCHED bit 2): the two up layers launch their shell's edge kernel on stream3 beside the face kernel
+        // (nm_launch_conv_up2c forks behind its main launch and joins before it returns); stream3 is idle here - the encoder's skip
+        // branch was joined long before, the weight gradients are the training step's
+        NmLaunchState& ls = nm_ls();
+        const bool shell_side = !tape && (ls.enc_sched & 2) && c->stream3 && c->stream3 != n.s;
+        struct ShellLane {      // the lane is set for one conv_gn and cleared on every way out of it
+            NmLaunchState& l;
+            ShellLane(NmLaunchState& st, bool on, nm_ctx* cx) : l(st) { if (on) { l.shell_lane = cx->stream3; l.shell_fork = cx->ev_shell_fork; l.shell_join = cx->ev_shell_join; } }
+            ~ShellLane() { l.shell_lane = nullptr; l.shell_fork = l.shell_join = nullptr; }
+        };
+        auto up_layer = [&](const ConvW& w, const NormW& gn, ConvRec* rec) {
+            ShellLane lane(ls, shell_side, c);
+            x = conv_gn(n, x, w, &gn, 1, 1, LRELU, nullptr, true, rec);
+        };
+        up_layer(d.d1, d.dn2, tape ? &tape->d1 : nullptr);                                          // Upsample(x2, trilinear) fused into the staging
         x = conv_gn(n, x, d.d4, &d.dn5, 1, 1, LRELU, nullptr, false, tape ? &tape->d4 : nullptr);
-        x = conv_gn(n, x, d.d8, &d.dn9, 1, 1, LRELU, nullptr, true, tape ? &tape->d8 : nullptr);    // second Upsample(x2) likewise
+        up_layer(d.d8, d.dn9, tape ? &tape->d8 : nullptr);                                          // second Upsample(x2) likewise
         x = conv_gn(n, x, d.d11, &d.dn12, 1, 1, LRELU, nullptr, false, tape ? &tape->d11 : nullptr);
         if (n.live())
             n.run(nm_launch_decoder_tail(x, d.d14, first_frames + (size_t)b0 * ff_stride * G3, ff_stride, T,
@@ -771,6 +785,21 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
         n.run(nm_launch_cl_to_ncdhw_strided(ff, T, first_feature, n.s));
         if (affinity_on) n.run(nm_launch_affinity(d.affinity_params, N, K, aff, n.s, c->affinity_ver));
     }
+    // inference (NM355_ENC_SCHED bit 4): clip_loss_kernel - one workgroup per clip, reads the keypoints and the affinity only - goes to
+    // stream3 here, where its inputs exist, and runs beside the voxel decoder instead of behind it; joined in front of loss_finalize.
+    // clip_part and aff were allocated before every frame mark of this call and nothing below releases them, so nothing the main
+    // stream allocates meanwhile aliases what the kernel touches.  (nm_launch_volfit_gauss, vol_fit_type 'gaussian', is not moved: its
+    // workspace is allocated behind the decoder's, and it stays in front of loss_finalize on the main stream.)
+    const bool loss_side = !tape && recon && losses && (nm_ls().enc_sched & 4) && c->stream3 && c->stream3 != n.s;
+    bool loss_forked = false;
+    if (loss_side && n.live()) {
+        loss_forked = true;
+        n.run(nm_check_hip(hipEventRecord(c->ev_loss_fork, n.s), "clip loss fork event"));
+        n.run(nm_check_hip(hipStreamWaitEvent(c->stream3, c->ev_loss_fork, 0), "clip loss stream wait"));
+        if (n.ok()) n.run(nm_launch_clip_loss(keypoints, aff, B, T, K, N, c->cfg.sep_sigma, clip_part, c->stream3, c->graph_loss_ver));
+        if (nm_ls().prof_on) ++nm_ls().side_launches;
+        n.run(nm_check_hip(hipEventRecord(c->ev_loss_join, c->stream3), "clip loss join event"));
+    }
     // (recon == nullptr: the keypoints-only pass of nm_detector_keypoints - no voxel decoder, no losses)
     if (recon) decode_frames(n, keypoints, feat, T, vox_in, T, B, T, vox_in, c->cfg.vol_fit_chamfer == 1, recon, tail_part, tape, c->learn_sigma != 0);
     if (tape) {
@@ -778,10 +807,12 @@ int detector_graph(nm_ctx* c, const float* vox_in, int B, int T, int affinity_on
         tape->heat_part = heat_part; tape->heat_mean = heat_mean; tape->tail_part = tail_part; tape->aff = aff;
         tape->keypoints = keypoints; tape->recon = recon;
     }
+    // (joined whatever became of the decoder: stream3 never stays ahead of a call that has returned)
+    if (loss_forked) n.run(nm_check_hip(hipStreamWaitEvent(n.s, c->ev_loss_join, 0), "join the clip loss"));
     float* vol_fs = nullptr; float* vol_ws = nullptr;               // vol_fit_type 'gaussian' (cfg.vol_fit_chamfer == 2): its own per-frame sums
     if (recon && losses && c->cfg.vol_fit_chamfer == 2) { vol_fs = n.alloc((size_t)F * 2); vol_ws = n.alloc(nm_volfit_gauss_ws_floats(F, G)); }
     if (n.live() && recon && losses) {
-        n.run(nm_launch_clip_loss(keypoints, aff, B, T, K, N, c->cfg.sep_sigma, clip_part, n.s, c->graph_loss_ver));
+        if (!loss_forked) n.run(nm_launch_clip_loss(keypoints, aff, B, T, K, N, c->cfg.sep_sigma, clip_part, n.s, c->graph_loss_ver));
         if (vol_fs) n.run(nm_launch_volfit_gauss(vox_in, keypoints, B, T, K, G, c->cfg.gaussian_sigma, vol_ws, vol_fs, n.s));
         n.run(nm_launch_loss_finalize(tail_part, tb, B, T, K, N, G, heat_mean, clip_part, aff, c->cfg.vol_fit_chamfer,
                                       c->cfg.use_graph_traj, frame_sums, losses, n.s, vol_fs, c->graph_flags));

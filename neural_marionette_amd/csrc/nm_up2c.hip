@@ -1625,6 +1625,17 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     launch_io(main_split, MAIN_ONE, single, io, dim3((unsigned)min(p.march ? columns : total, cus)), 512, LDS_BYTES, s, p);
     int rc = nm_check_hip(hipGetLastError(), "conv_up2c launch");
     if (rc) return rc;
+    // NM355_ENC_SCHED bit 2 (the lane is set by decode_frames only, nm_net.hip): the edge launch goes to the lane, behind the main
+    // launch and BESIDE the face launch, and is joined before this function returns - the caller's profiler bracket and the
+    // gn_finalize that follows see the whole layer.  The two launches are independent in every instantiation ("shell kernels" above:
+    // each reads the main kernel's output at the cells it owns and nowhere else, stores one float per lane and owned row, and the
+    // partial slots are disjoint - face items and the zeroed y-face slots below 8 bricks + 4 fg, edge items from there).
+    NmLaunchState& ls = nm_ls();
+    const hipStream_t se = (ls.shell_lane && ls.shell_lane != s && ls.shell_fork && ls.shell_join) ? ls.shell_lane : s;
+    if (se != s) {
+        if ((rc = nm_check_hip(hipEventRecord(ls.shell_fork, s), "conv_up2c: shell fork event"))) return rc;
+        if ((rc = nm_check_hip(hipStreamWaitEvent(se, ls.shell_fork, 0), "conv_up2c: shell lane wait"))) return rc;
+    }
     int TZ, TY, TX; shell_tiles(in.D, in.H, in.W, TZ, TY, TX);
     const int fg = face_groups(in.D, in.H, in.W), ei = edge_items(in.D, in.H, in.W);
     const size_t face_lds = (size_t)(in.C / 16 * 4) * FPV * 16;
@@ -1643,11 +1654,19 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
     }
     else launch_io(conv_up2c_face_kernel<false>, FACE_ONE, single, io, dim3((unsigned)(p.N * fg)), 256, face_lds, s, p, TY, TX);
     rc = nm_check_hip(hipGetLastError(), "conv_up2c_face launch");
-    if (rc) return rc;
     const long long items = (long long)p.N * ei;
     // (one output half: the ring's registers leave one wave per SIMD, and 1.5 items per SIMD then run in two rounds - measured
     //  slower than conv_up2c_edge_kernel on the 64 -> 32 layer, which keeps it)
-    if (edge_p && Cout == 64) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    else launch_io(conv_up2c_edge_kernel<false>, EDGE_ONE, single, io, dim3((unsigned)((items + 3) / 4)), 256, 0, s, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-    return nm_check_hip(hipGetLastError(), "conv_up2c_edge launch");
+    if (!rc) {
+        if (edge_p && Cout == 64) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, se, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+        else launch_io(conv_up2c_edge_kernel<false>, EDGE_ONE, single, io, dim3((unsigned)((items + 3) / 4)), 256, 0, se, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+        rc = nm_check_hip(hipGetLastError(), "conv_up2c_edge launch");
+        if (!rc && se != s && ls.prof_on) ++ls.side_launches;
+    }
+    if (se != s) {      // (joined behind a failed face or edge launch too: once forked, the lane never stays ahead of s)
+        int rj = nm_check_hip(hipEventRecord(ls.shell_join, se), "conv_up2c: shell join event");
+        if (!rj) rj = nm_check_hip(hipStreamWaitEvent(s, ls.shell_join, 0), "conv_up2c: join the shell lane");
+        if (!rc) rc = rj;
+    }
+    return rc;
 }
