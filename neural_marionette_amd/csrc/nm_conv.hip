@@ -22,15 +22,15 @@
 //   sum / sum-of-squares partials for the following GroupNorm (deterministic: no float
 //   atomics).
 #include "nm_common.h"
+#include "nm_brick_walk.h"
 #include "nm_f16p8_plan.h"
+#include "nm_halo_stage.h"
 #include "nm_up2c.h"
 #include <type_traits>
 #include <utility>
 #include <vector>
 
 namespace {
-
-#define NM_SPLIT_SCALE 2048.0f   // lo parts of the split-fp16 operands are stored times 2^11
 
 struct ConvParams {
     const float* in; const float* in_scale; const float* in_shift; float in_slope;
@@ -49,9 +49,7 @@ struct ConvParams {
     int ZP;                       // f16s: pitch between halo z-planes in LDS (>= HY*HX, = 4 mod 16)
     const void* w16;              // conv_mfma_kernel<1,NT>: split-fp16 weights (null: fp32 MFMA core)
     int ksplit;                   // conv_mfma_kernel<1,NT> + w16: the taps are dealt to 2 / 4 waves that share a row tile (tiny volumes)
-    int st_z, st_y, st_x;         // f16s / f16p: XCD super-tile in bricks (0: bricks in linear order), see super_tile_item()
-    unsigned st_sx, st_sy, st_pf; // super-tiles per row / column / frame, and ceil(2^32 / d) of each (0: d = 1): the three divisions of a brick
-    unsigned st_m_sx, st_m_sy, st_m_pf;   // decode as multiplications (round 6); st_pf = 0: the host could not prove them exact, plain divisions
+    nm_walk::SuperTile st;        // f16s / f16p: XCD super-tile in bricks (x == 0: bricks in linear order), nm_brick_walk.h
     const float* in_alt; const unsigned char* in_map;   // brick-sparse input (TensorRef::alt / brickmap), conv_pool_f16s only
     const float* in2; const float* in2_scale; const float* in2_shift; float in2_slope;   // un-materialised residual sum (TensorRef::p2 ...), conv_pool_f16s only
     int in_h, out_h;              // 16-bit storage (conv mode 4): the input / output tensor is bfloat16 (kernels take it as the IO template bits 1 / 2)
@@ -128,10 +126,6 @@ __device__ __forceinline__ void up_idx(int o, int I, int& i0, int& i1, float& l1
     l1 = src - (float)i0;
 }
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // v = hi + lo * 2^-11 with hi = rne_f16(v), lo = rne_f16((v - hi) * 2^11).  v - hi is exact in fp32, so the lo part is
 // one v_fma_mix{lo,hi}_f16 of (hi, -2^11, v * 2^11): 2.5 VALU per value, none of them packed fp32 math.
@@ -948,41 +942,6 @@ int ceil_log2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 // 3 MFMAs per k-step instead of 1, at 16x the rate.  Activations are split while they are staged into LDS (planes
 // [hi|lo][lane half][halo voxel] of 8 halves = 16 B), weights are split once per weight update
 // ([tap][Cin/16][hi|lo][lane half][Co_pad][8 halves]).  Requires Cin % 16 == 0; other layers use the fp32 kernel.
-// Which brick a persistent workgroup processes in its iteration tau.  The eight XCDs have separate L2s and a brick's
-// 6x10x10 halo is 2.3x its 4x8x8 outputs, so in linear order (each workgroup a contiguous run of bricks, the 32 CUs of an
-// XCD far apart in the volume) the input is fetched from HBM about twice; conv 64^3 x 32 channels moved 8-10 GB per
-// launch for 4.3 GB of tensors.  Here the workgroups of one XCD (blockIdx % 8 is the XCD label) take, at the same time,
-// the st_z x st_y x st_x bricks of one super-tile (one brick per workgroup, 64 or 32 of them), and consecutive iterations
-// walk neighbouring super-tiles of the same frame, so halos shared between neighbouring bricks are served by that L2.
-struct BrickPos { int n, bz, by, bx; };
-__device__ __forceinline__ BrickPos super_tile_item(const ConvParams& p, int b, int tau, int per, int nbz, int nby, int nbx) {
-    BrickPos r;
-    if (p.st_x == 0) {
-        const int nbr = nbz * nby * nbx, item = b * per + tau;
-        r.n = item / nbr; const int br = item % nbr;
-        r.bx = br % nbx; r.by = (br / nbx) % nby; r.bz = br / (nbx * nby);
-        return r;
-    }
-    const int l = b >> 3, S = (b & 7) * per + tau;
-    if (p.st_pf) {
-        // (round 6) a persistent workgroup decodes every brick it walks - nine integer divisions by launch constants, ~250 vector
-        // instructions and a dozen hoisted reciprocal registers per wave, in the MFMA waves' path between two steps (in-kernel stamps of
-        // conv_f16p: 720 of a 9 800-tick step).  The super-tile is always 4 x 4 bricks in (y, x); the three real divisions are by host
-        // constants: q = umulhi(x, ceil(2^32 / d)), exact while x d < 2^32 (checked by choose_super_tile).
-        auto fdiv = [](unsigned x, unsigned m) { return m ? __umulhi(x, m) : x; };
-        const unsigned n = fdiv((unsigned)S, p.st_m_pf), si = (unsigned)S - n * p.st_pf;
-        const unsigned q = fdiv(si, p.st_m_sx), sx = si - q * p.st_sx;
-        const unsigned sz = fdiv(q, p.st_m_sy), sy = q - sz * p.st_sy;
-        r.n = (int)n; r.bx = (int)(sx * 4u) + (l & 3); r.by = (int)(sy * 4u) + ((l >> 2) & 3); r.bz = (int)sz * p.st_z + (l >> 4);
-        return r;
-    }
-    const int SX = nbx / p.st_x, SY = nby / p.st_y, stpf = SX * SY * (nbz / p.st_z);
-    r.n = S / stpf; const int si = S % stpf;
-    r.bx = (si % SX) * p.st_x + l % p.st_x;
-    r.by = ((si / SX) % SY) * p.st_y + (l / p.st_x) % p.st_y;
-    r.bz = (si / (SX * SY)) * p.st_z + l / (p.st_x * p.st_y);
-    return r;
-}
 
 // Brick = 4(z) x 8(y) x 8(x) output voxels, 256 GEMM rows.  Each 32-row MFMA tile is the 8(x) x 4(z) slab of one
 // brick row y: with the halo tile's plane pitch ZP = 4 (mod 16) slots, the four 16-lane groups of a ds_read_b128
@@ -1018,7 +977,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16s_kernel(ConvParams p) {
     const int per = (total_items + (int)gridDim.x - 1) / (int)gridDim.x;
     const int item_end = min(total_items, ((int)blockIdx.x + 1) * per);
     for (int item = (int)blockIdx.x * per; item < item_end; ++item) {
-    const BrickPos bp = super_tile_item(p, (int)blockIdx.x, item - (int)blockIdx.x * per, per, p.nbz, p.nby, p.nbx);
+    const nm_walk::BrickPos bp = nm_walk::super_tile_item(p.st, (int)blockIdx.x, item - (int)blockIdx.x * per, per, p.nbz, p.nby, p.nbx);
     const int n = bp.n, bxi = bp.bx, byi = bp.by, bzi = bp.bz;
     const int br = (bzi * p.nby + byi) * p.nbx + bxi;
     const int oz0 = bzi << 2, oy0 = byi << 3, ox0 = bxi << 3;
@@ -1487,15 +1446,6 @@ __global__ __launch_bounds__(256, 2) void conv_pool_f16s_kernel(ConvParams p) {
     epilogue_xz<2, NT>(e, red, acc, accl, n, br, nblk, oz0, oy0, ox0, co_base);
 }
 
-// 16-byte global load the compiler's wait-count tracking does not see.  hipcc waits vmcnt(0) at the first use of an
-// ordinary load result whenever an LDS-DMA is in flight, which would drain the weight pipeline of conv_f16p at the first
-// staging piece; the kernel instead waits explicitly (its group-end vmcnt(0)) before the results are used.
-__device__ __forceinline__ f32x4 load16_untracked(const float* q) {
-    f32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(q) : "memory");
-    return r;
-}
-
 // 16-byte LDS read the compiler's wait-count tracking does not see (byte address = base + OFF).  The pipelined tap stream of
 // conv_f16p keeps 12 reads in flight and waits with an exact s_waitcnt lgkmcnt(10) before each MFMA; with tracked reads hipcc
 // falls back to lgkmcnt(0) every second tap, which drains the read issued one instruction earlier.
@@ -1505,20 +1455,6 @@ __device__ __forceinline__ half8 lds_read16_untracked(unsigned base) {
     half8 r;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(base), "n"(OFF) : "memory");
     return r;
-}
-
-// 8-byte form (four bfloat16 channels of a 16-bit-storage tensor), same tracking rules
-__device__ __forceinline__ nm_u32x2 load8_untracked(const float* base, unsigned byte_off) {
-    nm_u32x2 r;
-    const char* q = reinterpret_cast<const char*>(base) + byte_off;
-    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(r) : "v"(q) : "memory");
-    return r;
-}
-
-// the same from a wave-uniform base and a 32-bit per-lane byte offset (one 64-bit VALU add; the scalar-base addressing form
-// needs the base in SGPRs, which the compiler does not guarantee for an inline-asm operand computed through VALU divisions)
-__device__ __forceinline__ f32x4 load16_untracked(const float* base, unsigned byte_off) {
-    return load16_untracked(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off));
 }
 
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{})
@@ -1727,6 +1663,34 @@ __global__ __launch_bounds__(256, 2) void conv_pool_f16q_kernel(ConvParams p) {
     epilogue_xz<2, NT, OH>(e, red, acc, accl, n, br, nblk, oz0, oy0, ox0, co_base);
 }
 
+// ---- the persistent producer / consumer kernels: conv_f16p, _f16p2, _f16p8, _f16q2, _f16r ------------------------------------------
+// What the five share lives in two headers: nm_brick_walk.h (which brick, cout group and channel chunk a workgroup takes in each step:
+// Work, Step, decode, advance; the MFMA waves and the producers walk the same stream) and nm_halo_stage.h (the producers' piece table,
+// inside mask, tile base and conversions).  Each kernel keeps its own schedule: the order of loads, converts, counted waits and barriers.
+// LDS layout of one of them, in this order: halo tiles and weights (16-byte slots), GroupNorm scratch (floats), the bias [Cout], TAIL
+// bytes.  The kernel's pointers and the launcher's byte count both come from here (conv_f16p8: nm_f16p8_plan.h).
+template <int HALO_SLOTS, int WEIGHT_SLOTS, int RED_FLOATS, int TAIL = 0>
+struct PcLds {
+    static constexpr int kHaloSlots = HALO_SLOTS, kWeightSlots = WEIGHT_SLOTS, kRedFloats = RED_FLOATS;
+    static constexpr size_t bytes(int Cout) { return (size_t)(HALO_SLOTS + WEIGHT_SLOTS) * 16 + (size_t)(RED_FLOATS + Cout) * sizeof(float) + TAIL; }
+};
+using F16pLds = PcLds<2 * 4 * 600, 3 * 9 * 4 * 32, 4 * 32 * 2>;     // halo [2][hi h0 | hi h1 | lo h0 | lo h1][600], weights [3][9 taps][4 planes][32], red [4 waves][32][2]
+using F16p2Lds = PcLds<2 * 4 * 600, 2 * 9 * 4 * 64, 4 * 64 * 2>;    // weights [2][9 taps][4 planes][64], red [4 waves][64][2]
+using F16q2Lds = PcLds<2 * 2 * 600, 2 * 27 * 2 * 64, 4 * 64 * 2>;   // halo [2][h0 | h1][600], weights [2][27 taps][h0 | h1][64]
+// conv_f16r's tail, behind the bias: the store slots of the MFMA-wave lanes that hold no total (nobody reads them).  A lane's slot is
+// kLane bytes at tid * kLane, a channel's totals go kChannels' worth of compile-time offsets further, and the parity of the brick moves
+// every store by kParity = one parity of `red`, so that one address register serves the real rows and the dummy slots alike.
+struct F16rTail { static constexpr int kLane = 8, kChannels = 256, kParity = 4 * 32 * 2 * (int)sizeof(float), kBytes = 256 * kLane + kChannels + kParity; };
+static_assert(((15 & 3) + 8 * (15 >> 2)) * 8 + 8 <= F16rTail::kChannels, "the largest channel offset of a totals store (register r = 15) stays inside the span");
+template <int C16T>                                                 // weights [27 taps][C16T][h0 | h1][32], red [2 brick parities][4 waves][32][2]
+using F16rLds = PcLds<2 * 2 * 600, 27 * C16T * 64, 2 * 4 * 32 * 2, F16rTail::kBytes>;
+static_assert(F16rTail::kParity * 2 == F16rLds<2>::kRedFloats * (int)sizeof(float) && F16rTail::kBytes == 2048 + 256 + 1024, "conv_f16r tail");
+// gfx950: 163 840 B of LDS per workgroup.  Cout is a launch parameter of the first three: 512 channels is more than any layer has
+static_assert(F16pLds::bytes(32) == 133248 && F16pLds::bytes(512) <= 160 * 1024, "conv_f16p LDS");
+static_assert(F16p2Lds::bytes(64) == 152832 && F16p2Lds::bytes(512) <= 160 * 1024, "conv_f16p2 LDS");
+static_assert(F16q2Lds::bytes(64) == 151296 && F16q2Lds::bytes(512) <= 160 * 1024, "conv_f16q2 LDS");
+static_assert(F16rLds<2>::bytes(32) == 99200 && F16rLds<4>::bytes(32) == 154496 && F16rLds<4>::bytes(32) <= 160 * 1024, "conv_f16r LDS");
+
 // ---- conv_f16p: k3 s1 p1 split-fp16 conv, one persistent workgroup per CU, MFMA waves + producer waves ---------------
 // conv_f16s runs two independent 4-wave workgroups per CU and leaves the matrix pipe ~50 % idle: staging, the epilogue
 // and the per-brick set-up of one workgroup overlap the other's MFMAs only by chance.  Here ONE workgroup owns the CU and
@@ -1742,9 +1706,9 @@ __global__ __launch_bounds__(256, 2) void conv_pool_f16q_kernel(ConvParams p) {
 //     group g), loaded through registers one group ahead of the barrier that publishes them.
 // Three barriers per step (tap-group ends).  Cout is processed 32 channels per step, the cout groups of a brick back to
 // back (its input stays in L2).
-//   LDS: halo [2 buffers][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [3][9 taps][4 planes][32] x 16 B, GroupNorm scratch.
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-
+//   LDS: halo [2 buffers][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [3][9 taps][4 planes][32] x 16 B, GroupNorm scratch (F16pLds).
+// Shared with the other four: the walk (nm_walk::Walk<4, true>) and the producers' pieces and split conversion, its IH and SINGLE arms
+// included (HaloPieces, nm_halo_stage.h).
 // IO: bit 0 = bfloat16 input (a producer piece is then an 8-byte load of the same four channels), bit 1 = bfloat16 output
 template <bool SINGLE = false, int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
@@ -1755,48 +1719,18 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
     constexpr int NP = 10;                                          // 16-byte input pieces per producer thread and step (2400 / 256)
     extern __shared__ f32x4 lds[];
     half8* ldh = reinterpret_cast<half8*>(lds);                     // [2][4][HV]
-    half8* ldb = ldh + 8 * HV;                                      // [3][GB]
-    float* red = reinterpret_cast<float*>(ldb + 3 * GB);            // [4 waves][32 channels][2]
-    float* lbias = red + 256;                                       // [Cout] bias (zeros without one), written once by the producers
+    half8* ldb = ldh + F16pLds::kHaloSlots;                         // [3][GB]
+    float* red = reinterpret_cast<float*>(ldb + F16pLds::kWeightSlots);   // [4 waves][32 channels][2]
+    float* lbias = red + F16pLds::kRedFloats;                       // [Cout] bias (zeros without one), written once by the producers
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
     const int C16 = p.Cin >> 4;
-    const int ncg = p.Cout >> 5;
-    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 2, nbr = nbx * nby * nbz;
-    const int total = p.N * nbr * ncg;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
-    if (id_first >= id_last) return;
-
-    struct Work { int n, oz0, oy0, ox0, cg; };
-    const bool tiled = p.st_x != 0;                                 // XCD super-tile order (one cout group only), see super_tile_item
-    auto decode = [&](int id) {
-        Work w;
-        if (tiled) {
-            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
-            w.cg = 0; w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 2;
-            return w;
-        }
-        w.cg = id % ncg; const int bid = id / ncg;
-        w.n = bid / nbr; const int br = bid % nbr;
-        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 2;
-        return w;
-    };
-    auto next_work = [&](Work w, int id) {                          // work item id from item id - 1 (linear order: no divisions)
-        if (tiled) return decode(id);
-        if (++w.cg == ncg) {
-            w.cg = 0;
-            if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 4) == p.OD) { w.oz0 = 0; ++w.n; } } }
-        }
-        return w;
-    };
-    struct Step { Work w; int id, cb; };
-    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
-        if (st.cb + 1 < C16) { ++st.cb; return true; }
-        if (st.id + 1 >= id_last) return false;
-        st.cb = 0; ++st.id; st.w = next_work(st.w, st.id);
-        return true;
-    };
+    using Walk = nm_walk::Walk<4, true>;                            // nm_brick_walk.h: the stream of steps (brick, cout group, 16-channel chunk) of this workgroup
+    using Work = typename Walk::Work;
+    using Step = typename Walk::Step;
+    const Walk walk(p.st, p.N, p.OD, p.OH, p.OW, p.Cout >> 5, C16, (int)blockIdx.x, (int)gridDim.x);
+    if (walk.items <= 0) return;
+    const int nbx = walk.nbx, nby = walk.nby, nbr = walk.nbr;
 #ifdef NM_DIAG
     int step_no = 0;
 #define NM_PSTAMP(i) do { if (p.stamps && lane == 0 && step_no < 64) p.stamps[(((size_t)blockIdx.x * 64 + step_no) * 8 + wave) * 16 + (i)] = clock64(); } while (0)
@@ -1809,80 +1743,19 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
         const half8* __restrict__ w8 = reinterpret_cast<const half8*>(p.w);
         const size_t plane = (size_t)p.Co_pad;
         const int lane_off = h * (int)plane + l31;
-        // pieces of this thread: piece k = channels 4 * quad .. +3 (of the chunk's 16) of halo voxel (pt >> 2) + 64k; four
-        // neighbouring lanes fetch one voxel's 64 contiguous bytes
-        const int quad = pt & 3;
-        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int v = (pt >> 2) + 64 * k, vc = min(v, HV - 1);
-            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
-            pc_slot[k] = (quad >> 1) * HV + hz * ZP + hy * HX + hx;    // half8 slot of the hi part in a halo buffer (lo: + 2 HV)
-            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + 4 * quad;
-            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
-        }
+        const HaloPieces<NP, HV, 4, EB, ConvParams> hp(pt, p);       // this thread's pieces of a halo tile (nm_halo_stage.h)
         using RawT = std::conditional_t<IH, nm_u32x2, f32x4>;
         RawT raw[NP]; f32x4 sc, sh, wreg[5];
 #pragma unroll
         for (int i = 0; i < 5; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};       // (SINGLE uses three of them; all five are operands of the counted waits)
-        const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * EB;   // halo voxel (1,1,1): always inside
-        // bit k: piece k of a brick's halo tile lies inside the volume
-        auto inside_mask = [&](const Work& w) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
-                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
-                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
-                m |= (in ? 1u : 0u) << k;
-            }
-            return m;
-        };
-        auto tile_base = [&](const Work& w, int cb) {               // wave-uniform: halo voxel (0,0,0), channel 16 cb (may lie
-            return nm_eptr(p.in, (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16), IH);   // outside)
-        };
-        auto load_piece = [&](const float* base, unsigned mask, auto K) {      // outside pieces fetch an inside voxel (zeroed later)
-            constexpr int k = decltype(K)::value;
-            if constexpr (IH) raw[k] = load8_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
-            else raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
-        };
-        auto load_affine = [&](const Work& w, int cb) {                       // always two loads: the waits below count instructions
-            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            sc = load16_untracked(ps, 16u * quad); sh = load16_untracked(ph, 16u * quad);
-        };
+        // loads and conversion of piece k: nm_halo_stage.h, on this kernel's registers (the counted waits below name them)
+        auto load_piece = [&](const float* base, unsigned mask, auto K) { hp.load_piece(raw[decltype(K)::value], base, mask, K); };
+        auto load_affine = [&](const Work& w, int cb) { hp.load_affine(&sc, &sh, w.n, cb); };    // always two loads: the waits below count instructions
         // wait until all but the N youngest vector-memory operations are done; ties every load destination to the wait
 #define NM_PRODUCER_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" \
             : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]), "+v"(raw[6]), "+v"(raw[7]), \
               "+v"(raw[8]), "+v"(raw[9]), "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]), "+v"(wreg[4]) :: "memory")
-        auto convert = [&](int buf, unsigned mask, auto K) {                  // activate, split, write piece k into halo buffer buf
-            constexpr int k = decltype(K)::value;
-            half4v hi4, lo4;
-            const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-                float v0, v1;
-                if constexpr (IH) { const unsigned u = raw[k][e >> 1]; v0 = nm_bf_lo(u); v1 = nm_bf_hi(u); }
-                else { v0 = raw[k][e]; v1 = raw[k][e + 1]; }
-                if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
-                // LeakyReLU (slope in (0, 1]) and the padding mask in two instructions per value: max(v, slope v) * keep
-                v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
-                half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
-                asm volatile("" : "+v"(hv));
-                const float t0 = v0 * NM_SPLIT_SCALE, t1 = v1 * NM_SPLIT_SCALE;
-                hi4[e] = hv[0]; hi4[e + 1] = hv[1];
-                if constexpr (!SINGLE) {                            // (conv mode 3 has no use for the lo halves)
-                    lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
-                    lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
-                }
-            }
-            if (pc_pos[k] >= 0) {
-                half4v* dst = reinterpret_cast<half4v*>(ldh + buf * 4 * HV + pc_slot[k]) + (quad & 1);
-                dst[0] = hi4;
-                if constexpr (!SINGLE) dst[4 * HV] = lo4;           // + 2 HV half8 slots
-            }
-        };
+        auto convert = [&](int buf, unsigned mask, auto K) { hp.template convert_split<SINGLE>(ldh + buf * 4 * HV, raw[decltype(K)::value], sc, sh, mask, K); };
         // direct-to-LDS copy of tap group g of (cout group cg, chunk cb) into weight buffer g: 18 one-KiB wave loads; every
         // producer wave issues five (two are issued twice) so that the counted waits are the same in all of them.  The
         // per-wave source / destination offsets inside a tap group are fixed: per call only a scalar base is computed.
@@ -1910,35 +1783,35 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 
         // The input runs two steps ahead of the MFMA waves: during step s the tile of step s+1 (loaded during step s-1) is
         // converted piece by piece, and each piece's registers are refilled at once with the load for step s+2.
-        Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+        Step cur = walk.first();
         int hb = 0;
-        Step s1 = cur; bool has1 = advance(s1);                     // step s+1 (= cur on the last step: staged, never read)
-        Step s2 = s1;  bool has2 = has1 && advance(s2);
-        unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
+        Step s1 = cur; bool has1 = walk.advance(s1);                     // step s+1 (= cur on the last step: staged, never read)
+        Step s2 = s1;  bool has2 = has1 && walk.advance(s2);
+        unsigned m_cvt = hp.inside_mask(cur.w), m_ld = m_cvt;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first two weight groups in the open, loads of the second tile in flight
         load_b_group(cur.w.cg, 0, 0);
         load_affine(cur.w, 0);
-        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        { const float* b = hp.tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         NM_PRODUCER_WAIT(0);
         store_b_group(0);
         load_b_group(cur.w.cg, 0, 1);
         static_for<NP>([&](auto K) { convert(0, m_cvt, K); });
         NM_PRODUCER_WAIT(0);
         store_b_group(1);
-        m_cvt = inside_mask(s1.w);
-        load_affine(s1.w, s1.cb);
-        { const float* b = tile_base(s1.w, s1.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        m_cvt = hp.inside_mask(s1.w);
+        load_affine(s1.w, s1.c.cb);
+        { const float* b = hp.tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         lds_barrier();
         for (;;) {
             // the tile being loaded (step s+2); its inside mask changes only with the brick
-            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = inside_mask(s2.w);
+            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = hp.inside_mask(s2.w);
             else m_ld = m_cvt;
-            const float* b2 = tile_base(s2.w, s2.cb);
+            const float* b2 = hp.tile_base(s2.w, s2.c.cb);
             NM_PSTAMP(0);
             // tap group 0: weights of this step's group 2; pieces 0-3.  Everything older than the 5 weight loads has landed
             // after the first wait (the tile of step s+1 and its affine were issued a step ago).
-            load_b_group(cur.w.cg, cur.cb, 2);
+            load_b_group(cur.w.cg, cur.c.cb, 2);
             if constexpr (SINGLE) { NM_PRODUCER_WAIT(3); } else { NM_PRODUCER_WAIT(5); }      // (the NWP weight loads are the youngest)
             NM_PSTAMP(1);
             static_for<4>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
@@ -1948,9 +1821,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             lds_barrier();
             NM_PSTAMP(3);
             // tap group 1: weights of the next step's group 0; pieces 4-9; the halo tile is complete at this barrier
-            load_b_group(s1.w.cg, s1.cb, 0);
+            load_b_group(s1.w.cg, s1.c.cb, 0);
             static_for<6>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 4>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 4>{}); });
-            load_affine(s2.w, s2.cb);                               // (sc / sh are free: piece 9 was their last user)
+            load_affine(s2.w, s2.c.cb);                               // (sc / sh are free: piece 9 was their last user)
             NM_PSTAMP(4);
             NM_PRODUCER_WAIT(8);                                    // the weight loads: 6 piece + 2 affine loads are younger
             store_b_group(0);
@@ -1958,14 +1831,14 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
             lds_barrier();
             NM_PSTAMP(6);
             // tap group 2: weights of the next step's group 1
-            load_b_group(s1.w.cg, s1.cb, 1);
+            load_b_group(s1.w.cg, s1.c.cb, 1);
             NM_PRODUCER_WAIT(0);                                    // (everything: the input loads are a group or more old)
             store_b_group(1);
             NM_PSTAMP(7);
             lds_barrier();
             NM_PSTAMP(8);
             if (!has1) break;
-            cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
+            cur = s1; s1 = s2; has1 = has2; has2 = has2 && walk.advance(s2);
             m_cvt = m_ld; hb ^= 1;
 #ifdef NM_DIAG
             ++step_no;
@@ -2048,7 +1921,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
         epi = w;
     };
 
-    Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+    Step cur = walk.first();
     int hb = 0;
     lds_barrier();                                                  // the producers' prologue
 
@@ -2076,7 +1949,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 
     for (;;) {
         Step nxt = cur;
-        const bool has_next = advance(nxt);
+        const bool has_next = walk.advance(nxt);
         if (part_due) { epi_part(part_w); part_due = false; }
         const bool run_epi = pending;
         // One read per MFMA gap, issued two taps (12 MFMAs, ~400 cycles) before its first use; before each MFMA "all but the
@@ -2159,7 +2032,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
         };
         if (run_epi) stream(std::true_type{}); else stream(std::false_type{});
         if (run_epi) { pending = false; part_due = true; part_w = epi; }      // (epi_take may name the next brick at once: one-chunk layers)
-        if (cur.cb == C16 - 1) { epi_take(cur.w); pending = true; }
+        if (cur.c.cb == C16 - 1) { epi_take(cur.w); pending = true; }
         NM_PSTAMP(7);
         if (!has_next) break;
         cur = nxt; hb ^= 1;
@@ -2187,7 +2060,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16p_kernel(ConvParams p) {
 //     themselves (16-byte stores from transposed accumulators, DPP partial sums, one extra workgroup barrier per brick);
 //   * LDS: two weight buffers (2 x 36 KB) instead of three, so the B operands of a tap group's first tap are read after
 //     the barrier that publishes them; operands one tap (12 MFMAs) ahead, double buffered.
-//   LDS: halo [2][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [2][9 taps][4 planes][64] x 16 B, GroupNorm scratch, bias.
+//   LDS: halo [2][hi h0 | hi h1 | lo h0 | lo h1][600] x 16 B, weights [2][9 taps][4 planes][64] x 16 B, GroupNorm scratch, bias (F16p2Lds).
+// The walk is nm_walk::Walk<4, true>, the pieces and the split conversion HaloPieces (nm_brick_walk.h, nm_halo_stage.h).
 // Split-fp16 (three products), fp32 storage only: the one-product modes (3 / 4) have their own kernel, conv_f16q2, below.
 // The epilogue stays exposed (7 800 of a 64-channel brick's 58 000 cycles).  A variant with one accumulator per tile and the finished
 // brick's epilogue interleaved into the next brick's first step was built (round 6) and was slower, 1.31-1.33 -> 1.36-1.43 ms at
@@ -2198,48 +2072,18 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
     constexpr int NP = 10;                                          // 16-byte input pieces per producer thread and step (2400 / 256)
     extern __shared__ f32x4 lds[];
     half8* ldh = reinterpret_cast<half8*>(lds);                     // [2][4][HV]
-    half8* ldb = ldh + 8 * HV;                                      // [2][GB]
-    float* red = reinterpret_cast<float*>(ldb + 2 * GB);            // [4 waves][64 channels][2]
-    float* lbias = red + 512;                                       // [Cout] bias (zeros without one), written once by the producers
+    half8* ldb = ldh + F16p2Lds::kHaloSlots;                        // [2][GB]
+    float* red = reinterpret_cast<float*>(ldb + F16p2Lds::kWeightSlots);   // [4 waves][64 channels][2]
+    float* lbias = red + F16p2Lds::kRedFloats;                      // [Cout] bias (zeros without one), written once by the producers
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
     const int C16 = p.Cin >> 4;
-    const int ncg = p.Cout >> 6;
-    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 2, nbr = nbx * nby * nbz;
-    const int total = p.N * nbr * ncg;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
-    if (id_first >= id_last) return;
-
-    struct Work { int n, oz0, oy0, ox0, cg; };
-    const bool tiled = p.st_x != 0;                                 // XCD super-tile order (one cout group only), see super_tile_item
-    auto decode = [&](int id) {
-        Work w;
-        if (tiled) {
-            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
-            w.cg = 0; w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 2;
-            return w;
-        }
-        w.cg = id % ncg; const int bid = id / ncg;
-        w.n = bid / nbr; const int br = bid % nbr;
-        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 2;
-        return w;
-    };
-    auto next_work = [&](Work w, int id) {
-        if (tiled) return decode(id);
-        if (++w.cg == ncg) {
-            w.cg = 0;
-            if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 4) == p.OD) { w.oz0 = 0; ++w.n; } } }
-        }
-        return w;
-    };
-    struct Step { Work w; int id, cb; };
-    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
-        if (st.cb + 1 < C16) { ++st.cb; return true; }
-        if (st.id + 1 >= id_last) return false;
-        st.cb = 0; ++st.id; st.w = next_work(st.w, st.id);
-        return true;
-    };
+    using Walk = nm_walk::Walk<4, true>;                            // nm_brick_walk.h: the stream of steps (brick, cout group, 16-channel chunk) of this workgroup
+    using Work = Walk::Work;
+    using Step = Walk::Step;
+    const Walk walk(p.st, p.N, p.OD, p.OH, p.OW, p.Cout >> 6, C16, (int)blockIdx.x, (int)gridDim.x);
+    if (walk.items <= 0) return;
+    const int nbx = walk.nbx, nby = walk.nby, nbr = walk.nbr;
 
 #ifdef NM_DIAG
     int step_no = 0;                                                // (NM_PSTAMP: tools/diag_f16p2_steps.py)
@@ -2249,71 +2093,18 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
         const int pt = tid - 256, pw = wave - 4;
         const half8* __restrict__ w8 = reinterpret_cast<const half8*>(p.w);
         const size_t plane = (size_t)p.Co_pad;
-        const int quad = pt & 3;
-        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int v = (pt >> 2) + 64 * k, vc = min(v, HV - 1);
-            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
-            pc_slot[k] = (quad >> 1) * HV + hz * ZP + hy * HX + hx;
-            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + 4 * quad;
-            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
-        }
+        const HaloPieces<NP, HV, 4, 4u, ConvParams> hp(pt, p);       // this thread's pieces of a halo tile (nm_halo_stage.h)
         f32x4 raw[NP], sc, sh, wreg[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * 4u;   // halo voxel (1,1,1): always inside (byte offset)
-        auto inside_mask = [&](const Work& w) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
-                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
-                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
-                m |= (in ? 1u : 0u) << k;
-            }
-            return m;
-        };
-        auto tile_base = [&](const Work& w, int cb) {
-            return p.in + (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16);
-        };
-        auto load_piece = [&](const float* base, unsigned mask, auto K) {
-            constexpr int k = decltype(K)::value;
-            raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * 4u : rel111);
-        };
-        auto load_affine = [&](const Work& w, int cb) {             // always two loads: the waits below count instructions
-            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            sc = load16_untracked(ps, 16u * quad);
-            sh = load16_untracked(ph, 16u * quad);
-        };
+        // loads and conversion of piece k: nm_halo_stage.h, on this kernel's registers (the counted waits below name them)
+        auto load_piece = [&](const float* base, unsigned mask, auto K) { hp.load_piece(raw[decltype(K)::value], base, mask, K); };
+        auto load_affine = [&](const Work& w, int cb) { hp.load_affine(&sc, &sh, w.n, cb); };    // always two loads: the waits below count instructions
 #define NM_PRODUCER2_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" \
             : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]), "+v"(raw[6]), "+v"(raw[7]), \
               "+v"(raw[8]), "+v"(raw[9]), "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]), "+v"(wreg[4]), \
               "+v"(wreg[5]), "+v"(wreg[6]), "+v"(wreg[7]), "+v"(wreg[8]) :: "memory")
-        auto convert = [&](int buf, unsigned mask, auto K) {        // activate, split, write piece k into halo buffer buf
-            constexpr int k = decltype(K)::value;
-            half4v hi4, lo4;
-            const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-                float v0 = raw[k][e], v1 = raw[k][e + 1];
-                if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
-                v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
-                half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
-                asm volatile("" : "+v"(hv));
-                const float t0 = v0 * NM_SPLIT_SCALE, t1 = v1 * NM_SPLIT_SCALE;
-                hi4[e] = hv[0]; hi4[e + 1] = hv[1];
-                lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
-                lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
-            }
-            if (pc_pos[k] >= 0) {
-                half4v* dst = reinterpret_cast<half4v*>(ldh + buf * 4 * HV + pc_slot[k]) + (quad & 1);
-                dst[0] = hi4;
-                dst[4 * HV] = lo4;
-            }
-        };
+        auto convert = [&](int buf, unsigned mask, auto K) { hp.template convert_split<false>(ldh + buf * 4 * HV, raw[decltype(K)::value], sc, sh, mask, K); };
         // tap group g of (cout group cg, chunk cb): 36 one-KiB wave pieces (tap t, plane r, 64 channels), nine per producer wave.
         // The weight copies are three quarters of a producer wave's issue slots.
         constexpr int NW = 9;
@@ -2343,27 +2134,27 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             for (int i = 0; i < NW; ++i) *reinterpret_cast<f32x4*>(lbase + w_dst[i]) = wreg[i];
         };
 
-        Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+        Step cur = walk.first();
         int hb = 0, gpar = 0;                                       // halo buffer of the step the MFMA waves run; weight buffer of its tap group
-        Step s1 = cur; bool has1 = advance(s1);
-        Step s2 = s1;  bool has2 = has1 && advance(s2);
-        unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
+        Step s1 = cur; bool has1 = walk.advance(s1);
+        Step s2 = s1;  bool has2 = has1 && walk.advance(s2);
+        unsigned m_cvt = hp.inside_mask(cur.w), m_ld = m_cvt;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first weight group in the open, loads of the second tile in flight
         load_b_group(cur.w.cg, 0, 0);
         load_affine(cur.w, 0);
-        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        { const float* b = hp.tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         NM_PRODUCER2_WAIT(0);
         store_b_group(0);
         static_for<NP>([&](auto K) { convert(0, m_cvt, K); });
-        m_cvt = inside_mask(s1.w);
-        load_affine(s1.w, s1.cb);
-        { const float* b = tile_base(s1.w, s1.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        m_cvt = hp.inside_mask(s1.w);
+        load_affine(s1.w, s1.c.cb);
+        { const float* b = hp.tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         lds_barrier();
         for (;;) {
-            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = inside_mask(s2.w);
+            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = hp.inside_mask(s2.w);
             else m_ld = m_cvt;
-            const float* b2 = tile_base(s2.w, s2.cb);
+            const float* b2 = hp.tile_base(s2.w, s2.c.cb);
             // The ten pieces are dealt 3 / 5 / 2 to the three tap groups (round 3; they were 4 / 6 / 0).  In-kernel stamps
             // (tools/diag_f16p2_steps.py) showed the producers, not the MFMA waves, arriving last at the first two barriers of a step
             // (MFMA waves waiting 734 + 1011 of a 15 272-cycle step) with 1 100 cycles to spare at the third: a step's 39 global loads
@@ -2372,7 +2163,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             // tap group 0: weights of this step's group 1 (into the buffer group 2 of the last step was read from); pieces 0-2.
             // Everything older than the 9 weight loads has landed after the first wait.
             NM_PSTAMP(0);
-            load_b_group(cur.w.cg, cur.cb, 1);
+            load_b_group(cur.w.cg, cur.c.cb, 1);
             NM_PRODUCER2_WAIT(9);                                   // (the NW weight loads are the youngest)
             NM_PSTAMP(1);
             static_for<3>([&](auto K) { convert(hb ^ 1, m_cvt, K); load_piece(b2, m_ld, K); });
@@ -2382,7 +2173,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             lds_barrier(); gpar ^= 1;
             NM_PSTAMP(3);
             // tap group 1: weights of this step's group 2; pieces 3-7
-            load_b_group(cur.w.cg, cur.cb, 2);
+            load_b_group(cur.w.cg, cur.c.cb, 2);
             static_for<5>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 3>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 3>{}); });
             NM_PSTAMP(4);
             NM_PRODUCER2_WAIT(5);                                   // the weight loads: 5 piece loads are younger
@@ -2391,9 +2182,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             lds_barrier(); gpar ^= 1;
             NM_PSTAMP(6);
             // tap group 2: weights of the next step's group 0; pieces 8-9; the halo tile is complete at this barrier
-            load_b_group(s1.w.cg, s1.cb, 0);
+            load_b_group(s1.w.cg, s1.c.cb, 0);
             static_for<2>([&](auto K) { convert(hb ^ 1, m_cvt, ic<decltype(K)::value + 8>{}); load_piece(b2, m_ld, ic<decltype(K)::value + 8>{}); });
-            load_affine(s2.w, s2.cb);                               // (sc / sh are free: piece 9 was their last user)
+            load_affine(s2.w, s2.c.cb);                               // (sc / sh are free: piece 9 was their last user)
             NM_PRODUCER2_WAIT(0);
             store_b_group(gpar ^ 1);
             NM_PSTAMP(7);
@@ -2402,9 +2193,9 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 #ifdef NM_DIAG
             ++step_no;
 #endif
-            if (cur.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
+            if (cur.c.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
             if (!has1) break;
-            cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
+            cur = s1; s1 = s2; has1 = has2; has2 = has2 && walk.advance(s2);
             m_cvt = m_ld; hb ^= 1;
         }
         NM_PRODUCER2_WAIT(0);                                       // loads still in flight for a step that does not exist
@@ -2428,7 +2219,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc[mt][nt][r] = 0.f; accl[mt][nt][r] = 0.f; }
 
-    Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+    Step cur = walk.first();
     int hb = 0, gpar = 0;
     lds_barrier();                                                  // the producers' prologue
 
@@ -2443,7 +2234,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
     }
     for (;;) {
         Step nxt = cur;
-        const bool has_next = advance(nxt);
+        const bool has_next = walk.advance(nxt);
         const unsigned va = (unsigned)(size_t)(ldh + hb * 4 * HV + h * HV + arow0);          // this step's halo tile
         const unsigned van = (unsigned)(size_t)(ldh + (hb ^ 1) * 4 * HV + h * HV + arow0);   // the next step's
         const unsigned vbe = vb0 + (unsigned)(gpar * GB * 16), vbo = vb0 + (unsigned)((gpar ^ 1) * GB * 16);   // buffers of groups 0/2 and 1
@@ -2494,7 +2285,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
             ah0[0] = lds_read16_untracked<0>(van); al0[0] = lds_read16_untracked<LO>(van);
             ah1[0] = lds_read16_untracked<YO>(van); al1[0] = lds_read16_untracked<LO + YO>(van);
         }
-        if (cur.cb == C16 - 1) {
+        if (cur.c.cb == C16 - 1) {
             // ---- epilogue of the finished brick (exposed): transposed accumulators -> 16-byte stores, DPP partial sums
             const Work& w = cur.w;
             NM_PSTAMP(8);
@@ -2573,6 +2364,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p2_kernel(ConvParams p) {
 //   four barriers per 324-MFMA step.  halo [2][hi h0 | hi h1 | lo h0 | lo h1][1000] x 16 B, weights [2][7 taps][4 planes][32] x 16 B,
 //   GroupNorm scratch [2 z halves][4 waves][32][2], bias: 158 848 B.
 //   Barriers: both roles take theirs from nm_f16p8_plan.h (group ends, brick end); tests/cpp/f16p8_barrier_walk.cpp walks both.
+//   The walk is nm_walk::Walk<8, false> (its cursor is the plan's), the pieces (1000 halo voxels) and the split conversion HaloPieces.
 // Arithmetic per output element is conv_f16p's, operation for operation (chunks ascending, taps 0 ... 26, per tile acc += bh ah,
 // accl += bl ah, accl += bh al; (acc + accl 2^-11) + bias), and a brick writes the two GroupNorm partial rows of the two 4 x 8 x 8
 // bricks it covers exactly as conv_f16p would: stored outputs, partial sums and everything downstream are bit-identical.
@@ -2592,38 +2384,12 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
     const int C16 = p.Cin >> 4;
-    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 3, nbr = nbx * nby * nbz;
-    const int total = p.N * nbr;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
-    if (id_first >= id_last) return;
-    const int items = id_last - id_first;
-
-    struct Work { int n, oz0, oy0, ox0; };
-    const bool tiled = p.st_x != 0;                                 // XCD super-tile order on 8 x 8 x 8 bricks, see super_tile_item
-    auto decode = [&](int id) {
-        Work w;
-        if (tiled) {
-            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
-            w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 3;
-            return w;
-        }
-        w.n = id / nbr; const int br = id % nbr;
-        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 3;
-        return w;
-    };
-    auto next_work = [&](Work w, int id) {
-        if (tiled) return decode(id);
-        if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 8) == p.OD) { w.oz0 = 0; ++w.n; } } }
-        return w;
-    };
-    struct Step { Work w; pl::Cursor c; };
-    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
-        const int item = st.c.item;
-        if (!pl::next_step(st.c, items, C16)) return false;
-        if (st.c.item != item) st.w = next_work(st.w, id_first + st.c.item);
-        return true;
-    };
+    using Walk = nm_walk::Walk<8, false>;                           // nm_brick_walk.h: the stream of steps (brick, 16-channel chunk) of this workgroup
+    using Work = Walk::Work;
+    using Step = Walk::Step;
+    const Walk walk(p.st, p.N, p.OD, p.OH, p.OW, 1, C16, (int)blockIdx.x, (int)gridDim.x);
+    if (walk.items <= 0) return;
+    const int nbx = walk.nbx, nby = walk.nby;
 
     if (wave >= 4) {
         // =========================== producer waves ===========================================================
@@ -2631,72 +2397,19 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
         const half8* __restrict__ w8 = reinterpret_cast<const half8*>(p.w);
         const size_t plane = (size_t)p.Co_pad;
         const int lane_off = h * (int)plane + l31;
-        const int quad = pt & 3;
-        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int v = (pt >> 2) + 64 * k, vc = min(v, HV - 1);
-            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
-            pc_slot[k] = (quad >> 1) * HV + hz * ZP + hy * HX + hx;    // half8 slot of the hi part in a halo buffer (lo: + 2 HV)
-            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + 4 * quad;
-            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
-        }
+        const HaloPieces<NP, HV, 4, 4u, ConvParams> hp(pt, p);       // this thread's pieces of a halo tile (nm_halo_stage.h)
         f32x4 raw[NP], sc, sh, wreg[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * 4u;   // halo voxel (1,1,1): always inside (byte offset)
-        auto inside_mask = [&](const Work& w) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
-                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
-                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
-                m |= (in ? 1u : 0u) << k;
-            }
-            return m;
-        };
-        auto tile_base = [&](const Work& w, int cb) {
-            return p.in + (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16);
-        };
-        auto load_piece = [&](const float* base, unsigned mask, auto K) {      // outside pieces fetch an inside voxel (zeroed later)
-            constexpr int k = decltype(K)::value;
-            raw[k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * 4u : rel111);
-        };
-        auto load_affine = [&](const Work& w, int cb) {             // always two loads: the waits below count instructions
-            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            sc = load16_untracked(ps, 16u * quad);
-            sh = load16_untracked(ph, 16u * quad);
-        };
+        // loads and conversion of piece k: nm_halo_stage.h, on this kernel's registers (the counted waits below name them)
+        auto load_piece = [&](const float* base, unsigned mask, auto K) { hp.load_piece(raw[decltype(K)::value], base, mask, K); };
+        auto load_affine = [&](const Work& w, int cb) { hp.load_affine(&sc, &sh, w.n, cb); };    // always two loads: the waits below count instructions
         // wait until all but the N youngest vector-memory operations are done; ties every load destination to the wait
 #define NM_PRODUCER8_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" \
             : "+v"(raw[0]), "+v"(raw[1]), "+v"(raw[2]), "+v"(raw[3]), "+v"(raw[4]), "+v"(raw[5]), "+v"(raw[6]), "+v"(raw[7]), \
               "+v"(raw[8]), "+v"(raw[9]), "+v"(raw[10]), "+v"(raw[11]), "+v"(raw[12]), "+v"(raw[13]), "+v"(raw[14]), "+v"(raw[15]), \
               "+v"(sc), "+v"(sh), "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]) :: "memory")
-        auto convert = [&](int buf, unsigned mask, auto K) {        // activate, split, write piece k into halo buffer buf
-            constexpr int k = decltype(K)::value;
-            half4v hi4, lo4;
-            const float keep = ((mask >> k) & 1) ? 1.f : 0.f;       // padding is zero AFTER the activation
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-                float v0 = raw[k][e], v1 = raw[k][e + 1];
-                if (has_affine) { v0 = __builtin_fmaf(v0, sc[e], sh[e]); v1 = __builtin_fmaf(v1, sc[e + 1], sh[e + 1]); }
-                v0 = fmaxf(v0 * keep, (v0 * keep) * p.in_slope); v1 = fmaxf(v1 * keep, (v1 * keep) * p.in_slope);
-                half2v hv = __builtin_convertvector(f32x2{v0, v1}, half2v);
-                asm volatile("" : "+v"(hv));
-                const float t0 = v0 * NM_SPLIT_SCALE, t1 = v1 * NM_SPLIT_SCALE;
-                hi4[e] = hv[0]; hi4[e + 1] = hv[1];
-                lo4[e] = (_Float16)__builtin_fmaf((float)hv[0], -NM_SPLIT_SCALE, t0);
-                lo4[e + 1] = (_Float16)__builtin_fmaf((float)hv[1], -NM_SPLIT_SCALE, t1);
-            }
-            if (pc_pos[k] >= 0) {
-                half4v* dst = reinterpret_cast<half4v*>(ldh + buf * 4 * HV + pc_slot[k]) + (quad & 1);
-                dst[0] = hi4;
-                dst[4 * HV] = lo4;                                  // + 2 HV half8 slots
-            }
-        };
+        auto convert = [&](int buf, unsigned mask, auto K) { hp.template convert_split<false>(ldh + buf * 4 * HV, raw[decltype(K)::value], sc, sh, mask, K); };
         // tap group g of chunk cb: group_taps(g) x 2 one-KiB wave pieces (tap t, hi | lo; lanes = plane half h x 32 channels).  Every
         // producer wave issues four loads per group so that the counted waits are the same in all of them: 14 pieces (12 in the six-tap
         // group) dealt round robin, the surplus slots repeat the group's last piece.
@@ -2734,27 +2447,27 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
             for (int i = 0; i < NW; ++i) *reinterpret_cast<f32x4*>(lbase + ((short_group && i == NW - 1) ? w_dst6 : w_dst[i])) = wreg[i];
         };
 
-        Step cur; cur.w = decode(id_first); cur.c.item = 0; cur.c.cb = 0;
+        Step cur = walk.first();
         int hb = 0;                                                 // halo buffer of the step the MFMA waves run
-        Step s1 = cur; bool has1 = advance(s1);                     // step s+1 (= cur on the last step: staged, never read)
-        Step s2 = s1;  bool has2 = has1 && advance(s2);
-        unsigned m_cvt = inside_mask(cur.w), m_ld = m_cvt;
+        Step s1 = cur; bool has1 = walk.advance(s1);                     // step s+1 (= cur on the last step: staged, never read)
+        Step s2 = s1;  bool has2 = has1 && walk.advance(s2);
+        unsigned m_cvt = hp.inside_mask(cur.w), m_ld = m_cvt;
         for (int c = pt; c < 32; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first weight group in the open, loads of the second tile in flight
         load_b_group(0, ic<0>{});
         load_affine(cur.w, 0);
-        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        { const float* b = hp.tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         NM_PRODUCER8_WAIT(0);
         store_b_group(ic<0>{});
         static_for<NP>([&](auto K) { convert(0, m_cvt, K); });
-        m_cvt = inside_mask(s1.w);
+        m_cvt = hp.inside_mask(s1.w);
         load_affine(s1.w, s1.c.cb);
-        { const float* b = tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
+        { const float* b = hp.tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m_cvt, K); }); }
         lds_barrier();
         for (;;) {
-            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = inside_mask(s2.w);
+            if (s2.w.n != s1.w.n || s2.w.oz0 != s1.w.oz0 || s2.w.oy0 != s1.w.oy0 || s2.w.ox0 != s1.w.ox0) m_ld = hp.inside_mask(s2.w);
             else m_ld = m_cvt;
-            const float* b2 = tile_base(s2.w, s2.c.cb);
+            const float* b2 = hp.tile_base(s2.w, s2.c.cb);
             // One stage per tap group g: fetch the weights of the group after it (this step's g + 1, or the next step's group 0) into
             // the buffer group g - 1 was read from, convert this stage's pieces of the tile of step s + 1 and refill their registers
             // with the loads for step s + 2, store the weights, meet the MFMA waves at the group's barrier.  The tile of step s + 1 is
@@ -2775,7 +2488,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
             });
             if (pl::brick_end(cur.c.cb, C16)) lds_barrier();        // the MFMA waves' epilogue barrier of a finished brick
             if (!has1) break;
-            cur = s1; s1 = s2; has1 = has2; has2 = has2 && advance(s2);
+            cur = s1; s1 = s2; has1 = has2; has2 = has2 && walk.advance(s2);
             m_cvt = m_ld; hb ^= 1;
         }
         NM_PRODUCER8_WAIT(0);                                       // loads still in flight for a step that does not exist
@@ -2798,7 +2511,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[m][r] = 0.f; accl[m][r] = 0.f; }
 
-    Step cur; cur.w = decode(id_first); cur.c.item = 0; cur.c.cb = 0;
+    Step cur = walk.first();
     int hb = 0;
     lds_barrier();                                                  // the producers' prologue
 
@@ -2817,7 +2530,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
     const int nbr4 = nbx * nby * (p.OD >> 2);                       // GroupNorm partial rows per frame: one per 4 x 8 x 8 brick
     for (;;) {
         Step nxt = cur;
-        const bool has_next = advance(nxt);
+        const bool has_next = walk.advance(nxt);
         const unsigned va = (unsigned)(size_t)(ldh + hb * 4 * HV + h * HV + arow0);          // this step's halo tile
         const unsigned van = (unsigned)(size_t)(ldh + (hb ^ 1) * 4 * HV + h * HV + arow0);   // the next step's
         static_for<pl::kTaps>([&](auto TT) {
@@ -2938,7 +2651,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16p8_kernel(ConvParams p) {
 //     thread and step instead of 10 eight-byte ones);
 //   * the MFMA waves keep operands two taps ahead (three register sets, counted lgkmcnt waits): a tap is only four MFMAs.
 // Arithmetic per output element (k order: channel chunk outer, tap inner; epilogue) is conv_f16p2's with the two lo products left out.
-//   LDS: halo [2][h0 | h1][600] x 16 B, weights [2][27 taps][h0 | h1][64] x 16 B, GroupNorm scratch, bias: 148 KB + bias.
+//   LDS: halo [2][h0 | h1][600] x 16 B, weights [2][27 taps][h0 | h1][64] x 16 B, GroupNorm scratch, bias: 148 KB + bias (F16q2Lds).
+// The walk is nm_walk::Walk<4, true>; the pieces (quads of fp32 | octets of bfloat16), fix_affine and the packed conversion are HaloPieces'.
 template <int IO = 0>
 __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
     constexpr bool IH = (IO & 1) != 0, OH = (IO & 2) != 0;
@@ -2951,66 +2665,25 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
     constexpr int NA = IH ? 4 : 2;                                  // affine loads per step
     extern __shared__ f32x4 lds[];
     half8* ldh = reinterpret_cast<half8*>(lds);                     // [2][2][HV]
-    half8* ldb = ldh + 4 * HV;                                      // [2][WB]
-    float* red = reinterpret_cast<float*>(ldb + 2 * WB);            // [4 waves][64 channels][2]
-    float* lbias = red + 512;                                       // [Cout]
+    half8* ldb = ldh + F16q2Lds::kHaloSlots;                        // [2][WB]
+    float* red = reinterpret_cast<float*>(ldb + F16q2Lds::kWeightSlots);   // [4 waves][64 channels][2]
+    float* lbias = red + F16q2Lds::kRedFloats;                      // [Cout]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
     const int C16 = p.Cin >> 4;
-    const int ncg = p.Cout >> 6;
-    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 2, nbr = nbx * nby * nbz;
-    const int total = p.N * nbr * ncg;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
-    if (id_first >= id_last) return;
-
-    struct Work { int n, oz0, oy0, ox0, cg; };
-    const bool tiled = p.st_x != 0;
-    auto decode = [&](int id) {
-        Work w;
-        if (tiled) {
-            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
-            w.cg = 0; w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 2;
-            return w;
-        }
-        w.cg = id % ncg; const int bid = id / ncg;
-        w.n = bid / nbr; const int br = bid % nbr;
-        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 2;
-        return w;
-    };
-    auto next_work = [&](Work w, int id) {
-        if (tiled) return decode(id);
-        if (++w.cg == ncg) {
-            w.cg = 0;
-            if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 4) == p.OD) { w.oz0 = 0; ++w.n; } } }
-        }
-        return w;
-    };
-    struct Step { Work w; int id, cb; };
-    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
-        if (st.cb + 1 < C16) { ++st.cb; return true; }
-        if (st.id + 1 >= id_last) return false;
-        st.cb = 0; ++st.id; st.w = next_work(st.w, st.id);
-        return true;
-    };
+    using Walk = nm_walk::Walk<4, true>;                            // nm_brick_walk.h: the stream of steps (brick, cout group, 16-channel chunk) of this workgroup
+    using Work = typename Walk::Work;
+    using Step = typename Walk::Step;
+    const Walk walk(p.st, p.N, p.OD, p.OH, p.OW, p.Cout >> 6, C16, (int)blockIdx.x, (int)gridDim.x);
+    if (walk.items <= 0) return;
+    const int nbx = walk.nbx, nby = walk.nby, nbr = walk.nbr;
 
     if (wave >= 4) {
         // =========================== producer waves ===========================================================
         const int pt = tid - 256, pw = wave - 4;
         const half8* __restrict__ w8 = reinterpret_cast<const half8*>(p.w);
         const size_t plane = (size_t)p.Co_pad;
-        // piece k of this thread: halo voxel v, channel group sub (fp32 input: a quad of the chunk's 16 channels, v = pt / 4 + 64 k;
-        // bfloat16 input: one of its two octets, v = pt / 2 + 128 k)
-        const int sub = IH ? (pt & 1) : (pt & 3);
-        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int v = IH ? (pt >> 1) + 128 * k : (pt >> 2) + 64 * k, vc = min(v, HV - 1);
-            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
-            pc_slot[k] = (IH ? sub : (sub >> 1)) * HV + hz * ZP + hy * HX + hx;
-            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + NCH * sub;
-            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
-        }
+        const HaloPieces<NP, HV, NCH, EB, ConvParams> hp(pt, p);       // this thread's pieces of a halo tile (nm_halo_stage.h)
         // two register sets for the input pieces (and their affine): a tile's loads are issued TWO producer iterations before its
         // conversion - one full step of cover.  (With one set the loads of step s + 2 were issued between the conversions of step
         // s + 1 and consumed at the top of the next iteration: half a step of cover for an HBM round trip; loads alone or conversions
@@ -3018,45 +2691,10 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         f32x4 raw[2][NP], sc[2][NA / 2], sh[2][NA / 2], wreg[NWL];
 #pragma unroll
         for (int i = 0; i < NWL; ++i) wreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * EB;   // halo voxel (1,1,1): always inside
-        auto inside_mask = [&](const Work& w) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
-                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
-                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
-                m |= (in ? 1u : 0u) << k;
-            }
-            return m;
-        };
-        auto tile_base = [&](const Work& w, int cb) {
-            return nm_eptr(p.in, (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16), IH);
-        };
-        auto load_piece = [&](const float* base, unsigned mask, auto K, auto SET) {
-            constexpr int k = decltype(K)::value, set = decltype(SET)::value;
-            raw[set][k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
-        };
-        auto load_affine = [&](const Work& w, int cb, auto SET) {   // always NA loads: the waits below count instructions
-            constexpr int set = decltype(SET)::value;
-            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-#pragma unroll
-            for (int q = 0; q < NA / 2; ++q) {
-                sc[set][q] = load16_untracked(ps, 4u * (unsigned)(NCH * sub + 4 * q));
-                sh[set][q] = load16_untracked(ph, 4u * (unsigned)(NCH * sub + 4 * q));
-            }
-        };
-        // a tensor without a pending affine gets the identity, once per step (behind the wait that covers the loads above): the
-        // conversion below is then branch- and select-free (x * 1 + 0 is x)
-        auto fix_affine = [&](auto SET) {
-            constexpr int set = decltype(SET)::value;
-            if (!has_affine) {
-#pragma unroll
-                for (int q = 0; q < NA / 2; ++q) { sc[set][q] = f32x4{1.f, 1.f, 1.f, 1.f}; sh[set][q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            }
-        };
+        // loads and conversion of piece k of register set SET: nm_halo_stage.h, on this kernel's registers
+        auto load_piece = [&](const float* base, unsigned mask, auto K, auto SET) { hp.load_piece(raw[decltype(SET)::value][decltype(K)::value], base, mask, K); };
+        auto load_affine = [&](const Work& w, int cb, auto SET) { hp.load_affine(sc[decltype(SET)::value], sh[decltype(SET)::value], w.n, cb); };   // always NA loads: the waits below count instructions
+        auto fix_affine = [&](auto SET) { hp.fix_affine(sc[decltype(SET)::value], sh[decltype(SET)::value]); };
         // counted waits: one asm statement that the compiler must order every use of the named registers behind
 #define NM_Q2_REGS_W "+v"(wreg[0]), "+v"(wreg[1]), "+v"(wreg[2]), "+v"(wreg[3]), "+v"(wreg[4]), "+v"(wreg[5]), "+v"(wreg[6]), \
                      "+v"(wreg[7]), "+v"(wreg[8]), "+v"(wreg[9]), "+v"(wreg[10]), "+v"(wreg[11]), "+v"(wreg[12]), "+v"(wreg[13])
@@ -3067,37 +2705,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
                              "+v"(raw[S][5]), "+v"(raw[S][6]), "+v"(raw[S][7]), "+v"(raw[S][8]), "+v"(raw[S][9]), "+v"(sc[S][0]), "+v"(sh[S][0]) :: "memory")
 #define NM_Q2_WAIT_SET(S, NH, NF) do { if constexpr (IH) { NM_Q2_WAIT_SET_H(S, NH); } else { NM_Q2_WAIT_SET_F(S, NF); } } while (0)
 #define NM_Q2_WAIT_WP(NH, NF) do { if constexpr (IH) { NM_Q2_WAIT_W(NH); } else { NM_Q2_WAIT_W(NF); } } while (0)
-        auto convert = [&](int buf, unsigned mask, auto K, auto SET) {   // activate, round to fp16, write piece k into halo buffer buf
-            constexpr int k = decltype(K)::value, set = decltype(SET)::value;
-            const bool keep = ((mask >> k) & 1) != 0;               // padding is zero AFTER the activation: selected on the packed halves
-            unsigned pk[NCH / 2];
-#pragma unroll
-            for (int e = 0; e < NCH; e += 2) {
-                float v0, v1;
-                // (by value: bit_cast of a vector element through a reference reads element 0)
-                if constexpr (IH) { const float rf = raw[set][k][e >> 1]; const unsigned u = nm_fbits(rf); v0 = nm_bf_lo(u); v1 = nm_bf_hi(u); }
-                else { v0 = raw[set][k][e]; v1 = raw[set][k][e + 1]; }
-                // the pair's affine and slope product as PACKED fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32: two elements per issue
-                // slot - the producers are bound by vector issue); the same fma / mul / max per element
-                f32x2 vv = f32x2{v0, v1};
-                const f32x4 sq = sc[set][e >> 2], hq = sh[set][e >> 2];
-                const f32x2 s2 = (e & 2) ? f32x2{sq[2], sq[3]} : f32x2{sq[0], sq[1]}, h2 = (e & 2) ? f32x2{hq[2], hq[3]} : f32x2{hq[0], hq[1]};
-                vv = __builtin_elementwise_fma(vv, s2, h2);
-                const f32x2 vs = vv * f32x2{p.in_slope, p.in_slope};
-                vv = f32x2{fmaxf(vv[0], vs[0]), fmaxf(vv[1], vs[1])};
-                half2v hv = __builtin_convertvector(vv, half2v);
-                asm volatile("" : "+v"(hv));
-                pk[e >> 1] = keep ? __builtin_bit_cast(unsigned, hv) : 0u;
-            }
-            if (pc_pos[k] >= 0) {
-                if constexpr (IH) {
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    *reinterpret_cast<u32x4*>(ldh + buf * 2 * HV + pc_slot[k]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-                } else {
-                    reinterpret_cast<nm_u32x2*>(ldh + buf * 2 * HV + pc_slot[k])[sub & 1] = nm_u32x2{pk[0], pk[1]};
-                }
-            }
-        };
+        auto convert = [&](int buf, unsigned mask, auto K, auto SET) { hp.convert_packed(ldh + buf * 2 * HV, raw[decltype(SET)::value][decltype(K)::value], sc[decltype(SET)::value], sh[decltype(SET)::value], mask, K); };
         // the step's weights: 54 one-KiB wave pieces (tap t, plane r of (cout group cg, chunk cb)), piece j = pw + 4 i of producer wave pw:
         // r = pw & 1 for every piece of the wave and t = (pw >> 1) + 2 i, so a piece's source is src0 + i * wstep and its LDS slot
         // dst0 + 256 i - one add per load, an immediate offset per store (slots 54, 55 - i = 13 of waves 2, 3 - repeat the wave's piece 12:
@@ -3121,49 +2729,49 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
             *reinterpret_cast<f32x4*>(dst0 + ilast * 256) = wreg[13];
         };
 
-        Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+        Step cur = walk.first();
         int hb = 0;                                                 // buffers (halo and weights alike) of the step the MFMA waves run
-        Step s1 = cur; bool has1 = advance(s1);
-        Step s2 = s1;  bool has2 = has1 && advance(s2);
-        Step s3 = s2;  bool has3 = has2 && advance(s3);
-        unsigned m1 = inside_mask(cur.w), m2, m3;
+        Step s1 = cur; bool has1 = walk.advance(s1);
+        Step s2 = s1;  bool has2 = has1 && walk.advance(s2);
+        Step s3 = s2;  bool has3 = has2 && walk.advance(s3);
+        unsigned m1 = hp.inside_mask(cur.w), m2, m3;
         for (int c = pt; c < p.Cout; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
         // prologue: first tile + first step's weights in the open; the tiles of steps s1 (set 0) and s2 (set 1) in flight
         load_w(cur.w.cg, 0);
         load_affine(cur.w, 0, ic<0>{});
-        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
+        { const float* b = hp.tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
         NM_Q2_WAIT_SET(0, 0, 0);
         NM_Q2_WAIT_W(0);
         fix_affine(ic<0>{});
         store_w(0);
         static_for<NP>([&](auto K) { convert(0, m1, K, ic<0>{}); });
-        m1 = inside_mask(s1.w);
-        load_affine(s1.w, s1.cb, ic<0>{});
-        { const float* b = tile_base(s1.w, s1.cb); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
-        m2 = inside_mask(s2.w);
-        load_affine(s2.w, s2.cb, ic<1>{});
-        { const float* b = tile_base(s2.w, s2.cb); static_for<NP>([&](auto K) { load_piece(b, m2, K, ic<1>{}); }); }
+        m1 = hp.inside_mask(s1.w);
+        load_affine(s1.w, s1.c.cb, ic<0>{});
+        { const float* b = hp.tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
+        m2 = hp.inside_mask(s2.w);
+        load_affine(s2.w, s2.c.cb, ic<1>{});
+        { const float* b = hp.tile_base(s2.w, s2.c.cb); static_for<NP>([&](auto K) { load_piece(b, m2, K, ic<1>{}); }); }
         lds_barrier();
         // one producer iteration = one step of the MFMA waves (`cur`): set SET holds the tile of s1 (converted now into the other
         // halo buffer) and is refilled with the tile of s3; the other set holds s2.  false after the block's last step.
         auto iter = [&](auto SET) -> bool {
             constexpr int set = decltype(SET)::value;
-            m3 = (s3.w.n != s2.w.n || s3.w.oz0 != s2.w.oz0 || s3.w.oy0 != s2.w.oy0 || s3.w.ox0 != s2.w.ox0) ? inside_mask(s3.w) : m2;
-            const float* b3 = tile_base(s3.w, s3.cb);
+            m3 = (s3.w.n != s2.w.n || s3.w.oz0 != s2.w.oz0 || s3.w.oy0 != s2.w.oy0 || s3.w.ox0 != s2.w.ox0) ? hp.inside_mask(s3.w) : m2;
+            const float* b3 = hp.tile_base(s3.w, s3.c.cb);
             // weights of step s1 into the other buffer (read last during the step before this one)
-            load_w(s1.w.cg, s1.cb);
+            load_w(s1.w.cg, s1.c.cb);
             // in order: [tile s1 -> this set][tile s2 -> other set][these NWL weight loads]: this set has landed once only the
             // other set's loads and the weight loads are outstanding
             NM_Q2_WAIT_SET(set, 23, 26);
             fix_affine(SET);
             static_for<NP>([&](auto K) { convert(hb ^ 1, m1, K, SET); load_piece(b3, m3, K, SET); });
-            load_affine(s3.w, s3.cb, SET);
+            load_affine(s3.w, s3.c.cb, SET);
             NM_Q2_WAIT_WP(9, 12);                                   // the weight loads: only this iteration's NP + NA loads are younger
             store_w(hb ^ 1);
             lds_barrier();                                          // publishes tile + weights of s1; the MFMA waves are done with `cur`
-            if (cur.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
+            if (cur.c.cb == C16 - 1) lds_barrier();                   // the MFMA waves' epilogue barrier of a finished brick
             if (!has1) return false;
-            cur = s1; s1 = s2; has1 = has2; s2 = s3; has2 = has3; has3 = has3 && advance(s3);
+            cur = s1; s1 = s2; has1 = has2; s2 = s3; has2 = has3; has3 = has3 && walk.advance(s3);
             m1 = m2; m2 = m3; hb ^= 1;
             return true;
         };
@@ -3189,7 +2797,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
 
-    Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+    Step cur = walk.first();
     int hb = 0;
     lds_barrier();                                                  // the producers' prologue
 
@@ -3197,7 +2805,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
     half8 a0[3], a1[3], b0[3], b1[3];                               // operands of three taps in flight (index = tap % 3)
     for (;;) {
         Step nxt = cur;
-        const bool has_next = advance(nxt);
+        const bool has_next = walk.advance(nxt);
         const unsigned va = (unsigned)(size_t)(ldh + hb * 2 * HV + h * HV + arow0);
         const unsigned vb = (unsigned)(size_t)(ldb + hb * WB + h * 64 + l31);
         // taps 0 and 1 (the tile and the weights were published by the barrier just passed)
@@ -3221,7 +2829,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
         });
         asm volatile("s_barrier" ::: "memory");                     // the producers publish the next step's tile and weights
         __builtin_amdgcn_sched_barrier(0);
-        if (cur.cb == C16 - 1) {
+        if (cur.c.cb == C16 - 1) {
             // ---- epilogue of the finished brick (exposed): transposed accumulators -> 16-byte stores, DPP partial sums
             const Work& w = cur.w;
 #pragma unroll
@@ -3282,7 +2890,8 @@ __global__ __launch_bounds__(512, 1) void conv_f16q2_kernel(ConvParams p) {
 // 27 taps x Cin x 32 outputs x 2 B = 55 KB (Cin = 32) or 110 KB (Cin = 64).  Here they are loaded ONCE per workgroup and stay; the
 // producer waves only stage halo tiles (conv_f16q2's two-register-set pipeline: a tile's loads are issued two steps ahead), one
 // workgroup barrier per 16-channel step, and the MFMA waves keep operands three taps ahead (a tap is two MFMAs here).
-//   LDS: halo [2][h0 | h1][600] x 16 B = 38 KB, weights [27 taps][C16][h0 | h1][32] x 16 B, GroupNorm scratch, bias.
+//   LDS: halo [2][h0 | h1][600] x 16 B = 38 KB, weights [27 taps][C16][h0 | h1][32] x 16 B, GroupNorm scratch, bias (F16rLds<C16T>).
+// The walk is nm_walk::Walk<4, false>; pieces, fix_affine and the packed conversion are conv_f16q2's (HaloPieces, nm_halo_stage.h).
 // k order per output element: channel chunk outer, tap inner (conv_f16q2's); epilogue identical.
 template <int IO, int C16T>
 __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
@@ -3295,42 +2904,17 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
     constexpr int TS = C16T * 64;                                   // half8 slots of one tap: [C16T][h0 | h1][32]
     extern __shared__ f32x4 lds[];
     half8* ldh = reinterpret_cast<half8*>(lds);                     // [2][2][HV]
-    half8* ldb = ldh + 4 * HV;                                      // [27][C16T][2][32]
-    float* red = reinterpret_cast<float*>(ldb + 27 * TS);           // [2 brick parities][4 waves][32 channels][2]
-    float* lbias = red + 512;                                       // [32]
+    half8* ldb = ldh + F16rLds<C16T>::kHaloSlots;                   // [27][C16T][2][32]
+    float* red = reinterpret_cast<float*>(ldb + F16rLds<C16T>::kWeightSlots);   // [2 brick parities][4 waves][32 channels][2]
+    float* lbias = red + F16rLds<C16T>::kRedFloats;                 // [32]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
-    const int nbx = p.OW >> 3, nby = p.OH >> 3, nbz = p.OD >> 2, nbr = nbx * nby * nbz;
-    const int total = p.N * nbr;
-    const int per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int id_first = (int)blockIdx.x * per, id_last = min(total, id_first + per);
-    if (id_first >= id_last) return;
-
-    struct Work { int n, oz0, oy0, ox0; };
-    const bool tiled = p.st_x != 0;
-    auto decode = [&](int id) {
-        Work w;
-        if (tiled) {
-            const BrickPos bp = super_tile_item(p, (int)blockIdx.x, id - id_first, per, nbz, nby, nbx);
-            w.n = bp.n; w.ox0 = bp.bx << 3; w.oy0 = bp.by << 3; w.oz0 = bp.bz << 2;
-            return w;
-        }
-        w.n = id / nbr; const int br = id % nbr;
-        w.ox0 = (br % nbx) << 3; w.oy0 = ((br / nbx) % nby) << 3; w.oz0 = (br / (nbx * nby)) << 2;
-        return w;
-    };
-    auto next_work = [&](Work w, int id) {
-        if (tiled) return decode(id);
-        if ((w.ox0 += 8) == p.OW) { w.ox0 = 0; if ((w.oy0 += 8) == p.OH) { w.oy0 = 0; if ((w.oz0 += 4) == p.OD) { w.oz0 = 0; ++w.n; } } }
-        return w;
-    };
-    struct Step { Work w; int id, cb; };
-    auto advance = [&](Step& st) {                                  // false (and st unchanged) on the block's last step
-        if (st.cb + 1 < C16T) { ++st.cb; return true; }
-        if (st.id + 1 >= id_last) return false;
-        st.cb = 0; ++st.id; st.w = next_work(st.w, st.id);
-        return true;
-    };
+    using Walk = nm_walk::Walk<4, false>;                           // nm_brick_walk.h: the stream of steps (brick, 16-channel chunk) of this workgroup
+    using Work = typename Walk::Work;
+    using Step = typename Walk::Step;
+    const Walk walk(p.st, p.N, p.OD, p.OH, p.OW, 1, C16T, (int)blockIdx.x, (int)gridDim.x);
+    if (walk.items <= 0) return;
+    const int nbx = walk.nbx, nby = walk.nby, nbr = walk.nbr;
 
     if (wave >= 4) {
         // =========================== producer waves ===========================================================
@@ -3340,116 +2924,47 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
         // the layer's weights, once: 1-KiB pieces (tap t, chunk cb) = the hi planes of both lane halves x 32 outputs
         for (int j = pw; j < 27 * C16T; j += 4) ldb[j * 64 + lane] = w8[((size_t)j * 4 + (lane >> 5)) * plane + (lane & 31)];
         for (int c = pt; c < 32; c += 256) lbias[c] = p.bias ? p.bias[c] : 0.f;
-        const int sub = IH ? (pt & 1) : (pt & 3);
-        int pc_slot[NP], pc_rel[NP], pc_pos[NP];
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int v = IH ? (pt >> 1) + 128 * k : (pt >> 2) + 64 * k, vc = min(v, HV - 1);
-            const int hz = vc / 100, r = vc % 100, hy = r / 10, hx = r % 10;
-            pc_slot[k] = (IH ? sub : (sub >> 1)) * HV + hz * ZP + hy * HX + hx;
-            pc_rel[k] = ((hz * p.IH + hy) * p.IW + hx) * p.Cin + NCH * sub;
-            pc_pos[k] = (v < HV) ? (hz | (hy << 8) | (hx << 16)) : -1;
-        }
+        const HaloPieces<NP, HV, NCH, EB, ConvParams> hp(pt, p);       // this thread's pieces of a halo tile (nm_halo_stage.h)
         f32x4 raw[2][NP], sc[2][NA / 2], sh[2][NA / 2];
-        const bool has_affine = p.in_scale != nullptr;
-        const unsigned rel111 = (unsigned)(((p.IH + 1) * p.IW + 1) * p.Cin) * EB;   // halo voxel (1,1,1): always inside
-        auto inside_mask = [&](const Work& w) {
-            unsigned m = 0;
-#pragma unroll
-            for (int k = 0; k < NP; ++k) {
-                const int hz = pc_pos[k] & 0xff, hy = (pc_pos[k] >> 8) & 0xff, hx = pc_pos[k] >> 16;
-                const bool in = pc_pos[k] >= 0 && (unsigned)(w.oz0 - 1 + hz) < (unsigned)p.ID && (unsigned)(w.oy0 - 1 + hy) < (unsigned)p.IH &&
-                                (unsigned)(w.ox0 - 1 + hx) < (unsigned)p.IW;
-                m |= (in ? 1u : 0u) << k;
-            }
-            return m;
-        };
-        auto tile_base = [&](const Work& w, int cb) {
-            return nm_eptr(p.in, (size_t)(((((long long)w.n * p.ID + (w.oz0 - 1)) * p.IH + (w.oy0 - 1)) * p.IW + (w.ox0 - 1)) * (long long)p.Cin + cb * 16), IH);
-        };
-        auto load_piece = [&](const float* base, unsigned mask, auto K, auto SET) {
-            constexpr int k = decltype(K)::value, set = decltype(SET)::value;
-            raw[set][k] = load16_untracked(base, ((mask >> k) & 1) ? (unsigned)pc_rel[k] * EB : rel111);
-        };
-        auto load_affine = [&](const Work& w, int cb, auto SET) {   // always NA loads: the waits below count instructions
-            constexpr int set = decltype(SET)::value;
-            const float* ps = has_affine ? p.in_scale + (size_t)w.n * p.Cin + cb * 16 : p.in;
-            const float* ph = has_affine ? p.in_shift + (size_t)w.n * p.Cin + cb * 16 : p.in;
-#pragma unroll
-            for (int q = 0; q < NA / 2; ++q) {
-                sc[set][q] = load16_untracked(ps, 4u * (unsigned)(NCH * sub + 4 * q));
-                sh[set][q] = load16_untracked(ph, 4u * (unsigned)(NCH * sub + 4 * q));
-            }
-        };
-        auto fix_affine = [&](auto SET) {
-            constexpr int set = decltype(SET)::value;
-            if (!has_affine) {
-#pragma unroll
-                for (int q = 0; q < NA / 2; ++q) { sc[set][q] = f32x4{1.f, 1.f, 1.f, 1.f}; sh[set][q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            }
-        };
-        auto convert = [&](int buf, unsigned mask, auto K, auto SET) {   // activate, round to fp16, write piece k into halo buffer buf
-            constexpr int k = decltype(K)::value, set = decltype(SET)::value;
-            const bool keep = ((mask >> k) & 1) != 0;               // padding is zero AFTER the activation: selected on the packed halves
-            unsigned pk[NCH / 2];
-#pragma unroll
-            for (int e = 0; e < NCH; e += 2) {
-                float v0, v1;
-                if constexpr (IH) { const float rf = raw[set][k][e >> 1]; const unsigned u = nm_fbits(rf); v0 = nm_bf_lo(u); v1 = nm_bf_hi(u); }
-                else { v0 = raw[set][k][e]; v1 = raw[set][k][e + 1]; }
-                f32x2 vv = f32x2{v0, v1};
-                const f32x4 sq = sc[set][e >> 2], hq = sh[set][e >> 2];
-                const f32x2 s2 = (e & 2) ? f32x2{sq[2], sq[3]} : f32x2{sq[0], sq[1]}, h2 = (e & 2) ? f32x2{hq[2], hq[3]} : f32x2{hq[0], hq[1]};
-                vv = __builtin_elementwise_fma(vv, s2, h2);
-                const f32x2 vs = vv * f32x2{p.in_slope, p.in_slope};
-                vv = f32x2{fmaxf(vv[0], vs[0]), fmaxf(vv[1], vs[1])};
-                half2v hv = __builtin_convertvector(vv, half2v);
-                asm volatile("" : "+v"(hv));
-                pk[e >> 1] = keep ? __builtin_bit_cast(unsigned, hv) : 0u;
-            }
-            if (pc_pos[k] >= 0) {
-                if constexpr (IH) {
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    *reinterpret_cast<u32x4*>(ldh + buf * 2 * HV + pc_slot[k]) = u32x4{pk[0], pk[1], pk[2], pk[3]};
-                } else {
-                    reinterpret_cast<nm_u32x2*>(ldh + buf * 2 * HV + pc_slot[k])[sub & 1] = nm_u32x2{pk[0], pk[1]};
-                }
-            }
-        };
+        // loads and conversion of piece k of register set SET: nm_halo_stage.h, on this kernel's registers
+        auto load_piece = [&](const float* base, unsigned mask, auto K, auto SET) { hp.load_piece(raw[decltype(SET)::value][decltype(K)::value], base, mask, K); };
+        auto load_affine = [&](const Work& w, int cb, auto SET) { hp.load_affine(sc[decltype(SET)::value], sh[decltype(SET)::value], w.n, cb); };   // always NA loads: the waits below count instructions
+        auto fix_affine = [&](auto SET) { hp.fix_affine(sc[decltype(SET)::value], sh[decltype(SET)::value]); };
+        auto convert = [&](int buf, unsigned mask, auto K, auto SET) { hp.convert_packed(ldh + buf * 2 * HV, raw[decltype(SET)::value][decltype(K)::value], sc[decltype(SET)::value], sh[decltype(SET)::value], mask, K); };
 
-        Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+        Step cur = walk.first();
         int hb = 0;                                                 // halo buffer of the step the MFMA waves run
-        Step s1 = cur; bool has1 = advance(s1);
-        Step s2 = s1;  bool has2 = has1 && advance(s2);
-        Step s3 = s2;  bool has3 = has2 && advance(s3);
-        unsigned m1 = inside_mask(cur.w), m2, m3;
+        Step s1 = cur; bool has1 = walk.advance(s1);
+        Step s2 = s1;  bool has2 = has1 && walk.advance(s2);
+        Step s3 = s2;  bool has3 = has2 && walk.advance(s3);
+        unsigned m1 = hp.inside_mask(cur.w), m2, m3;
         // prologue: first tile in the open; the tiles of steps s1 (set 0) and s2 (set 1) in flight
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (the weight loads above are the compiler's)
         load_affine(cur.w, 0, ic<0>{});
-        { const float* b = tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
+        { const float* b = hp.tile_base(cur.w, 0); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
         NM_Q2_WAIT_SET(0, 0, 0);
         fix_affine(ic<0>{});
         static_for<NP>([&](auto K) { convert(0, m1, K, ic<0>{}); });
-        m1 = inside_mask(s1.w);
-        load_affine(s1.w, s1.cb, ic<0>{});
-        { const float* b = tile_base(s1.w, s1.cb); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
-        m2 = inside_mask(s2.w);
-        load_affine(s2.w, s2.cb, ic<1>{});
-        { const float* b = tile_base(s2.w, s2.cb); static_for<NP>([&](auto K) { load_piece(b, m2, K, ic<1>{}); }); }
+        m1 = hp.inside_mask(s1.w);
+        load_affine(s1.w, s1.c.cb, ic<0>{});
+        { const float* b = hp.tile_base(s1.w, s1.c.cb); static_for<NP>([&](auto K) { load_piece(b, m1, K, ic<0>{}); }); }
+        m2 = hp.inside_mask(s2.w);
+        load_affine(s2.w, s2.c.cb, ic<1>{});
+        { const float* b = hp.tile_base(s2.w, s2.c.cb); static_for<NP>([&](auto K) { load_piece(b, m2, K, ic<1>{}); }); }
         lds_barrier();
         // one producer iteration = one step of the MFMA waves (`cur`): set SET holds the tile of s1 (converted now into the other
         // halo buffer) and is refilled with the tile of s3; the other set holds s2.  false after the block's last step.
         auto iter = [&](auto SET) -> bool {
             constexpr int set = decltype(SET)::value;
-            m3 = (s3.w.n != s2.w.n || s3.w.oz0 != s2.w.oz0 || s3.w.oy0 != s2.w.oy0 || s3.w.ox0 != s2.w.ox0) ? inside_mask(s3.w) : m2;
-            const float* b3 = tile_base(s3.w, s3.cb);
+            m3 = (s3.w.n != s2.w.n || s3.w.oz0 != s2.w.oz0 || s3.w.oy0 != s2.w.oy0 || s3.w.ox0 != s2.w.ox0) ? hp.inside_mask(s3.w) : m2;
+            const float* b3 = hp.tile_base(s3.w, s3.c.cb);
             NM_Q2_WAIT_SET(set, 9, 12);                             // only the other set's NP + NA loads are younger
             fix_affine(SET);
             static_for<NP>([&](auto K) { convert(hb ^ 1, m1, K, SET); load_piece(b3, m3, K, SET); });
-            load_affine(s3.w, s3.cb, SET);
+            load_affine(s3.w, s3.c.cb, SET);
             lds_barrier();                                          // publishes the tile of s1; the MFMA waves are done with `cur`
             if (!has1) return false;
-            cur = s1; s1 = s2; has1 = has2; s2 = s3; has2 = has3; has3 = has3 && advance(s3);
+            cur = s1; s1 = s2; has1 = has2; s2 = s3; has2 = has3; has3 = has3 && walk.advance(s3);
             m1 = m2; m2 = m3; hb ^= 1;
             return true;
         };
@@ -3482,7 +2997,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[st][mt][r] = 0.f;
 
-    Step cur; cur.w = decode(id_first); cur.id = id_first; cur.cb = 0;
+    Step cur = walk.first();
     int hb = 0;
     lds_barrier();                                                  // the producers' prologue (weights, bias, first tile)
 
@@ -3499,7 +3014,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
     // into 8-byte slots behind the bias that nobody reads (no exec-mask branch inside the tap loop)
     // (`red` is double buffered by brick parity: the row of brick k is read - part_row, by wave 0 - while the other waves may already be
     //  storing the sums of brick k + 1 when a brick has only two steps)
-    unsigned rbase = l31 == 16 ? (unsigned)(size_t)red + (unsigned)((wave * 32 + 4 * h) * 8) : (unsigned)(size_t)(lbias + 32) + (unsigned)tid * 8u;
+    unsigned rbase = l31 == 16 ? (unsigned)(size_t)red + (unsigned)((wave * 32 + 4 * h) * 8) : (unsigned)(size_t)(lbias + 32) + (unsigned)tid * (unsigned)F16rTail::kLane;
     asm volatile("" : "+v"(rbase));
     unsigned rcur = rbase;
     int rpar = 0;
@@ -3540,7 +3055,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
         if (p.part && tid < 32) {
             float a = 0.f, b = 0.f;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { a += red[rpar * 256 + (q * 32 + tid) * 2]; b += red[rpar * 256 + (q * 32 + tid) * 2 + 1]; }
+            for (int q = 0; q < 4; ++q) { a += red[rpar * (F16rTail::kParity / 4) + (q * 32 + tid) * 2]; b += red[rpar * (F16rTail::kParity / 4) + (q * 32 + tid) * 2 + 1]; }
             const int br = ((pw.oz0 >> 2) * nby + (pw.oy0 >> 3)) * nbx + (pw.ox0 >> 3);
             float* dp = p.part + (((size_t)pw.n * nbr + br) * p.Cout + tid) * 2;
             dp[0] = a; dp[1] = b;
@@ -3552,7 +3067,7 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
         if constexpr (PH != 0) load_bias(ic<2 * (PH == 2 ? 1 : 0)>{});
         const unsigned va = (unsigned)(size_t)(ldh + hb * 2 * HV + h * HV + arow0);
         unsigned vbz[3];
-        vbz[0] = (unsigned)(size_t)(ldb + cur.cb * 64 + h * 32 + l31);
+        vbz[0] = (unsigned)(size_t)(ldb + cur.c.cb * 64 + h * 32 + l31);
         vbz[1] = vbz[0] + 9 * TS * 16; vbz[2] = vbz[0] + 18 * TS * 16;
         a0[0] = lds_read16_untracked<0>(va);  a1[0] = lds_read16_untracked<YO>(va);      b0[0] = lds_read16_untracked<0>(vbz[0]);
         a0[1] = lds_read16_untracked<16>(va); a1[1] = lds_read16_untracked<16 + YO>(va); b0[1] = lds_read16_untracked<TS * 16>(vbz[0]);
@@ -3588,16 +3103,16 @@ __global__ __launch_bounds__(512, 1) void conv_f16r_kernel(ConvParams p) {
     };
     for (;;) {
         Step nxt = cur;
-        const bool has_next = advance(nxt);
-        const int ph = pend ? (cur.cb == 0 ? 1 : (cur.cb == 1 ? 2 : 0)) : 0;
+        const bool has_next = walk.advance(nxt);
+        const int ph = pend ? (cur.c.cb == 0 ? 1 : (cur.c.cb == 1 ? 2 : 0)) : 0;
         if (aset == 0) { if (ph == 0) run_step(ic<0>{}, ic<0>{}); else if (ph == 1) run_step(ic<0>{}, ic<1>{}); else run_step(ic<0>{}, ic<2>{}); }
         else           { if (ph == 0) run_step(ic<1>{}, ic<0>{}); else if (ph == 1) run_step(ic<1>{}, ic<1>{}); else run_step(ic<1>{}, ic<2>{}); }
         asm volatile("s_barrier" ::: "memory");                     // the producers publish the next step's tile
         __builtin_amdgcn_sched_barrier(0);
         if (ph == 2) { part_row(); pend = false; }
-        if (cur.cb == C16T - 1) {
+        if (cur.c.cb == C16T - 1) {
             pend = true; pw = cur.w; aset ^= 1;
-            rpar ^= 1; rcur = rbase + (unsigned)rpar * 1024u;
+            rpar ^= 1; rcur = rbase + (unsigned)rpar * (unsigned)F16rTail::kParity;
             obrick = ((((size_t)pw.n * p.OD + pw.oz0) * p.OH + pw.oy0) * p.OW + pw.ox0) * (size_t)p.Cout;
         }
         if (!has_next) break;
@@ -3692,27 +3207,6 @@ int launch_t(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) {
     return nm_check_hip(hipGetLastError(), "conv_mfma launch");
 }
 
-// XCD super-tile (see super_tile_item): the persistent grid must be 8 x (bricks per super-tile) workgroups, the brick grid
-// a multiple of the super-tile, and the super-tiles split evenly over the eight XCDs
-void choose_super_tile(ConvParams& p, int nblocks, int nbz, int nby, int nbx) {
-    p.st_z = p.st_y = p.st_x = 0;
-    p.st_sx = p.st_sy = p.st_pf = p.st_m_sx = p.st_m_sy = p.st_m_pf = 0;
-    if (nblocks % 8) return;
-    const int gs = nblocks / 8;
-    const int sz = gs == 64 ? 4 : gs == 32 ? 2 : 0;
-    if (!sz || nbz % sz || nby % 4 || nbx % 4) return;
-    const long long st = (long long)p.N * (nbz / sz) * (nby / 4) * (nbx / 4);
-    if (st % 8 || st / 8 * nblocks != (long long)p.N * nbz * nby * nbx) return;
-    p.st_z = sz; p.st_y = 4; p.st_x = 4;
-    // the decode's divisions as multiplications (super_tile_item): exact while (largest dividend) x (divisor) < 2^32
-    const unsigned SX = (unsigned)nbx / 4u, SY = (unsigned)nby / 4u, pf = SX * SY * (unsigned)(nbz / sz);
-    const unsigned long long smax = 8ull * (unsigned long long)(((long long)p.N * nbz * nby * nbx + nblocks - 1) / nblocks) + 8ull;
-    auto magic = [](unsigned d) { return d == 1u ? 0u : (unsigned)((0x100000000ull + d - 1ull) / d); };
-    if (smax * pf < 0x100000000ull) {
-        p.st_sx = SX; p.st_sy = SY; p.st_pf = pf; p.st_m_sx = magic(SX); p.st_m_sy = magic(SY); p.st_m_pf = magic(pf);
-    }
-}
-
 // conv mode 3 (nm_ls().single): the split-fp16 kernels keep only the hi x hi product (SINGLE instantiations)
 
 template <int MT, int NT, int KS, bool UP2, bool SINGLE, int IO = 0>
@@ -3721,7 +3215,7 @@ int launch_f16s_impl(const ConvParams& p_in, const Tiling& t, dim3 grid, hipStre
     static NmDeviceOnce attr_set;
     if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_f16s)", &conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>)) return rc;
     dim3 pgrid(min(grid.x, 512u), grid.y);                          // persistent: ~2 resident workgroups per CU
-    choose_super_tile(p, (int)pgrid.x, p.nbz, p.nby, p.nbx);
+    p.st = nm_walk::choose_super_tile(p.N, (int)pgrid.x, p.nbz, p.nby, p.nbx);
     NmProfScope prof(s, conv_flops(p, (double)p.ks * p.ks * p.ks), UP2 ? 10 + (NT - 1) : 5 + (NT - 1));      // the fused-upsample layers are families of their own
     hipLaunchKernelGGL((conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>), pgrid, dim3(256), t.lds_bytes, s, p);
     return nm_check_hip(hipGetLastError(), "conv_f16s launch");
@@ -3785,7 +3279,7 @@ int launch_persistent(const char* what_attr, const char* what_launch, int varian
     ConvParams p = p_in;
     const int wgs = wgs_cap > 0 && wgs_cap < cus ? min(cus, max(8, wgs_cap & ~7)) : cus;
     dim3 grid((unsigned)min(work_items, wgs));
-    if (super_tile) choose_super_tile(p, (int)grid.x, p.OD / BRICK_Z, p.OH / 8, p.OW / 8);
+    if (super_tile) p.st = nm_walk::choose_super_tile(p.N, (int)grid.x, p.OD / BRICK_Z, p.OH / 8, p.OW / 8);
     NmProfScope prof(s, conv_flops(p, 27.0), variant);
     hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds_bytes, s, p);
     return nm_check_hip(hipGetLastError(), what_launch);
@@ -3793,8 +3287,7 @@ int launch_persistent(const char* what_attr, const char* what_launch, int varian
 
 template <bool SINGLE, int IO = 0>
 int launch_f16p_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)3 * 9 * 4 * 32 * 16 + (size_t)(256 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, lds_bytes, work_items, s, wgs_cap);
+    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, F16pLds::bytes(p.Cout), work_items, s, wgs_cap);
 }
 int launch_f16p(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
@@ -3812,21 +3305,19 @@ int launch_f16p8(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap
 }
 
 int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const size_t lds_bytes = (size_t)8 * 600 * 16 + (size_t)2 * 9 * 4 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
-    return launch_persistent<&conv_f16p2_kernel>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
+    return launch_persistent<&conv_f16p2_kernel>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, F16p2Lds::bytes(p.Cout), work_items, s, wgs_cap);
 }
 // the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
 template <int IO>
 int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)2 * 27 * 2 * 64 * 16 + (size_t)(512 + p.Cout) * sizeof(float);
+    const size_t lds_bytes = F16q2Lds::bytes(p.Cout);
     if (lds_bytes > 160 * 1024) { nm_set_error("conv_f16q2: %d output channels exceed the LDS budget", p.Cout); return NM_ERR_UNSUPPORTED; }
     return launch_persistent<&conv_f16q2_kernel<IO>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
 }
 // the one-product modes' kernel for the 32-output-channel layers (conv_f16r_kernel: resident weights); Cin = 16 C16T
 template <int IO, int C16T>
 int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const size_t lds_bytes = (size_t)4 * 600 * 16 + (size_t)27 * C16T * 64 * 16 + (size_t)(512 + 32) * sizeof(float) + 2048 + 256 + 1024;      // (+ the store slots of the lanes that hold no total)
-    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, lds_bytes, work_items, s, wgs_cap);
+    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, F16rLds<C16T>::bytes(32), work_items, s, wgs_cap);
 }
 int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
     const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
@@ -4024,8 +3515,7 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
     p.bz_l2 = t.bz_l2; p.by_l2 = t.by_l2; p.bx_l2 = t.bx_l2; p.nbz = t.nbz; p.nby = t.nby; p.nbx = t.nbx;
     p.cin_real = cin_real > 0 ? cin_real : in.C;
     p.up2 = g.up2 ? 1 : 0;
-    p.st_z = p.st_y = p.st_x = 0;
-    p.st_sx = p.st_sy = p.st_pf = p.st_m_sx = p.st_m_sy = p.st_m_pf = 0;
+    p.st = nm_walk::SuperTile{};
     p.in_alt = in.alt; p.in_map = in.brickmap;
     p.in2 = in.p2; p.in2_scale = in.scale2; p.in2_shift = in.shift2; p.in2_slope = in.slope2;
     p.in_h = in.h; p.out_h = out_h;

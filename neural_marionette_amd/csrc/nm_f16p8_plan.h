@@ -5,11 +5,7 @@
 // tests/cpp/f16p8_barrier_walk.cpp walks both roles with these same functions and compares the sequences.
 #pragma once
 
-#ifdef __HIPCC__
-#define NM_PLAN_FN __host__ __device__ constexpr
-#else
-#define NM_PLAN_FN constexpr
-#endif
+#include "nm_brick_walk.h"
 
 namespace nm_f16p8 {
 
@@ -44,14 +40,9 @@ static_assert(kGroups % 2 == 0, "group g in buffer g & 1 needs an even number of
 static_assert(group_end(6) && group_end(13) && group_end(20) && group_end(26) && !group_end(0) && !group_end(25), "group ends");
 static_assert(piece_first(kGroups) == kPieces, "every piece is dealt to a group");
 
-// position of a role in its workgroup's run of `items` bricks (work items) of C16 chunks each
-struct Cursor { int item, cb; };
-// advances to the next step; false (cursor unchanged) on the run's last step
-NM_PLAN_FN bool next_step(Cursor& c, int items, int C16) {
-    if (c.cb + 1 < C16) { ++c.cb; return true; }
-    if (c.item + 1 >= items) return false;
-    c.cb = 0; ++c.item;
-    return true;
-}
+// position of a role in its workgroup's run of bricks, and the step to the next one: the walk's (nm_brick_walk.h), which the kernel
+// reaches through nm_walk::Walk::advance
+using nm_walk::Cursor;
+using nm_walk::next_step;
 
 }  // namespace nm_f16p8
