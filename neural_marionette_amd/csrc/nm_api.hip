@@ -24,7 +24,7 @@ NmLaunchState::NmLaunchState()
       gnb_apply4(env_int("NM355_GNB_APPLY4", 1)),   // 0: gnb_apply_kernel (one 16-byte item per iteration) for every channel count
       defer_sums(env_int("NM355_DEFER_SUMS", 1)),      // 0: the per-layer gamma / beta / bias gradient sums are launched inside each GroupNorm backward (A/B)
       wgrad_async(env_int("NM355_WGRAD_ASYNC", 1)),    // 0: the weight gradients of the training backward stay in the main stream's chain (A/B)
-      wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: every split-fp16 k3 weight gradient on wgrad16_kernel (VALU transposition) instead of wgrad16z_kernel: the one A/B of the family (w16z_takes)
+      wgrad_tr(env_int("NM355_WGRAD_TR", 1)),       // 0: every split-fp16 k3 weight gradient on wgrad16_kernel (VALU transposition) instead of wgrad16z_kernel: the one A/B of the family (nm_wgrad::plan)
       tail_rank1(env_int("NM355_TAIL_RANK1", 1)),   // 0: the decoder tail's backward materialises its [F][G^3][32] gradient (A/B)
       vrnn_mid(env_int("NM355_VRNN_MID", 1)),          // 0: prior steps as six launches instead of three (A/B)
       vrnn_gemm(env_int("NM355_VRNN_GEMM", 1)),    // 0: one wavefront per output row at every batch size (A/B)
@@ -536,7 +536,10 @@ int nm_op_conv3d_backward(nm_ctx* ctx, const float* in, int32_t N, int32_t D, in
         a = with_h(make_ref(up, nullptr, nullptr, 1.0f, N, FD, FH, FW, Cin_pad), op_oh());
     }
     float* ws = ctx->ws.f(wsf);
-    if ((rc = nm_launch_wgrad(a, dyT, ks, stride, pad, Cin, ws, d_weight, s, nullptr, nm_conv_get_mode() != 0))) return rc;
+    // (NM355_TEST_WGRAD_WS, read per call: the launcher is told that many floats were reserved, at most wsf - its refusal under test)
+    const char* ws_env = std::getenv("NM355_TEST_WGRAD_WS");
+    const size_t ws_told = ws_env ? std::min(wsf, (size_t)std::strtoull(ws_env, nullptr, 10)) : wsf;
+    if ((rc = nm_launch_wgrad(a, dyT, ks, stride, pad, Cin, ws, ws_told, d_weight, s, nullptr, nm_conv_get_mode() != 0))) return rc;
     float* bp = ctx->ws.f((size_t)N * nbb * Cout * 2);
     if ((rc = nm_launch_gnb_partials(dy, dyT, bp, s))) return rc;
     if ((rc = nm_launch_sum_partials(bp, N * nbb, Cout, d_bias, s))) return rc;
@@ -577,7 +580,7 @@ int nm_op_conv5_occ_backward(nm_ctx* ctx, const float* occ, int32_t N, int32_t G
     ctx->ws.release(0);
     TensorRef dyT = with_h(make_ref(dy, nullptr, nullptr, 1.0f, N, G, G, G, Cout), op_oh());
     float* ws = ctx->ws.f(wsf); float* bp = ctx->ws.f((size_t)N * nbb * Cout * 2);
-    if ((rc = nm_launch_wgrad_k5occ(occ, N, G, dyT, ws, d_weight, ctx->stream, sparse_occ))) return rc;
+    if ((rc = nm_launch_wgrad_k5occ(occ, N, G, dyT, ws, wsf, d_weight, ctx->stream, sparse_occ))) return rc;
     if ((rc = nm_launch_gnb_partials(dy, dyT, bp, ctx->stream))) return rc;
     return nm_launch_sum_partials(bp, N * nbb, Cout, d_bias, ctx->stream);
 } catch (...) { return nm_abi_catch("nm_op_conv5_occ_backward"); }
@@ -601,7 +604,7 @@ int nm_op_convT2_backward(nm_ctx* ctx, const float* in, int32_t N, int32_t D, in
     TensorRef a = make_ref(in, in_scale, in_shift, in_slope, N, D, H, W, Cin);
     TensorRef dyT = make_ref(dy, nullptr, nullptr, 1.0f, N, OD, OH, OW, Cout);
     float* ws = ctx->ws.f(wsf);
-    if ((rc = nm_launch_wgrad(dyT, a, 2, 2, 0, Cout, ws, d_weight, s, nullptr, nm_conv_get_mode() != 0))) return rc;       // roles swapped: [Cin][Cout][8] = IODHW
+    if ((rc = nm_launch_wgrad(dyT, a, 2, 2, 0, Cout, ws, wsf, d_weight, s, nullptr, nm_conv_get_mode() != 0))) return rc;       // roles swapped: [Cin][Cout][8] = IODHW
     float* bp = ctx->ws.f((size_t)N * nbb * Cout * 2);
     if ((rc = nm_launch_gnb_partials(dy, dyT, bp, s))) return rc;
     if ((rc = nm_launch_sum_partials(bp, N * nbb, Cout, d_bias, s))) return rc;

@@ -5,11 +5,17 @@
 // ---- weight gradients ------------------------------------------------------------------------------------------------
 // dW[m][c][tap] = sum_{n,v} dy[n, v, m] * act(in)[n, stride*v + tap - pad, c]      (torch OIDHW layout, fp32 MFMA, exact)
 // Both operands are lazy tensors (ConvTranspose3d weight gradients swap the roles: the activated input plays dy).
-// `ws` holds the per-workgroup partial tiles (nm_wgrad_ws_floats), reduced in a fixed order: deterministic, no atomics.
+// One launch plan (nm_wgrad_plan.h) decides each call: which of the seven kernels takes it (wgrad_kernel in its three modes,
+// wgrad_k1_kernel, wgrad16_kernel, wgrad16z_kernel, wgrad16k2_kernel), its grid, LDS bytes and partial-sum slots, and the floats of
+// workspace behind them; a call no kernel takes is refused by the plan.  `ws` holds the per-workgroup partial tiles, reduced in a fixed
+// order: deterministic, no atomics.  nm_wgrad_ws_floats is the largest plan a caller can reach with this geometry (either allow_f16,
+// any operand storage, any pad / input extent); the launcher gets the number the caller reserved (ws_floats) and returns
+// NM_ERR_INTERNAL, before any launch, when its plan needs more.
 size_t nm_wgrad_ws_floats(int N, int OD, int OH, int OW, int M, int Nc, int ks, int stride);
 // mul (optional): device scalar multiplied into the result (dy was read pre-scaled by its inverse, see nm_launch_make_scale);
-// allow_f16: 3x3x3 stride-1 layers whose extents fit the 2x8x8 brick run on the split-fp16 MFMA kernel (fp32-equivalent products)
-int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride, int pad, int cin_real, float* ws,
+// allow_f16: 3x3x3 stride-1 layers whose extents fit the 2x8x8 brick, and k2 s2 layers of whole 8x8 coarse bricks, run on the split-fp16
+// MFMA kernels (fp32-equivalent products)
+int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride, int pad, int cin_real, float* ws, size_t ws_floats,
                     float* dW, hipStream_t s, const float* mul = nullptr, int allow_f16 = 0);
 // first layer (Basic3DBlock k5 on cat[occ, x1, x2, x3], kypt_detector.py:265): the input is rebuilt from the occupancy
 // grid while staging; dW is [Cout][4][5][5][5]
@@ -17,7 +23,8 @@ size_t nm_wgrad_k5occ_ws_floats(int N, int G, int M);
 // sparse_occ: the occupancy is a few per cent dense (per-frame grids): its channel is gathered over the occupied voxels and the
 // coordinate channels take the dense kernel on one frame of frame-summed dy; 0: dense kernel over all frames (the clip-mean grid
 // of the spatio-temporal net is the union of T frames, 15-30 % dense: the gather took 11.7 ms there against 0.5 ms)
-int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, float* dW, hipStream_t s, int sparse_occ = 1);
+// The sparse forms carve ws by nm_wgrad::FirstLayout, which nm_wgrad_k5occ_ws_floats sizes it by.
+int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, size_t ws_floats, float* dW, hipStream_t s, int sparse_occ = 1);
 
 // ---- GroupNorm + LeakyReLU backward ------------------------------------------------------------------------------------
 // y: the raw conv output with its forward scale/shift/slope (lazy tensor);  dA: gradient w.r.t. the activated values.

@@ -14,6 +14,7 @@
 //                        group) coefficients, then dy = c1*dz + c2*y + c3.   HBM-bound.
 //   upsample2_adjoint    adjoint of the trilinear x2 upsampling (gather form, deterministic).  HBM-bound.
 #include "nm_grad.h"
+#include "nm_wgrad_plan.h"
 #include <cstdlib>
 #include <utility>
 
@@ -1882,278 +1883,151 @@ __global__ __launch_bounds__(256) void axpby4_kernel(float* __restrict__ dst, co
 
 int grid_for(size_t work_items) { return (int)min((work_items + 255) / 256, (size_t)(256 * 16)); }
 
-struct WgradPlan { WgradParams p; int mode, m_tiles, slots; size_t lds, ws_floats; };
+// ---- weight gradients: plan (nm_wgrad_plan.h), refuse or launch by the plan's enum, reduce ------------------------------------------
+namespace W = nm_wgrad;
+static_assert(W::ERR_ARG == NM_ERR_ARG && W::ERR_UNSUPPORTED == NM_ERR_UNSUPPORTED, "nm_wgrad_plan.h restates the error codes");
+static_assert(W::w16_lds() == W16_LDS && W::w16z_lds(0) == WZ_LDS + 64 + 256 && W::w16k2_lds(2, false) == w2_lds_bytes(2, false) &&
+              W::w16k2_lds(4, true) == w2_lds_bytes(4, true) && W::K5S_CHUNK_VOXELS == K5S_CHUNK, "nm_wgrad_plan.h restates the kernels' LDS layouts");
 
-// split-fp16 kernel: 3x3x3, stride 1, "same" padding, output extents multiples of the 2 x 8 x 8 brick
-bool wgrad16_eligible(int OD, int OH, int OW, int ks, int stride) {
-    return ks == 3 && stride == 1 && OD % 2 == 0 && OH % 8 == 0 && OW % 8 == 0;
-}
+W::Switches wgrad_switches() { return {nm_ls().wgrad_tr, nm_ls().wgrad_async, nm_conv_single() != 0, nm_ls().store16}; }
 
-// wgrad16z_kernel keeps the per-frame scale / shift rows of its input in LDS (256 B per frame) behind its tiles.  The bound of 96
-// frames is the one its predecessors' larger tiles left room for in the 163840 B (DESIGN_HISTORY.md); at 96 frames wgrad16z asks
-// for 134464 B.  Bfloat16 operands exist on wgrad16z_kernel only, so above that count launch_wgrad16 runs it once per group of at
-// most W16_TAB_FRAMES frames (equal groups: 97 frames are 49 + 48, not 96 + 1), every group on its own range of partial-sum slots.
-#define W16_TAB_FRAMES 96
-// Does wgrad16z_kernel take the call?  The one place that says so: plan_wgrad sizes the partial sums by it and launch_wgrad16 fills
-// them.  It needs a column of at least two bricks (nbz >= 2: the ring of z-planes) and a frame table that fits - or, above
-// W16_TAB_FRAMES frames, bfloat16 operands in the 16-bit storage mode, which run as frame groups.  Everything else is
-// wgrad16_kernel: more than 96 frames of fp32 operands, NM355_WGRAD_TR=0, and a volume one brick deep (2 x 8k x 8k voxels) - no layer
-// of the network has one (cubes whose y and x extents are multiples of 8 have nbz >= 4), only the op-level entry point reaches it.
-bool w16z_takes(int N, int nbz, bool h16) {
-    return nm_ls().wgrad_tr && nbz >= 2 && (N <= W16_TAB_FRAMES || (h16 && nm_ls().store16));
-}
-int w16_group_frames(int N) { const int groups = (N + W16_TAB_FRAMES - 1) / W16_TAB_FRAMES; return (N + groups - 1) / groups; }
-// slots of all groups together: a group has no more workgroups per tile pair than (frame, y, x) columns
-int w16_group_slots(int N, int S, int cols_per_frame) {
-    const int gf = w16_group_frames(N);
-    int slots = 0;
-    for (int f0 = 0; f0 < N; f0 += gf) slots += max(1, min(S, min(gf, N - f0) * cols_per_frame));
-    return slots;
-}
-
-WgradPlan plan_wgrad(int N, int OD, int OH, int OW, int M, int Nc, int ks, int stride, bool k5occ, bool f16 = false) {
-    WgradPlan q;
-    WgradParams& p = q.p;
-    p.ks = ks; p.stride = stride; p.M = M; p.Nc = Nc;
-    q.mode = k5occ ? 2 : (ks == 1 ? 1 : 0);
-    int bz = 4, by = 8, bx = 8;
-    if (f16) {
-        q.mode = 3;
-        p.BZ = 2; p.BY = 8; p.BX = 8; p.nbz = OD / 2; p.nby = OH / 8; p.nbx = OW / 8; p.HZ = 4; p.HY = 10; p.HX = 10;
-        q.m_tiles = (M + 31) / 32; p.n_tiles = (Nc + 31) / 32; p.groups = 27;
-        const int tiles = q.m_tiles * p.n_tiles, total = N * p.nbz * p.nby * p.nbx;
-        // workgroups of a launch: one per CU, or - when the weight gradients run on their own stream beside the main stream's walk
-        // (nm_net.hip conv_bwd) - 224, which leaves 32 CUs to the GroupNorm passes and small kernels of the walk: a whole-CU kernel on
-        // every CU admits nothing beside it until it ends (73.0 -> 71.3 ms per training step; 208: 71.7, 240: 72.9, 192: 72.7; in the
-        // reduced-precision mode 256 stays better: 53.4 vs 53.9).
-        const int wgs = nm_ls().wgrad_async == 1 && !nm_ls().single ? 224 : 256;
-        p.S = max(1, min(total, max(tiles, wgs) / tiles));
-        // wgrad16z_kernel hands out whole (frame, y, x) columns: no more workgroups per tile pair than columns
-        const bool z = w16z_takes(N, p.nbz, false);
-        if (z) p.S = max(1, min(p.S, N * p.nby * p.nbx));
-        q.slots = p.S; q.lds = W16_LDS;
-        // more frames than that, should the operands turn out bfloat16 (the plan does not see them): one wgrad16z launch per frame
-        // group, each with its own slots (launch_wgrad16)
-        int ws_slots = q.slots;
-        if (!z && w16z_takes(N, p.nbz, true)) ws_slots = max(ws_slots, w16_group_slots(N, p.S, p.nby * p.nbx));
-        q.ws_floats = (size_t)ws_slots * tiles * 27 * 1024;
-        return q;
+int refuse_wgrad(const W::Plan& q, const W::Call& c) {
+    switch (q.why) {
+    case W::LDS_TILE: nm_set_error("wgrad: LDS tile of %zu bytes", q.lds); break;
+    case W::BF16_NO_KERNEL: nm_set_error("wgrad: no kernel for bfloat16 operands (in %d, dy %d) with ks=%d mode=%d", c.in_h, c.dy_h, c.ks, (int)q.kernel); break;
+    case W::BF16_WGRAD16: nm_set_error("wgrad16: bfloat16 operands (in %d, dy %d) need conv mode 4, both tensors bfloat16 and the wgrad16z kernel", c.in_h, c.dy_h); break;
+    case W::K1_MIXED_STORAGE: nm_set_error("wgrad_k1: the two tensors must have the same element type (in %d, dy %d)", c.in_h, c.dy_h); break;
+    case W::ITEM_TABLES: nm_set_error("wgrad: brick %dx%dx%d / halo %dx%dx%d beyond the kernel's item tables", q.BZ, q.BY, q.BX, q.HZ, q.HY, q.HX); break;
+    default: nm_set_error("wgrad: ks=%d unsupported", c.ks); break;
     }
-    if (stride == 2) { bz = 2; by = 4; bx = 8; }
-    p.BX = min(bx, (OW + 1) & ~1); p.BY = min(by, OH); p.BZ = min(bz, OD);
-    p.nbx = (OW + p.BX - 1) / p.BX; p.nby = (OH + p.BY - 1) / p.BY; p.nbz = (OD + p.BZ - 1) / p.BZ;
-    p.HZ = (p.BZ - 1) * stride + ks; p.HY = (p.BY - 1) * stride + ks; p.HX = (p.BX - 1) * stride + ks;
-    q.m_tiles = (M + 31) / 32;
-    p.n_tiles = k5occ ? 1 : (Nc + 31) / 32;
-    p.groups = k5occ ? 25 : ks * ks * ks;
-    const int tiles = q.m_tiles * p.n_tiles;
-    const int total = N * p.nbz * p.nby * p.nbx;
-    p.S = max(1, min(total, 512 / tiles));
-    q.slots = q.mode == 1 ? p.S * 4 : p.S;
-    q.lds = ((size_t)p.BZ * p.BY * p.BX * 32 + (size_t)p.HZ * p.HY * p.HX * (k5occ ? 4 : 32)) * sizeof(float);
-    q.ws_floats = (size_t)q.slots * tiles * p.groups * 1024;
-    return q;
+    return q.status;
 }
 
-template <int MODE, int NTW, bool HX = false, bool HD = false>
-int launch_wgrad_t(const WgradPlan& q, hipStream_t s) {
-    {   // the kernel's per-thread item tables: 8 dY items, 20 input items (5 in MODE 2)
-        const int BV = q.p.BZ * q.p.BY * q.p.BX, HV = q.p.HZ * q.p.HY * q.p.HX;
-        if (BV > 256 || (MODE == 2 ? HV > 5 * 256 : HV * 8 > 20 * 256) || q.p.HX > 255 || q.p.HY > 255 || q.p.HZ > 255) {
-            nm_set_error("wgrad: brick %dx%dx%d / halo %dx%dx%d beyond the kernel's item tables", q.p.BZ, q.p.BY, q.p.BX, q.p.HZ, q.p.HY, q.p.HX);
-            return NM_ERR_ARG;
-        }
-    }
+// one launch of kernel K; its dynamic-LDS limit is raised once per device
+template <auto K, typename... A>
+int launch_wgrad_k(const char* what, dim3 grid, int threads, size_t lds, hipStream_t s, A... args) {
     static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad: cannot raise the dynamic LDS limit", &wgrad_kernel<MODE, NTW, HX, HD>)) return rc;
-    hipLaunchKernelGGL((wgrad_kernel<MODE, NTW, HX, HD>), dim3(q.p.S, q.m_tiles * q.p.n_tiles), dim3(256), q.lds, s, q.p);
-    return nm_check_hip(hipGetLastError(), "wgrad launch");
+    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, what, K)) return rc;
+    hipLaunchKernelGGL(K, grid, dim3(threads), lds, s, args...);
+    return nm_check_hip(hipGetLastError(), what);
 }
 
-
-// one wgrad16z launch of p.S workgroups per tile pair; LDS: tiles, X affine table (256 B per frame), dummy item, dY affine table
-int launch_w16z(const WgradParams& p, int tiles, hipStream_t s) {
-    static NmDeviceOnce attr_z;
-    if (int rc = nm_raise_lds_limit(attr_z, 160 * 1024, "wgrad16z: cannot raise the dynamic LDS limit", &wgrad16z_kernel<false, false>,
-                                    &wgrad16z_kernel<true, false>, &wgrad16z_kernel<true, true>)) return rc;
-    const size_t ldsz = WZ_LDS + (size_t)p.in.N * 64 * sizeof(float) + 64 + 256;
-    const dim3 grid(p.S, tiles);
-    if (p.in.h) hipLaunchKernelGGL((wgrad16z_kernel<true, true>), grid, dim3(512), ldsz, s, p);
-    else if (nm_conv_single()) hipLaunchKernelGGL((wgrad16z_kernel<true, false>), grid, dim3(512), ldsz, s, p);
-    else hipLaunchKernelGGL((wgrad16z_kernel<false, false>), grid, dim3(512), ldsz, s, p);
-    return nm_check_hip(hipGetLastError(), "wgrad16z launch");
+// the product form and the operands' storage pick the instantiation (bfloat16 dY comes with bfloat16 X only)
+template <int MT>
+int launch_k2f16_mt(const W::Plan& q, dim3 grid, const WgradParams& p, hipStream_t s) {
+    const char* what = "wgrad16k2 launch";
+    if (!q.single) return launch_wgrad_k<&wgrad16k2_kernel<MT, false, false, false>>(what, grid, q.threads, q.lds, s, p);
+    if (q.hd) return launch_wgrad_k<&wgrad16k2_kernel<MT, true, true, true>>(what, grid, q.threads, q.lds, s, p);
+    if (q.hx) return launch_wgrad_k<&wgrad16k2_kernel<MT, true, true, false>>(what, grid, q.threads, q.lds, s, p);
+    return launch_wgrad_k<&wgrad16k2_kernel<MT, true, false, false>>(what, grid, q.threads, q.lds, s, p);
 }
 
-// q.slots: the partial-sum slots the launch filled (the fixed-order reduce of run_wgrad walks them all)
-int launch_wgrad16(WgradPlan& q, hipStream_t s) {
-    const int N = q.p.in.N, tiles = q.m_tiles * q.p.n_tiles;
-    const bool h16 = q.p.in.h || q.p.dy.h, z = w16z_takes(N, q.p.nbz, h16);
-    // 16-bit storage: both operands bfloat16, on the z-walking kernel only (every layer of >= 32^3 voxels has nbz >= 16)
-    if (h16 && !(q.p.in.h && q.p.dy.h && nm_conv_single() && z)) {
-        nm_set_error("wgrad16: bfloat16 operands (in %d, dy %d) need conv mode 4, both tensors bfloat16 and the wgrad16z kernel", q.p.in.h, q.p.dy.h);
-        return NM_ERR_UNSUPPORTED;
-    }
-    if (z && N > W16_TAB_FRAMES) {
-        // more frames than table rows: one launch per frame group - the group's frames as a tensor of their own (data and scale / shift
-        // rows offset by its first frame), its partials behind those of the groups before it.  Groups and slots in a fixed order, one
-        // reduce over all of them: deterministic, no atomics.
-        const int gf = w16_group_frames(N);
-        const size_t xframe = (size_t)q.p.in.D * q.p.in.H * q.p.in.W * q.p.in.C, dframe = (size_t)q.p.dy.D * q.p.dy.H * q.p.dy.W * q.p.dy.C;
-        int slot0 = 0;
-        for (int f0 = 0; f0 < N; f0 += gf) {
-            WgradParams pz = q.p;
-            const int n = min(gf, N - f0);
-            pz.in.N = pz.dy.N = n;
-            pz.in.p = nm_eptr(q.p.in.p, f0 * xframe, q.p.in.h); pz.dy.p = nm_eptr(q.p.dy.p, f0 * dframe, q.p.dy.h);
-            if (pz.in.scale) { pz.in.scale += (size_t)f0 * pz.in.C; pz.in.shift += (size_t)f0 * pz.in.C; }
-            if (pz.dy.scale) { pz.dy.scale += (size_t)f0 * pz.dy.C; pz.dy.shift += (size_t)f0 * pz.dy.C; }
-            pz.S = max(1, min(q.p.S, n * pz.nby * pz.nbx));
-            pz.part = q.p.part + (size_t)slot0 * tiles * 27 * 1024;
-            if (int rc = launch_w16z(pz, tiles, s)) return rc;
-            slot0 += pz.S;
-        }
-        q.slots = slot0;
-        return NM_OK;
-    }
-    if (z) return launch_w16z(q.p, tiles, s);             // (plan_wgrad bounded S by the column count)
-    static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16: cannot raise the dynamic LDS limit", &wgrad16_kernel<false>, &wgrad16_kernel<true>)) return rc;
-    if (nm_conv_single()) hipLaunchKernelGGL(wgrad16_kernel<true>, dim3(q.p.S, tiles), dim3(256), q.lds, s, q.p);
-    else hipLaunchKernelGGL(wgrad16_kernel<false>, dim3(q.p.S, tiles), dim3(256), q.lds, s, q.p);
-    return nm_check_hip(hipGetLastError(), "wgrad16 launch");
+template <bool H16>
+int launch_k1(const W::Plan& q, dim3 grid, const WgradParams& p, hipStream_t s) {
+    const char* what = "wgrad_k1 launch";
+    if (q.ntw == 1) return launch_wgrad_k<&wgrad_k1_kernel<1, H16>>(what, grid, q.threads, q.lds, s, p, q.m_tiles, q.n_tiles);
+    if (q.ntw == 2) return launch_wgrad_k<&wgrad_k1_kernel<2, H16>>(what, grid, q.threads, q.lds, s, p, q.m_tiles, q.n_tiles);
+    return launch_wgrad_k<&wgrad_k1_kernel<6, H16>>(what, grid, q.threads, q.lds, s, p, q.m_tiles, q.n_tiles);
 }
 
-int run_wgrad(WgradPlan& q, float* ws, float* dW, int cin_real, int taps, hipStream_t s, const float* mul = nullptr) {
-    if (q.lds > 160 * 1024) { nm_set_error("wgrad: LDS tile of %zu bytes", q.lds); return NM_ERR_UNSUPPORTED; }
-    q.p.part = ws;
-    int rc;
-    const bool h16 = q.p.in.h || q.p.dy.h;
-    if (h16 && !(q.mode == 3 || (q.mode == 0 && q.p.ks == 2 && q.p.in.h) || (q.mode == 2 && !q.p.in.h))) {
-        nm_set_error("wgrad: no kernel for bfloat16 operands (in %d, dy %d) with ks=%d mode=%d", q.p.in.h, q.p.dy.h, q.p.ks, q.mode); return NM_ERR_UNSUPPORTED;
+// wgrad16z: one launch per frame group - the group's frames as a tensor of their own (data and scale / shift rows offset by its first
+// frame), its partials behind those of the groups before it.  Groups and slots in a fixed order, one reduce over all of them:
+// deterministic, no atomics.  (Up to W16_TAB_FRAMES frames: one group, the call's own tensors.)
+int launch_w16z(const W::Plan& q, const WgradParams& p, hipStream_t s) {
+    const int tiles = q.m_tiles * q.n_tiles;
+    const size_t xframe = (size_t)p.in.D * p.in.H * p.in.W * p.in.C, dframe = (size_t)p.dy.D * p.dy.H * p.dy.W * p.dy.C;
+    for (int i = 0; i < q.n_groups; ++i) {
+        const W::Group g = q.group(i);
+        WgradParams pz = p;
+        pz.in.N = pz.dy.N = g.frames;
+        pz.in.p = nm_eptr(p.in.p, g.frame0 * xframe, p.in.h); pz.dy.p = nm_eptr(p.dy.p, g.frame0 * dframe, p.dy.h);
+        if (pz.in.scale) { pz.in.scale += (size_t)g.frame0 * pz.in.C; pz.in.shift += (size_t)g.frame0 * pz.in.C; }
+        if (pz.dy.scale) { pz.dy.scale += (size_t)g.frame0 * pz.dy.C; pz.dy.shift += (size_t)g.frame0 * pz.dy.C; }
+        pz.S = g.S;
+        pz.part = p.part + (size_t)g.slot0 * tiles * 27 * 1024;
+        const dim3 grid(g.S, tiles);
+        const size_t lds = W::w16z_lds(g.frames);
+        const char* what = "wgrad16z launch";
+        int rc;
+        if (!q.single) rc = launch_wgrad_k<&wgrad16z_kernel<false, false>>(what, grid, q.threads, lds, s, pz);
+        else if (!q.hx) rc = launch_wgrad_k<&wgrad16z_kernel<true, false>>(what, grid, q.threads, lds, s, pz);
+        else rc = launch_wgrad_k<&wgrad16z_kernel<true, true>>(what, grid, q.threads, lds, s, pz);
+        if (rc) return rc;
     }
+    return NM_OK;
+}
+
+int launch_wgrad_plan(const W::Plan& q, const WgradParams& p, hipStream_t s) {
+    const dim3 grid(q.grid_x, q.grid_y);
+    const char* what = "wgrad launch";
+    switch (q.kernel) {
+    case W::WGRAD16Z: return launch_w16z(q, p, s);
+    case W::WGRAD16:
+        return !q.single ? launch_wgrad_k<&wgrad16_kernel<false>>("wgrad16 launch", grid, q.threads, q.lds, s, p) : launch_wgrad_k<&wgrad16_kernel<true>>("wgrad16 launch", grid, q.threads, q.lds, s, p);
+    case W::WGRAD_FIRST:
+        return q.hd ? launch_wgrad_k<&wgrad_kernel<2, 7, false, true>>(what, grid, q.threads, q.lds, s, p) : launch_wgrad_k<&wgrad_kernel<2, 7>>(what, grid, q.threads, q.lds, s, p);
+    case W::WGRAD_POINT: return launch_wgrad_k<&wgrad_kernel<1, 1>>(what, grid, q.threads, q.lds, s, p);
+    case W::WGRAD_TAPS:
+        if (q.ntw == 2 && q.hx) return q.hd ? launch_wgrad_k<&wgrad_kernel<0, 2, true, true>>(what, grid, q.threads, q.lds, s, p) : launch_wgrad_k<&wgrad_kernel<0, 2, true, false>>(what, grid, q.threads, q.lds, s, p);
+        if (q.ntw == 2) return launch_wgrad_k<&wgrad_kernel<0, 2>>(what, grid, q.threads, q.lds, s, p);
+        return launch_wgrad_k<&wgrad_kernel<0, 7>>(what, grid, q.threads, q.lds, s, p);
+    case W::WGRAD_K1: return !q.hx ? launch_k1<false>(q, grid, p, s) : launch_k1<true>(q, grid, p, s);
+    case W::WGRAD16K2: return q.mt == 2 ? launch_k2f16_mt<2>(q, grid, p, s) : launch_k2f16_mt<4>(q, grid, p, s);
+    }
+    return NM_ERR_INTERNAL;
+}
+
+// plan the call, refuse it or launch its kernel on the partial sums in ws, then the fixed-order reduce into dW
+int run_wgrad(const W::Call& c, const TensorRef& in, const TensorRef& dy, int cin_real, float* ws, size_t ws_floats, float* dW, hipStream_t s, const float* mul = nullptr) {
+    const W::Plan q = W::plan(c, wgrad_switches());
+    if (q.status) return refuse_wgrad(q, c);
+    if (q.ws_floats > ws_floats) { nm_set_error("wgrad: the plan needs %zu floats of workspace, the caller reserved %zu", q.ws_floats, ws_floats); return NM_ERR_INTERNAL; }
+    WgradParams p;
+    p.in = in; p.dy = dy; p.part = ws; p.ks = c.ks; p.stride = c.stride; p.pad = c.pad; p.M = c.M; p.Nc = c.Nc;
+    p.BZ = q.BZ; p.BY = q.BY; p.BX = q.BX; p.nbz = q.nbz; p.nby = q.nby; p.nbx = q.nbx; p.HZ = q.HZ; p.HY = q.HY; p.HX = q.HX;
+    p.S = q.S; p.n_tiles = q.n_tiles; p.groups = q.groups;
+    auto go = [&]() {
+        if (int rc = launch_wgrad_plan(q, p, s)) return rc;
+        return launch_wgrad_reduce(ws, q.slots, q.m_tiles * q.n_tiles, q.n_tiles, q.groups, c.M, cin_real, q.taps, q.k5occ, mul, dW, s);
+    };
+    if (q.kernel == W::WGRAD_K1 || q.kernel == W::WGRAD16K2) return go();
     // (the split-fp16 k3 weight gradients are a profiler family of their own, nm_prof_kernel_name 13: kernel + its fixed-order reduce)
-    NmProfScope prof(s, q.mode == 3 ? 2.0 * q.p.in.N * (double)q.p.dy.D * q.p.dy.H * q.p.dy.W * q.p.M * (double)cin_real * taps : 0.0, 13);
-    if (q.mode == 3) rc = launch_wgrad16(q, s);
-    else if (q.mode == 2) rc = q.p.dy.h ? launch_wgrad_t<2, 7, false, true>(q, s) : launch_wgrad_t<2, 7>(q, s);
-    else if (q.mode == 1) rc = launch_wgrad_t<1, 1>(q, s);
-    else if (q.p.ks == 2 && h16) rc = q.p.dy.h ? launch_wgrad_t<0, 2, true, true>(q, s) : launch_wgrad_t<0, 2, true, false>(q, s);
-    else if (q.p.ks == 2) rc = launch_wgrad_t<0, 2>(q, s);
-    else if (q.p.ks == 3) rc = launch_wgrad_t<0, 7>(q, s);
-    else { nm_set_error("wgrad: ks=%d unsupported", q.p.ks); return NM_ERR_UNSUPPORTED; }
-    if (rc) return rc;
-    return launch_wgrad_reduce(ws, q.slots, q.m_tiles * q.p.n_tiles, q.p.n_tiles, q.p.groups, q.p.M, cin_real, taps, q.mode == 2 ? 1 : 0, mul, dW, s);
+    const bool k3f16 = q.kernel == W::WGRAD16 || q.kernel == W::WGRAD16Z;
+    NmProfScope prof(s, k3f16 ? 2.0 * c.N * (double)c.OD * c.OH * c.OW * c.M * (double)cin_real * q.taps : 0.0, 13);
+    return go();
 }
 
 }  // namespace
 
-#define K1_WGS 512            // (256 / 512 / 1024 workgroups: 2.36 / 1.92 / 1.84 ms per step over the three instantiations - one serial brick chain per workgroup; the reduce grows with it)
-static bool k1_wide_eligible(int OD, int OH, int OW, int M, int Nc, int ks, int stride) {
-    const int m_tiles = (M + 31) / 32, n_tiles = (Nc + 31) / 32;
-    return ks == 1 && stride == 1 && (OD * OH * OW) % 64 == 0 && m_tiles * n_tiles <= 24 && (size_t)64 * (m_tiles * 32 + n_tiles * 32 + 8) * 4 <= 150 * 1024;
-}
-
-// wgrad16k2_kernel: k2 s2 p0 layers whose fine grid is exactly twice the coarse one, whole 8 x 8 coarse (y, x) bricks, <= 128 dY channels
-static bool k2f16_shape_eligible(int OD, int OH, int OW, int M, int ks, int stride) {
-    return ks == 2 && stride == 2 && OH % 8 == 0 && OW % 8 == 0 && OD > 0 && M <= 128;
-}
-static int k2f16_slots(int N, int OD, int OH, int OW, int Nc) {
-    const int n_tiles = (Nc + 31) / 32, total = N * OD * (OH / 8) * (OW / 8);
-    return max(1, min(total, 512 / n_tiles));
-}
-template <int MT, bool SINGLE, bool HX, bool HD>
-static int launch_k2f16_t(const WgradParams& p, dim3 grid, hipStream_t s) {
-    static NmDeviceOnce attr_set;
-    const size_t ldsb = w2_lds_bytes(MT, SINGLE);
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad16k2: cannot raise the dynamic LDS limit", &wgrad16k2_kernel<MT, SINGLE, HX, HD>)) return rc;
-    hipLaunchKernelGGL((wgrad16k2_kernel<MT, SINGLE, HX, HD>), grid, dim3(256), ldsb, s, p);
-    return nm_check_hip(hipGetLastError(), "wgrad16k2 launch");
-}
-// the product form and the operands' storage pick the instantiation (bfloat16 dY comes with bfloat16 X only: nm_launch_wgrad)
-template <int MT>
-static int launch_k2f16_mt(const WgradParams& p, dim3 grid, hipStream_t s) {
-    if (!nm_conv_single()) return launch_k2f16_t<MT, false, false, false>(p, grid, s);
-    if (p.dy.h) return launch_k2f16_t<MT, true, true, true>(p, grid, s);
-    if (p.in.h) return launch_k2f16_t<MT, true, true, false>(p, grid, s);
-    return launch_k2f16_t<MT, true, false, false>(p, grid, s);
-}
-
 size_t nm_wgrad_ws_floats(int N, int OD, int OH, int OW, int M, int Nc, int ks, int stride) {
-    size_t a = plan_wgrad(N, OD, OH, OW, M, Nc, ks, stride, false).ws_floats;
-    if (k1_wide_eligible(OD, OH, OW, M, Nc, ks, stride)) a = max(a, (size_t)K1_WGS * ((M + 31) / 32) * ((Nc + 31) / 32) * 1024);
-    if (wgrad16_eligible(OD, OH, OW, ks, stride)) a = max(a, plan_wgrad(N, OD, OH, OW, M, Nc, ks, stride, false, true).ws_floats);
-    if (k2f16_shape_eligible(OD, OH, OW, M, ks, stride)) a = max(a, (size_t)k2f16_slots(N, OD, OH, OW, Nc) * ((M + 31) / 32) * ((Nc + 31) / 32) * 8 * 1024);
-    return a;
+    return W::reserve_floats(N, OD, OH, OW, M, Nc, ks, stride, wgrad_switches());
 }
-static int k5s_chunks(int G) { return (int)(((size_t)G * G * G + K5S_CHUNK - 1) / K5S_CHUNK); }
-size_t nm_wgrad_k5occ_ws_floats(int N, int G, int M) {
-    const size_t G3 = (size_t)G * G * G;
-    const size_t dense = plan_wgrad(N, G, G, G, M, 4, 5, 1, true).ws_floats;                      // exact-shape fallback (other Cout)
-    const size_t sparse = G3 * M + G3 + 64 + plan_wgrad(1, G, G, G, M, 4, 5, 1, true).ws_floats + (size_t)N * k5s_chunks(G) * 125 * M + 256;
-    return max(dense, sparse);
-}
+size_t nm_wgrad_k5occ_ws_floats(int N, int G, int M) { return W::first_reserve_floats(N, G, M, wgrad_switches()); }
 
-int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride, int pad, int cin_real, float* ws, float* dW,
+int nm_launch_wgrad(const TensorRef& in, const TensorRef& dy, int ks, int stride, int pad, int cin_real, float* ws, size_t ws_floats, float* dW,
                     hipStream_t s, const float* mul, int allow_f16) {
     if (in.C % 4 || dy.C % 4 || in.N != dy.N) { nm_set_error("wgrad: channel counts must be multiples of 4 and frame counts equal"); return NM_ERR_ARG; }
-    const bool f16 = allow_f16 && pad == 1 && wgrad16_eligible(dy.D, dy.H, dy.W, ks, stride) && in.D == dy.D && in.H == dy.H && in.W == dy.W;
-    if (k1_wide_eligible(dy.D, dy.H, dy.W, dy.C, in.C, ks, stride) && pad == 0 && in.D == dy.D && in.H == dy.H && in.W == dy.W) {
-        WgradParams p; p.in = in; p.dy = dy; p.part = ws; p.ks = 1; p.stride = 1; p.pad = 0; p.M = dy.C; p.Nc = in.C;
-        const int m_tiles = (dy.C + 31) / 32, n_tiles = (in.C + 31) / 32, T = m_tiles * n_tiles;
-        const int bricks = in.N * (dy.D * dy.H * dy.W / 64), S = min(bricks, K1_WGS);
-        const size_t ldsb = (size_t)64 * (m_tiles * 32 + 4 + n_tiles * 32 + 4) * sizeof(float);
-        static NmDeviceOnce attr_set;
-        if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "wgrad_k1: cannot raise the dynamic LDS limit", &wgrad_k1_kernel<1>,
-                &wgrad_k1_kernel<2>, &wgrad_k1_kernel<6>, &wgrad_k1_kernel<1, true>, &wgrad_k1_kernel<2, true>, &wgrad_k1_kernel<6, true>)) return rc;
-        if (in.h != dy.h) { nm_set_error("wgrad_k1: the two tensors must have the same element type (in %d, dy %d)", in.h, dy.h); return NM_ERR_UNSUPPORTED; }
-        if (in.h) {
-            if (T <= 4) hipLaunchKernelGGL((wgrad_k1_kernel<1, true>), dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-            else if (T <= 8) hipLaunchKernelGGL((wgrad_k1_kernel<2, true>), dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-            else hipLaunchKernelGGL((wgrad_k1_kernel<6, true>), dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-        } else
-        if (T <= 4) hipLaunchKernelGGL(wgrad_k1_kernel<1>, dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-        else if (T <= 8) hipLaunchKernelGGL(wgrad_k1_kernel<2>, dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-        else hipLaunchKernelGGL(wgrad_k1_kernel<6>, dim3(S), dim3(256), ldsb, s, p, m_tiles, n_tiles);
-        int rc = nm_check_hip(hipGetLastError(), "wgrad_k1 launch");
-        if (rc) return rc;
-        return launch_wgrad_reduce(ws, S, T, n_tiles, 1, dy.C, cin_real, 1, 0, mul, dW, s);
-    }
-    if (allow_f16 && pad == 0 && k2f16_shape_eligible(dy.D, dy.H, dy.W, dy.C, ks, stride) && in.D == 2 * dy.D && in.H == 2 * dy.H && in.W == 2 * dy.W &&
-        (!in.h || in.C % 8 == 0) && (!dy.h || (dy.C % 8 == 0 && in.h)) && (!(in.h || dy.h) || nm_conv_single())) {
-        WgradParams p; p.in = in; p.dy = dy; p.part = ws; p.ks = 2; p.stride = 2; p.pad = 0; p.M = dy.C; p.Nc = in.C;
-        const int m_tiles = (dy.C + 31) / 32, n_tiles = (in.C + 31) / 32;
-        p.n_tiles = n_tiles; p.groups = 8;
-        p.S = k2f16_slots(in.N, dy.D, dy.H, dy.W, in.C);
-        const dim3 grid(p.S, n_tiles);
-        if (int rc = m_tiles <= 2 ? launch_k2f16_mt<2>(p, grid, s) : launch_k2f16_mt<4>(p, grid, s)) return rc;
-        return launch_wgrad_reduce(ws, p.S, m_tiles * n_tiles, n_tiles, 8, dy.C, cin_real, 8, 0, mul, dW, s);
-    }
-    WgradPlan q = plan_wgrad(in.N, dy.D, dy.H, dy.W, dy.C, in.C, ks, stride, false, f16);
-    q.p.in = in; q.p.dy = dy; q.p.pad = pad;
-    return run_wgrad(q, ws, dW, cin_real, ks * ks * ks, s, mul);
+    const W::Call c = {in.N, dy.D, dy.H, dy.W, in.D, in.H, in.W, dy.C, in.C, ks, stride, pad, allow_f16 != 0, in.h != 0, dy.h != 0, false};
+    return run_wgrad(c, in, dy, cin_real, ws, ws_floats, dW, s, mul);
 }
 
-int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, float* dW, hipStream_t s, int sparse_occ) {
+int nm_launch_wgrad_k5occ(const float* occ, int N, int G, const TensorRef& dy, float* ws, size_t ws_floats, float* dW, hipStream_t s, int sparse_occ) {
     if (dy.C % 4 || dy.D != G) { nm_set_error("wgrad_k5occ: bad dy"); return NM_ERR_ARG; }
     TensorRef in; in.p = occ; in.scale = in.shift = nullptr; in.slope = 1.0f; in.N = N; in.D = in.H = in.W = G; in.C = 1;
     const bool sparse = sparse_occ && (dy.C == 32 || dy.C == 64) && !dy.scale && dy.slope == 1.0f;
-    if (!sparse) {
-        WgradPlan q = plan_wgrad(N, G, G, G, dy.C, 4, 5, 1, true);
-        q.p.in = in; q.p.dy = dy; q.p.pad = 2;
-        return run_wgrad(q, ws, dW, 4, 125, s);
-    }
+    if (!sparse) return run_wgrad(W::first_call(N, G, dy.C, dy.h != 0), in, dy, 4, ws, ws_floats, dW, s);
     const size_t G3 = (size_t)G * G * G;
-    const int C = dy.C, chunks = k5s_chunks(G);
-    float* dysum = ws; float* zocc = dysum + G3 * C; float* dense_ws = zocc + ((G3 + 63) & ~(size_t)63);
-    WgradPlan q = plan_wgrad(1, G, G, G, C, 4, 5, 1, true);
-    float* part = dense_ws + ((q.ws_floats + 63) & ~(size_t)63);
+    const W::FirstLayout l = W::first_layout(N, G, dy.C, wgrad_switches());
+    if (l.total > ws_floats) { nm_set_error("wgrad_k5occ: the layout needs %zu floats of workspace, the caller reserved %zu", l.total, ws_floats); return NM_ERR_INTERNAL; }
+    const int C = dy.C, chunks = l.chunks;
+    float* dysum = ws + l.dysum; float* zocc = ws + l.zocc; float* dense_ws = ws + l.dense_ws; float* part = ws + l.part;
     // coordinate channels: one frame holding the sum of dy over the frames, empty occupancy
     hipLaunchKernelGGL(sum_frames4_kernel, dim3(grid_for(G3 * C / 4)), dim3(256), 0, s, dy.p, N, G3 * C / 4, dysum, dy.h);
     int rc = nm_check_hip(hipMemsetAsync(zocc, 0, G3 * sizeof(float), s), "wgrad_k5occ: memset");
     if (rc) return rc;
     TensorRef in1 = in; in1.p = zocc; in1.N = 1;
     TensorRef dy1 = dy; dy1.p = dysum; dy1.N = 1; dy1.h = 0;         // (the frame sum is fp32)
-    q.p.in = in1; q.p.dy = dy1; q.p.pad = 2;
-    if ((rc = run_wgrad(q, dense_ws, dW, 4, 125, s))) return rc;
+    if ((rc = run_wgrad(W::first_call(1, G, C, false), in1, dy1, 4, dense_ws, l.part - l.dense_ws, dW, s))) return rc;
     // occupancy channel: matrix cores over the non-empty bricks (sparse_occ 1, grids that are whole 4x8x8 bricks), else the gather
     if (sparse_occ == 1 && G % 8 == 0) {
         static NmDeviceOnce attr_set;

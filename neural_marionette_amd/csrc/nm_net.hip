@@ -1037,7 +1037,7 @@ float* conv_bwd(Bwd& b, const ConvRec& r, const float* dA, bool need_din, const 
                 b.run(nm_launch_upsample2(in, b.sscratch, s3, h_fine));
                 a = with_h(mk(b.sscratch, in.N, 2 * in.D, 2 * in.H, 2 * in.W, in.C), h_fine);
             }
-            b.run(nm_launch_wgrad(a, dyS, w.ks, r.stride, r.pad, w.Cin, b.sscratch + up_floats, gw, s3, ds.inv(), split ? 1 : 0));
+            b.run(nm_launch_wgrad(a, dyS, w.ks, r.stride, r.pad, w.Cin, b.sscratch + up_floats, wg_floats, gw, s3, ds.inv(), split ? 1 : 0));
             b.run(nm_check_hip(hipEventRecord(b.c->ev_w[slot], s3), "backward: weight-gradient done event"));
             b.slot_busy[slot] = true;
         }
@@ -1059,7 +1059,7 @@ float* conv_bwd(Bwd& b, const ConvRec& r, const float* dA, bool need_din, const 
         //  state_dict's rows are copied out)
         float* gw_all = padded ? b.alloc((size_t)w.Cout * per_row) : gw;
         if (b.live()) {
-            b.run(nm_launch_wgrad(a, dyS, w.ks, r.stride, r.pad, w.Cin, wsb, gw_all, b.s, ds.inv(), split ? 1 : 0));
+            b.run(nm_launch_wgrad(a, dyS, w.ks, r.stride, r.pad, w.Cin, wsb, wg_floats, gw_all, b.s, ds.inv(), split ? 1 : 0));
             if (padded) b.run(nm_check_hip(hipMemcpyAsync(gw, gw_all, (size_t)w.Cout_src * per_row * sizeof(float), hipMemcpyDeviceToDevice, b.s), "backward: copy"));
         }
         b.ws.release(m2);
@@ -1126,14 +1126,15 @@ float* up_bwd(Bwd& b, const UpRec& r, const float* dA) {
     ds.prepare(b, w.wd16 && nm_conv_get_mode() != 0, r.out.N * r.out.C);
     const float* dy = norm_bwd(b, r.out, &w.n, r.fpart, r.nblk, r.chsum, w.key + ".bias", dA, ds.amax);
     const TensorRef dyT = plain(dy, r.out);
-    float* wsb = b.alloc(nm_wgrad_ws_floats(in.N, in.D, in.H, in.W, w.Cin, w.Cout, 2, 2));
+    const size_t wg_floats = nm_wgrad_ws_floats(in.N, in.D, in.H, in.W, w.Cin, w.Cout, 2, 2);
+    float* wsb = b.alloc(wg_floats);
     float* gw = b.grad(w.key + ".weight", (int64_t)w.Cin * w.Cout * 8);
     ConvGeom g; g.ks = 2; g.stride = 2; g.pad = 0; g.OD = in.D; g.OH = in.H; g.OW = in.W; g.Cout = w.Cin; g.Co_pad = w.cd_pad;
     if (b.live()) {
         if (!w.wd) { nm_set_error("detector_backward: weights were not packed for training (nm_ctx_set_training)"); b.rc = NM_ERR_STATE; }
     }
     const TensorRef dyS = ds.apply(b, dyT);
-    if (b.live() && w.wd) b.run(nm_launch_wgrad(dyS, in, 2, 2, 0, w.Cout, wsb, gw, b.s, ds.inv(), ds.amax ? 1 : 0));      // roles swapped: [Cin][Cout][8] = IODHW
+    if (b.live() && w.wd) b.run(nm_launch_wgrad(dyS, in, 2, 2, 0, w.Cout, wsb, wg_floats, gw, b.s, ds.inv(), ds.amax ? 1 : 0));      // roles swapped: [Cin][Cout][8] = IODHW
     if (b.live()) {
         b.run(nm_launch_conv(dyS, w.wd, b.zb, din, g, nullptr, b.s, w.Cout, w.wd16));
         if (ds.inv()) b.run(nm_launch_scale_by(din, numel_of(in), ds.inv(), b.s));
@@ -1171,9 +1172,10 @@ void feature_net_bwd(Bwd& b, const FeatRec& r, const float* dFeat) {
     // first layer: GroupNorm backward, then the weight gradient against cat[occ, coords] rebuilt from the occupancy
     const FeatNetW& w = *r.w;
     const float* dy = norm_bwd(b, r.first, &w.n0, r.fpart0, r.nblk0, r.chsum0, w.c0.key + ".bias", d_first);
-    float* wsb = b.alloc(nm_wgrad_k5occ_ws_floats(r.N, r.G, w.c0.Cout));
+    const size_t wg_floats = nm_wgrad_k5occ_ws_floats(r.N, r.G, w.c0.Cout);
+    float* wsb = b.alloc(wg_floats);
     float* gw = b.grad(w.c0.key + ".weight", (int64_t)w.c0.Cout * 4 * 125);
-    if (b.live()) b.run(nm_launch_wgrad_k5occ(r.occ, r.N, r.G, plain(dy, r.first), wsb, gw, b.s));
+    if (b.live()) b.run(nm_launch_wgrad_k5occ(r.occ, r.N, r.G, plain(dy, r.first), wsb, wg_floats, gw, b.s));
     b.ws.release(m);
 }
 

@@ -107,6 +107,35 @@ def test_conv3d_backward(ctx, case, mode):
     _lib.check(ctx.lib.nm_set_conv_mode(ctx.handle, 1), "set_conv_mode")
 
 
+# need: the plan's ws_floats = slots x tile pairs x tap groups x 1024 (wgrad16z: 2 (frame, y, x) columns x 1 x 27; wgrad16k2: 16 bricks x 6 x 8)
+@pytest.mark.parametrize("case,need", [((32, 32, 3, 1, 1, 8, 2, True, False, 32), 2 * 27 * 1024), ((48, 72, 2, 2, 0, 16, 2, True, False, 48), 16 * 6 * 8 * 1024)],
+                         ids=["wgrad16z", "wgrad16k2"])
+def test_conv3d_backward_refuses_a_short_workspace(ctx, case, need, monkeypatch):
+    """nm_launch_wgrad is told what its caller reserved and refuses, before any launch, a plan that needs more: with the op's figure
+    patched to one float less than the plan's need (NM355_TEST_WGRAD_WS, read per call) the call returns NM_ERR_INTERNAL and leaves the
+    outputs untouched; told exactly the need, and then unpatched, the same context computes the gradients as test_conv3d_backward holds them."""
+    from neural_marionette_amd import _lib
+    Cin, Cout, ks, stride, pad, size, N, _, _, csel = case
+    O = (size + 2 * pad - ks) // stride + 1
+    g = torch.Generator().manual_seed(3)
+    xd = torch.randn(N, size, size, size, Cin, generator=g).cuda()
+    wd = torch.randn(Cout, Cin, ks, ks, ks, generator=g).cuda()
+    dyd = torch.randn(N, O, O, O, Cout, generator=g).cuda()
+    d_w = torch.full(wd.shape, float("nan")).cuda(); d_b = torch.full((Cout,), float("nan")).cuda()
+    monkeypatch.setenv("NM355_TEST_WGRAD_WS", str(need - 1))
+    rc = ctx.lib.nm_op_conv3d_backward(ctx.handle, _lib.ptr(xd), N, size, size, size, Cin, None, None, 1.0, _lib.ptr(wd), Cout, ks, stride, pad, 0,
+                                       _lib.ptr(dyd), None, csel, _lib.ptr(d_w), _lib.ptr(d_b))
+    torch.cuda.synchronize()
+    msg = ctx.lib.nm_last_error().decode()
+    print("rc %d: %s" % (rc, msg))
+    assert rc == _lib.NM_ERR_INTERNAL and "needs %d floats of workspace, the caller reserved %d" % (need, need - 1) in msg
+    assert torch.isnan(d_w).all() and torch.isnan(d_b).all(), "a kernel ran"
+    monkeypatch.setenv("NM355_TEST_WGRAD_WS", str(need))
+    test_conv3d_backward(ctx, case, 1)
+    monkeypatch.delenv("NM355_TEST_WGRAD_WS")
+    test_conv3d_backward(ctx, case, 1)
+
+
 @pytest.mark.parametrize("sparse", [1, 2, 0], ids=["mfma-bricks", "gather", "dense"])
 @pytest.mark.parametrize("Cout,G,N,frac", [(32, 16, 2, False), (64, 12, 3, False), (32, 32, 1, False), (64, 24, 5, True), (32, 40, 3, True),
                                              (48, 16, 2, False)])

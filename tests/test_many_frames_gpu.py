@@ -7,7 +7,7 @@ in the library sit just above what the rest of the suite runs (64 frames per net
   64 / T whole clips, every pass with its own offsets into the table, the keypoints, the features, the first frames, the target, the
   reconstruction and the tail partials; the clip block is enqueued behind the second encoder chunk.
 
-  96 frames (nm_grad.hip, W16_TAB_FRAMES): wgrad16z_kernel keeps a per-frame scale / shift table in LDS; above 96 frames the
+  96 frames (nm_wgrad_plan.h, W16_TAB_FRAMES): wgrad16z_kernel keeps a per-frame scale / shift table in LDS; above 96 frames the
   fp32-storage modes run wgrad16_kernel (as a volume one brick deep does at every frame count), and the 16-bit storage mode (conv
   mode 4) runs wgrad16z_kernel once per group of frames.
 

@@ -27,4 +27,4 @@ def test_every_switch_is_named_by_a_test():
     tests = "\n".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True) if os.path.abspath(p) != me)
     untested = [s for s in switches if not re.search(r"\b%s\b" % s, tests)]
     assert sorted(untested) == sorted(UNTESTED), f"switches no test names: {untested}; allow-list: {sorted(UNTESTED)}"
-    assert len(switches) == 34, switches
+    assert len(switches) == 35, switches
