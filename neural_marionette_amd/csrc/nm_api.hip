@@ -389,10 +389,11 @@ int nm_op_conv3d(nm_ctx* ctx, const float* in, int32_t N, int32_t D, int32_t H, 
     ConvGeom g; g.ks = ks; g.stride = stride; g.pad = pad; g.up2 = up2 ? 1 : 0;
     g.OD = (us * D + 2 * pad - ks) / stride + 1; g.OH = (us * H + 2 * pad - ks) / stride + 1; g.OW = (us * W + 2 * pad - ks) / stride + 1;
     g.Cout = Cout; g.Co_pad = Co_pad;
-    const bool want_up2c = up2 && nm_up2c_eligible(D, H, W, Cin, Cout, ks, stride, pad);
+    const bool want_up2c = up2 && nm_conv_plan::up2c_eligible(nm_conv_switches(), D, H, W, Cin, Cout, ks, stride, pad);
     const size_t wflu = want_up2c ? nm_up2c_weight_floats(Cin, Co_pad) : 0;
     if (want_up2c) g.up2c = reinterpret_cast<const void*>((uintptr_t)256);      // (placeholder while sizing; the real pointer follows)
-    const int nblk = nm_conv_blocks_per_frame(g, Cin_pad);
+    const TensorRef t = with_h(make_ref(in, in_scale, in_shift, in_slope, N, D, H, W, Cin_pad), op_ih());
+    const int nblk = nm_conv_blocks_per_frame(t, g);
     const size_t wfl = nm_packed_weight_floats(ks, Cin_pad, Co_pad);
     const bool want16 = Cin % 8 == 0 && Cin >= 16;
     const size_t wfl16 = want16 ? nm_packed_weight_floats(ks, (Cin + 15) & ~15, Co_pad) : 0;
@@ -409,7 +410,6 @@ int nm_op_conv3d(nm_ctx* ctx, const float* in, int32_t N, int32_t D, int32_t H, 
     if (wp16 && (rc = nm_launch_pack_conv_weight16(weight, Cout, Cin, ks, wp16, Co_pad, ctx->stream))) return rc;
     if (wup && (rc = nm_launch_up2c_compose(weight, Cout, Cin, Co_pad, wup, ctx->stream))) return rc;
     g.up2c = wup;
-    TensorRef t = with_h(make_ref(in, in_scale, in_shift, in_slope, N, D, H, W, Cin_pad), op_ih());
     rc = nm_launch_conv(t, wp, bias, out, g, part, ctx->stream, Cin, wp16, op_oh());
     if (rc) return rc;
     int nblk_used = nblk;
@@ -425,7 +425,7 @@ int nm_op_conv3d(nm_ctx* ctx, const float* in, int32_t N, int32_t D, int32_t H, 
             (void)hipMemset(ctx->nf_flag, 0, sizeof(unsigned));
             nm_conv_set_mode(0);
             ConvGeom g32 = g; g32.up2c = nullptr;
-            nblk_used = nm_conv_blocks_per_frame(g32, Cin_pad);      // (the fp32 kernel's own partial-block layout; never more blocks than sized for)
+            nblk_used = nm_conv_blocks_per_frame(t, g32);      // (the conv mode 0 plan's rows: never more than the first plan's, nm_conv_plan.h)
             rc = nm_launch_conv(t, wp, bias, out, g32, part, ctx->stream, Cin, nullptr);
             nm_conv_set_mode(mode);
             if (rc) return rc;

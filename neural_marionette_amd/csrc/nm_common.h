@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
+#include "nm_conv_plan.h"
 
 #define NM_OK 0
 #define NM_ERR_ARG (-1)
@@ -212,8 +213,10 @@ NmLaunchState& nm_ls();        // the state of the context whose ABI call runs o
 size_t nm_packed_weight_floats(int ks, int Cin_pad, int Co_pad);
 int nm_launch_pack_conv_weight(const float* w_oidhw, int Cout, int Cin, int ks, float* packed,
                                int Cin_pad, int Co_pad, hipStream_t s);
-// number of per-frame partial blocks the conv epilogue writes (for sizing `part`)
-int nm_conv_blocks_per_frame(const ConvGeom& g, int Cin = 16 /* decides the kernel for up2 layers */);
+// the launch switches the forward convs' plan reads (nm_conv_plan.h), from nm_ls()
+nm_conv_plan::Switches nm_conv_switches();
+// GroupNorm partial rows per frame the kernel that nm_launch_conv will choose writes (for sizing `part`): the plan's part_rows
+int nm_conv_blocks_per_frame(const TensorRef& in, const ConvGeom& g);
 int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias, float* out,
                    const ConvGeom& g, float* part /*[N][nblk][Cout][2] or null*/, hipStream_t s,
                    int cin_real = 0 /* un-padded Cin, for the profiler's FLOP count */,
@@ -244,8 +247,6 @@ int nm_launch_conv_k5occ(const float* occ, int N, int G, const float* w_packed, 
                          int Co_pad, float* part, hipStream_t s, unsigned char* brickmap = nullptr, const float* field_part = nullptr,
                          unsigned char* flags = nullptr /* N * bricks bytes of scratch: per-brick occupancy pre-filter of the sparse form */,
                          int out_h = 0 /* 1: `out` is bfloat16 (dense form only) */);
-// true when nm_launch_conv sends a k2 s2 p0 conv of this input to conv_pool_f16s_kernel (the consumer of a brick-sparse tensor)
-bool nm_conv_pool16_eligible(int Cin, int OD, int OH, int OW, bool have_w16);
 void nm_conv_prof_enable(int on, hipStream_t stream);
 int nm_conv_prof_collect(int variant, double* ms_total, double* flops_total, long long* launches);
 void nm_conv_prof_reset();

@@ -1664,32 +1664,12 @@ __global__ __launch_bounds__(256, 2) void conv_pool_f16q_kernel(ConvParams p) {
 }
 
 // ---- the persistent producer / consumer kernels: conv_f16p, _f16p2, _f16p8, _f16q2, _f16r ------------------------------------------
-// What the five share lives in two headers: nm_brick_walk.h (which brick, cout group and channel chunk a workgroup takes in each step:
-// Work, Step, decode, advance; the MFMA waves and the producers walk the same stream) and nm_halo_stage.h (the producers' piece table,
-// inside mask, tile base and conversions).  Each kernel keeps its own schedule: the order of loads, converts, counted waits and barriers.
-// LDS layout of one of them, in this order: halo tiles and weights (16-byte slots), GroupNorm scratch (floats), the bias [Cout], TAIL
-// bytes.  The kernel's pointers and the launcher's byte count both come from here (conv_f16p8: nm_f16p8_plan.h).
-template <int HALO_SLOTS, int WEIGHT_SLOTS, int RED_FLOATS, int TAIL = 0>
-struct PcLds {
-    static constexpr int kHaloSlots = HALO_SLOTS, kWeightSlots = WEIGHT_SLOTS, kRedFloats = RED_FLOATS;
-    static constexpr size_t bytes(int Cout) { return (size_t)(HALO_SLOTS + WEIGHT_SLOTS) * 16 + (size_t)(RED_FLOATS + Cout) * sizeof(float) + TAIL; }
-};
-using F16pLds = PcLds<2 * 4 * 600, 3 * 9 * 4 * 32, 4 * 32 * 2>;     // halo [2][hi h0 | hi h1 | lo h0 | lo h1][600], weights [3][9 taps][4 planes][32], red [4 waves][32][2]
-using F16p2Lds = PcLds<2 * 4 * 600, 2 * 9 * 4 * 64, 4 * 64 * 2>;    // weights [2][9 taps][4 planes][64], red [4 waves][64][2]
-using F16q2Lds = PcLds<2 * 2 * 600, 2 * 27 * 2 * 64, 4 * 64 * 2>;   // halo [2][h0 | h1][600], weights [2][27 taps][h0 | h1][64]
-// conv_f16r's tail, behind the bias: the store slots of the MFMA-wave lanes that hold no total (nobody reads them).  A lane's slot is
-// kLane bytes at tid * kLane, a channel's totals go kChannels' worth of compile-time offsets further, and the parity of the brick moves
-// every store by kParity = one parity of `red`, so that one address register serves the real rows and the dummy slots alike.
-struct F16rTail { static constexpr int kLane = 8, kChannels = 256, kParity = 4 * 32 * 2 * (int)sizeof(float), kBytes = 256 * kLane + kChannels + kParity; };
-static_assert(((15 & 3) + 8 * (15 >> 2)) * 8 + 8 <= F16rTail::kChannels, "the largest channel offset of a totals store (register r = 15) stays inside the span");
-template <int C16T>                                                 // weights [27 taps][C16T][h0 | h1][32], red [2 brick parities][4 waves][32][2]
-using F16rLds = PcLds<2 * 2 * 600, 27 * C16T * 64, 2 * 4 * 32 * 2, F16rTail::kBytes>;
-static_assert(F16rTail::kParity * 2 == F16rLds<2>::kRedFloats * (int)sizeof(float) && F16rTail::kBytes == 2048 + 256 + 1024, "conv_f16r tail");
-// gfx950: 163 840 B of LDS per workgroup.  Cout is a launch parameter of the first three: 512 channels is more than any layer has
-static_assert(F16pLds::bytes(32) == 133248 && F16pLds::bytes(512) <= 160 * 1024, "conv_f16p LDS");
-static_assert(F16p2Lds::bytes(64) == 152832 && F16p2Lds::bytes(512) <= 160 * 1024, "conv_f16p2 LDS");
-static_assert(F16q2Lds::bytes(64) == 151296 && F16q2Lds::bytes(512) <= 160 * 1024, "conv_f16q2 LDS");
-static_assert(F16rLds<2>::bytes(32) == 99200 && F16rLds<4>::bytes(32) == 154496 && F16rLds<4>::bytes(32) <= 160 * 1024, "conv_f16r LDS");
+// What the five share lives in three headers: nm_brick_walk.h (which brick, cout group and channel chunk a workgroup takes in each step:
+// Work, Step, decode, advance; the MFMA waves and the producers walk the same stream), nm_halo_stage.h (the producers' piece table,
+// inside mask, tile base and conversions) and nm_conv_plan.h (the LDS layouts: the kernels' pointers and the plan's byte count both come
+// from PcLds; conv_f16p8: nm_f16p8_plan.h).  Each kernel keeps its own schedule: the order of loads, converts, counted waits and barriers.
+using nm_conv_plan::F16pLds; using nm_conv_plan::F16p2Lds; using nm_conv_plan::F16q2Lds; using nm_conv_plan::F16rTail;
+template <int C16T> using F16rLds = nm_conv_plan::F16rLds<C16T>;
 
 // ---- conv_f16p: k3 s1 p1 split-fp16 conv, one persistent workgroup per CU, MFMA waves + producer waves ---------------
 // conv_f16s runs two independent 4-wave workgroups per CU and leaves the matrix pipe ~50 % idle: staging, the epilogue
@@ -3143,43 +3123,6 @@ __global__ void pack_conv_weight16_kernel(const float* __restrict__ w, int Cout,
     }
 }
 
-struct Tiling { int MT, NT, bz_l2, by_l2, bx_l2, nbz, nby, nbx, KC, HZ, HY, HX, HV, HVp, CVp; size_t lds_bytes; };
-
-Tiling choose_tiling(const ConvGeom& g, int Cin) {
-    Tiling t;
-    const int vox = g.OD * g.OH * g.OW;
-    t.MT = vox >= 256 ? 2 : 1;
-    t.NT = (g.Co_pad % 64 == 0) ? 2 : 1;
-    const int bm_l2 = t.MT == 2 ? 8 : 7;
-    t.bx_l2 = min(3, ceil_log2(g.OW));
-    t.by_l2 = min(3, ceil_log2(g.OH));
-    t.bz_l2 = bm_l2 - t.bx_l2 - t.by_l2;
-    const int BX = 1 << t.bx_l2, BY = 1 << t.by_l2, BZ = min(1 << t.bz_l2, g.OD);
-    t.nbx = (g.OW + BX - 1) / BX; t.nby = (g.OH + BY - 1) / BY; t.nbz = (g.OD + (1 << t.bz_l2) - 1) >> t.bz_l2;
-    t.HX = (min(BX, g.OW) - 1) * g.stride + g.ks;
-    t.HY = (min(BY, g.OH) - 1) * g.stride + g.ks;
-    t.HZ = (BZ - 1) * g.stride + g.ks;
-    t.HV = t.HX * t.HY * t.HZ;
-    t.HVp = t.HV + ((2 - (t.HV & 7)) & 7);
-    t.CVp = 0;
-    if (g.up2) {
-        int cv = ((t.HZ >> 1) + 2) * ((t.HY >> 1) + 2) * ((t.HX >> 1) + 2);
-        t.CVp = cv + ((2 - (cv & 7)) & 7);
-    }
-    // channels staged per pass: 16 by default; more when the halo tile is small (<= 48 KB of LDS in total), 8 when
-    // even 16 do not fit in 72 KB
-    const size_t per16 = (size_t)4 * (t.HVp + t.CVp) * 16;
-    t.KC = (Cin % 16 == 0) ? 16 : 8;
-    if (per16 > 72 * 1024) t.KC = 8;
-    else {
-        int k = (int)((48 * 1024) / per16) * 16;
-        if (k > 16) t.KC = min(k, (Cin + 15) & ~15);
-        if (t.KC > Cin) t.KC = Cin;
-        if (t.KC % 8) t.KC = (Cin % 16 == 0) ? 16 : 8;
-    }
-    t.lds_bytes = max((size_t)(t.KC / 4) * (t.HVp + t.CVp) * 16, (size_t)4 * 64 * 2 * sizeof(float));
-    return t;
-}
 
 // ---- optional live timing of the conv launches (bench.py roofline leg) ---------------------------
 // (records live in the context: NmLaunchState, nm_common.h).  By default only launches on the profiled context's main stream are
@@ -3198,133 +3141,52 @@ hipEvent_t prof_event() {
 // algorithmic work of a conv launch: real channels and taps, no padding
 double conv_flops(const ConvParams& p, double taps) { return 2.0 * p.N * (double)p.OD * p.OH * p.OW * p.Cout * (double)p.cin_real * taps; }
 
-template <int MT, int NT>
-int launch_t(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) {
-    static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv)", &conv_mfma_kernel<MT, NT>)) return rc;
-    NmProfScope prof(s, conv_flops(p, (double)p.ks * p.ks * p.ks), (MT - 1) * 2 + (NT - 1));
-    hipLaunchKernelGGL((conv_mfma_kernel<MT, NT>), grid, dim3(256), t.lds_bytes, s, p);
-    return nm_check_hip(hipGetLastError(), "conv_mfma launch");
-}
+// ---- launching a plan (nm_conv_plan.h) --------------------------------------------------------------------------------------------------
+// A kernel instantiation, with the flag of its raised dynamic-LDS limit (per device)
+using nm_conv_plan::Plan;
+struct ConvEntry { void (*kernel)(ConvParams); NmDeviceOnce lds_raised; };
 
-// conv mode 3 (nm_ls().single): the split-fp16 kernels keep only the hi x hi product (SINGLE instantiations)
-
-template <int MT, int NT, int KS, bool UP2, bool SINGLE, int IO = 0>
-int launch_f16s_impl(const ConvParams& p_in, const Tiling& t, dim3 grid, hipStream_t s) {
-    ConvParams p = p_in;
-    static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_f16s)", &conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>)) return rc;
-    dim3 pgrid(min(grid.x, 512u), grid.y);                          // persistent: ~2 resident workgroups per CU
-    p.st = nm_walk::choose_super_tile(p.N, (int)pgrid.x, p.nbz, p.nby, p.nbx);
-    NmProfScope prof(s, conv_flops(p, (double)p.ks * p.ks * p.ks), UP2 ? 10 + (NT - 1) : 5 + (NT - 1));      // the fused-upsample layers are families of their own
-    hipLaunchKernelGGL((conv_f16s_kernel<MT, NT, KS, UP2, SINGLE, IO>), pgrid, dim3(256), t.lds_bytes, s, p);
-    return nm_check_hip(hipGetLastError(), "conv_f16s launch");
-}
-// 16-bit storage (p.in_h / p.out_h): the instantiations the training path of conv mode 4 needs - k1 layers at >= 32^3 (both tensors
-// bfloat16) and the fused-upsample layer that crosses the storage threshold (fp32 in, bfloat16 out); anything else is rejected
-int io16_unsupported(const char* k, const ConvParams& p) {
-    nm_set_error("%s: no instantiation for bfloat16 input=%d / output=%d in this conv mode / layer shape (16-bit storage needs conv mode 4)", k, p.in_h, p.out_h);
-    return NM_ERR_UNSUPPORTED;
-}
-template <int MT, int NT, int KS, bool UP2>
-int launch_f16s(const ConvParams& p, const Tiling& t, dim3 grid, hipStream_t s) {
-    const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    if (io) {
-        if (!nm_ls().single) return io16_unsupported("conv_f16s", p);
-        if constexpr (KS == 1 && !UP2) { if (io == 3) return launch_f16s_impl<MT, NT, KS, UP2, true, 3>(p, t, grid, s); }
-        if constexpr (KS == 3 && UP2 && NT == 2) { if (io == 2) return launch_f16s_impl<MT, NT, KS, UP2, true, 2>(p, t, grid, s); }
-        return io16_unsupported("conv_f16s", p);
+// The instantiation a plan names.  Conv mode 3 / 4 (Plan::SINGLE): the split-fp16 kernels keep only the hi x hi product.  16-bit storage
+// (Plan::IO, bit 0 bfloat16 input, bit 1 bfloat16 output): the instantiations the training path of conv mode 4 needs - the plan has
+// refused every other combination, so the empty entries are never chosen.
+ConvEntry& conv_entry(const Plan& q) {
+    using namespace nm_conv_plan;
+    const int nt = 2 - q.NT, one = q.SINGLE ? 1 : 0, io3 = q.IO == 3 ? 1 : 0, form = q.IO ? 0 : 2 - one;       // form: bfloat16 | one product | three products
+    switch (q.kernel) {
+    case CONV_F16P: { static ConvEntry e[3] = {{conv_f16p_kernel<true, 3>}, {conv_f16p_kernel<true>}, {conv_f16p_kernel<false>}}; return e[form]; }
+    case CONV_F16Q2: { static ConvEntry e[2] = {{conv_f16q2_kernel<3>}, {conv_f16q2_kernel<0>}}; return e[1 - io3]; }
+    case CONV_POOL_F16S: case CONV_POOL_F16Q: {     // [NT][SINGLE][bfloat16 in and out | bfloat16 in | un-materialised pair | conv_pool_f16q | conv_pool_f16s]
+        static ConvEntry e[2][2][5] = {
+            {{{conv_pool_f16q_kernel<2, true, false, 3>}, {conv_pool_f16q_kernel<2, true, false, 1>}, {conv_pool_f16q_kernel<2, true, true>}, {conv_pool_f16q_kernel<2, true, false>}, {conv_pool_f16s_kernel<2, true>}},
+             {{nullptr}, {nullptr}, {conv_pool_f16q_kernel<2, false, true>}, {conv_pool_f16q_kernel<2, false, false>}, {conv_pool_f16s_kernel<2, false>}}},
+            {{{conv_pool_f16q_kernel<1, true, false, 3>}, {conv_pool_f16q_kernel<1, true, false, 1>}, {conv_pool_f16q_kernel<1, true, true>}, {conv_pool_f16q_kernel<1, true, false>}, {conv_pool_f16s_kernel<1, true>}},
+             {{nullptr}, {nullptr}, {conv_pool_f16q_kernel<1, false, true>}, {conv_pool_f16q_kernel<1, false, false>}, {conv_pool_f16s_kernel<1, false>}}}};
+        return e[nt][1 - one][q.IO == 3 ? 0 : q.IO ? 1 : q.kernel == CONV_POOL_F16S ? 4 : q.IN2 ? 2 : 3];
     }
-    return nm_ls().single ? launch_f16s_impl<MT, NT, KS, UP2, true>(p, t, grid, s) : launch_f16s_impl<MT, NT, KS, UP2, false>(p, t, grid, s);
-}
-
-template <int NT, bool SINGLE>
-int launch_pool_f16s_impl(const ConvParams& p, dim3 grid, hipStream_t s) {
-    const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    // 16-bit storage: the pool convs of the training path (one-product modes, input always bfloat16)
-    if (io && (!SINGLE || p.Cin > 128 || p.in2 || p.in_map || !(io & 1))) return io16_unsupported("conv_pool_f16q", p);
-    NmProfScope prof(s, conv_flops(p, 8.0), 8);
-    if (io) {
-        if constexpr (SINGLE) {
-            if (io == 3) hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, true, false, 3>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, true, false, 1>), grid, dim3(256), 0, s, p);
-        }
-    } else
-    if (nm_ls().pool_q && p.Cin <= 128) {                           // (the affine table holds 128 channels)
-        if (p.in2) hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, SINGLE, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv_pool_f16q_kernel<NT, SINGLE, false>), grid, dim3(256), 0, s, p);
-    } else
-    hipLaunchKernelGGL((conv_pool_f16s_kernel<NT, SINGLE>), grid, dim3(256), 0, s, p);
-    return nm_check_hip(hipGetLastError(), "conv_pool_f16s launch");
-}
-template <int NT>
-int launch_pool_f16s(const ConvParams& p, dim3 grid, hipStream_t s) {
-    return nm_ls().single ? launch_pool_f16s_impl<NT, true>(p, grid, s) : launch_pool_f16s_impl<NT, false>(p, grid, s);
-}
-
-// The persistent producer / consumer kernels (conv_f16p, _f16p2, _f16q2, _f16r: k3 s1 p1 on 4 x 8 x 8 bricks; conv_f16p8 on
-// 8 x 8 x 8 bricks, BRICK_Z = 8: its work items and its super-tile count bricks of that depth; 512 threads): one
-// workgroup per CU, the bricks in XCD super-tile order where a brick is one work item.  wgs_cap > 0 is the cap of THIS launch (nm_launch_conv's argument: a conv that runs
-// beside another stream's chain of small dependent launches leaves it CUs), rounded down to a multiple of 8 so that every XCD keeps
-// the same number of workgroups; a workgroup walks a contiguous run of ceil(items / grid) work items, whatever the grid.  The XCD
-// super-tile exists for grids of 256 and 512 only (choose_super_tile: grid / 8 = 32 or 64), so a capped launch walks its bricks in
-// linear order - part of what the cap costs the capped conv itself.
-template <auto KERNEL, int BRICK_Z = 4>                             // BRICK_Z: z extent of the kernel's brick (conv_f16p8: 8)
-int launch_persistent(const char* what_attr, const char* what_launch, int variant, bool super_tile, const ConvParams& p_in,
-                      size_t lds_bytes, int work_items, hipStream_t s, int wgs_cap) {
-    static NmDeviceOnce attr_set;
-    if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, what_attr, KERNEL)) return rc;
-    const int cus = nm_num_cus();
-    if (!cus) return NM_ERR_HIP;
-    ConvParams p = p_in;
-    const int wgs = wgs_cap > 0 && wgs_cap < cus ? min(cus, max(8, wgs_cap & ~7)) : cus;
-    dim3 grid((unsigned)min(work_items, wgs));
-    if (super_tile) p.st = nm_walk::choose_super_tile(p.N, (int)grid.x, p.OD / BRICK_Z, p.OH / 8, p.OW / 8);
-    NmProfScope prof(s, conv_flops(p, 27.0), variant);
-    hipLaunchKernelGGL(KERNEL, grid, dim3(512), lds_bytes, s, p);
-    return nm_check_hip(hipGetLastError(), what_launch);
-}
-
-template <bool SINGLE, int IO = 0>
-int launch_f16p_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    return launch_persistent<&conv_f16p_kernel<SINGLE, IO>>("hipFuncSetAttribute(conv_f16p)", "conv_f16p launch", 7, p.Cout == 32, p, F16pLds::bytes(p.Cout), work_items, s, wgs_cap);
-}
-int launch_f16p(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    if (io) {                                                       // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients)
-        if (io != 3 || !nm_ls().single) return io16_unsupported("conv_f16p", p);
-        return launch_f16p_impl<true, 3>(p, work_items, s, wgs_cap);
+    case CONV_F16P2: { static ConvEntry e = {conv_f16p2_kernel}; return e; }
+    case CONV_F16P8: { static ConvEntry e = {conv_f16p8_kernel}; return e; }
+    case CONV_F16R: { static ConvEntry e[2][2] = {{{conv_f16r_kernel<3, 2>}, {conv_f16r_kernel<0, 2>}}, {{conv_f16r_kernel<3, 4>}, {conv_f16r_kernel<0, 4>}}}; return e[q.C16T == 4][1 - io3]; }
+    case CONV_F16S: {       // [k3 fused upsample | k3 | k1][NT][form]; bfloat16: the fused-upsample layer that crosses the storage threshold (fp32 in, bfloat16 out), k1 layers at >= 32^3 (both tensors)
+        static ConvEntry e[3][2][3] = {
+            {{{conv_f16s_kernel<2, 2, 3, true, true, 2>}, {conv_f16s_kernel<2, 2, 3, true, true>}, {conv_f16s_kernel<2, 2, 3, true, false>}}, {{nullptr}, {conv_f16s_kernel<2, 1, 3, true, true>}, {conv_f16s_kernel<2, 1, 3, true, false>}}},
+            {{{nullptr}, {conv_f16s_kernel<2, 2, 3, false, true>}, {conv_f16s_kernel<2, 2, 3, false, false>}}, {{nullptr}, {conv_f16s_kernel<2, 1, 3, false, true>}, {conv_f16s_kernel<2, 1, 3, false, false>}}},
+            {{{conv_f16s_kernel<2, 2, 1, false, true, 3>}, {conv_f16s_kernel<2, 2, 1, false, true>}, {conv_f16s_kernel<2, 2, 1, false, false>}}, {{conv_f16s_kernel<2, 1, 1, false, true, 3>}, {conv_f16s_kernel<2, 1, 1, false, true>}, {conv_f16s_kernel<2, 1, 1, false, false>}}}};
+        return e[q.KS == 1 ? 2 : q.UP2 ? 0 : 1][nt][form];
     }
-    return nm_ls().single ? launch_f16p_impl<true>(p, work_items, s, wgs_cap) : launch_f16p_impl<false>(p, work_items, s, wgs_cap);
+    default: { static ConvEntry e[2][2] = {{{conv_mfma_kernel<2, 2>}, {conv_mfma_kernel<2, 1>}}, {{conv_mfma_kernel<1, 2>}, {conv_mfma_kernel<1, 1>}}}; return e[2 - q.MT][nt]; }
+    }
 }
 
-// the 32-output-channel layers on 8 x 8 x 8 bricks (conv_f16p8_kernel); the caller has checked three products, fp32 storage, OD % 8 == 0.
-// Profiler variant 7: the kernel files under the conv_f16p family (all 16 variant slots are taken).
-int launch_f16p8(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    return launch_persistent<&conv_f16p8_kernel, 8>("hipFuncSetAttribute(conv_f16p8)", "conv_f16p8 launch", 7, true, p, (size_t)nm_f16p8::kLdsBytes, work_items, s, wgs_cap);
-}
-
-int launch_f16p2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    return launch_persistent<&conv_f16p2_kernel>("hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch", 9, p.Cout == 64, p, F16p2Lds::bytes(p.Cout), work_items, s, wgs_cap);
-}
-// the one-product modes' own kernel (conv_f16q2_kernel); the caller has checked conv mode 3 / 4
-template <int IO>
-int launch_f16q2_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const size_t lds_bytes = F16q2Lds::bytes(p.Cout);
-    if (lds_bytes > 160 * 1024) { nm_set_error("conv_f16q2: %d output channels exceed the LDS budget", p.Cout); return NM_ERR_UNSUPPORTED; }
-    return launch_persistent<&conv_f16q2_kernel<IO>>("hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch", 14, p.Cout == 64, p, lds_bytes, work_items, s, wgs_cap);
-}
-// the one-product modes' kernel for the 32-output-channel layers (conv_f16r_kernel: resident weights); Cin = 16 C16T
-template <int IO, int C16T>
-int launch_f16r_impl(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    return launch_persistent<&conv_f16r_kernel<IO, C16T>>("hipFuncSetAttribute(conv_f16r)", "conv_f16r launch", 15, true, p, F16rLds<C16T>::bytes(32), work_items, s, wgs_cap);
-}
-int launch_f16p2(const ConvParams& p, int work_items, hipStream_t s, int wgs_cap) {
-    const int io = (p.in_h ? 1 : 0) | (p.out_h ? 2 : 0);
-    // 16-bit storage: both tensors bfloat16 (layers at >= 32^3 and their data gradients), one-product modes only
-    if (io && (io != 3 || !nm_ls().single)) return io16_unsupported("conv_f16p2", p);
-    if (nm_ls().single) return io ? launch_f16q2_impl<3>(p, work_items, s, wgs_cap) : launch_f16q2_impl<0>(p, work_items, s, wgs_cap);
-    return launch_f16p2_impl(p, work_items, s, wgs_cap);
+// the attribute raise, the profiler scope and the launch of a planned kernel (every kernel but the pool kernels asks for dynamic LDS)
+int launch_planned(const Plan& q, const ConvParams& p, hipStream_t s) {
+    static const char* const WHAT[][2] = {{"hipFuncSetAttribute(conv)", "conv_mfma launch"}, {"hipFuncSetAttribute(conv_f16s)", "conv_f16s launch"}, {"", "conv_pool_f16s launch"}, {"", "conv_pool_f16s launch"},
+                                          {"hipFuncSetAttribute(conv_f16p)", "conv_f16p launch"}, {"hipFuncSetAttribute(conv_f16p2)", "conv_f16p2 launch"}, {"hipFuncSetAttribute(conv_f16p8)", "conv_f16p8 launch"},
+                                          {"hipFuncSetAttribute(conv_f16q2)", "conv_f16q2 launch"}, {"hipFuncSetAttribute(conv_f16r)", "conv_f16r launch"}};
+    ConvEntry& e = conv_entry(q);
+    if (q.lds) if (int rc = nm_raise_lds_limit(e.lds_raised, 160 * 1024, WHAT[q.kernel][0], e.kernel)) return rc;
+    NmProfScope prof(s, conv_flops(p, q.taps), q.variant);
+    hipLaunchKernelGGL(e.kernel, dim3((unsigned)q.grid_x, (unsigned)q.grid_y), dim3((unsigned)q.threads), q.lds, s, p);
+    return nm_check_hip(hipGetLastError(), WHAT[q.kernel][1]);
 }
 
 #ifdef NM_DIAG
@@ -3412,24 +3274,18 @@ int nm_launch_pack_conv_weight(const float* w, int Cout, int Cin, int ks, float*
     return nm_check_hip(hipGetLastError(), "pack_conv_weight launch");
 }
 
-static bool use_up2c(const ConvGeom& g, int Cin) {
-    return g.up2 && g.up2c && nm_ls().conv_mode == 1 && nm_up2c_eligible(g.OD / 2, g.OH / 2, g.OW / 2, Cin, g.Cout, g.ks, g.stride, g.pad);
+nm_conv_plan::Switches nm_conv_switches() {
+    const NmLaunchState& l = nm_ls();
+    return {l.conv_mode, l.f16p_all, l.conv_mode && l.single, l.pool_q, l.f16r, l.up2y, l.up2y_march, l.up2y_ypad, l.up2c_shell};
 }
 
-// a k2 s2 p0 conv with tiling t goes to the pool kernels: split-fp16 weights, whole 16-channel chunks, 4 x 8 x 8 output bricks
-static bool pool16_case(const Tiling& t, int Cin, bool have_w16) {
-    return nm_ls().conv_mode == 1 && have_w16 && Cin % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2;
+static nm_conv_plan::Call conv_call(const TensorRef& in, const ConvGeom& g, int cin_real, bool have_w16, int out_h, int wgs_cap, int cus) {
+    return {in.N, in.D, in.H, in.W, in.C, cin_real > 0 ? cin_real : in.C, g.Cout, g.Co_pad, g.ks, g.stride, g.pad, g.up2 != 0, have_w16, g.up2c != nullptr,
+            in.h != 0, out_h != 0, in.p2 != nullptr, in.brickmap != nullptr, in.alt != nullptr, wgs_cap, cus};
 }
 
-bool nm_conv_pool16_eligible(int Cin, int OD, int OH, int OW, bool have_w16) {
-    ConvGeom g; g.ks = 2; g.stride = 2; g.pad = 0; g.OD = OD; g.OH = OH; g.OW = OW; g.Cout = Cin; g.Co_pad = (Cin + 31) & ~31;
-    return pool16_case(choose_tiling(g, Cin), Cin, have_w16);
-}
-
-int nm_conv_blocks_per_frame(const ConvGeom& g, int Cin) {
-    if (use_up2c(g, Cin)) return nm_up2c_blocks_per_frame(g.OD / 2, g.OH / 2, g.OW / 2);
-    Tiling t = choose_tiling(g, 16);
-    return t.nbz * t.nby * t.nbx;
+int nm_conv_blocks_per_frame(const TensorRef& in, const ConvGeom& g) {
+    return nm_conv_plan::plan(conv_call(in, g, 0, false, 0, 0, 256), nm_conv_switches()).part_rows;       // (the rows depend on neither the weights' packs nor the grid)
 }
 
 void nm_conv_prof_enable(int on, hipStream_t stream) {
@@ -3482,8 +3338,12 @@ void nm_conv_prof_reset() {
     l.side_launches = 0;
 }
 
+static_assert(nm_conv_plan::ERR_ARG == NM_ERR_ARG && nm_conv_plan::ERR_UNSUPPORTED == NM_ERR_UNSUPPORTED, "nm_conv_plan.h error codes");
+
+// validate the arguments, plan (nm_conv_plan.h: the routing lives there), refuse or fill ConvParams, launch by the plan's enum
 int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias, float* out,
                    const ConvGeom& g, float* part, hipStream_t s, int cin_real, const void* w_packed16, int out_h, int wgs_cap) {
+    using namespace nm_conv_plan;
     if (in.C % 8 != 0 || g.Co_pad % 32 != 0 || g.Cout > g.Co_pad || g.Cout <= 0) {
         nm_set_error("conv: unsupported channels Cin=%d Cout=%d Co_pad=%d", in.C, g.Cout, g.Co_pad);
         return NM_ERR_ARG;
@@ -3496,113 +3356,41 @@ int nm_launch_conv(const TensorRef& in, const float* w_packed, const float* bias
         return NM_ERR_ARG;
     }
     if ((in.scale == nullptr) != (in.shift == nullptr)) { nm_set_error("conv: scale/shift must come together"); return NM_ERR_ARG; }
-    if ((in.brickmap || in.p2) && g.up2) { nm_set_error("conv: a brick-sparse input tensor can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG; }
-    if (use_up2c(g, in.C)) {
-        // the fused-upsample layers on the coarse grid with composite weights (nm_up2c.hip): main + shell launch, timed together
-        double flops = 2.0 * in.N * (double)g.OD * g.OH * g.OW * g.Cout * (double)(cin_real > 0 ? cin_real : in.C) * 27.0;
-        if (nm_up2y_active()) flops *= 0.5;          // the products conv_up2y_kernel PERFORMS: 4 x 27 per coarse voxel instead of the fine conv's 8 x 27 (halo rows not counted)
-        NmProfScope prof(s, flops, 12);
-        return nm_launch_conv_up2c(in, g.up2c, bias, out, g.Cout, g.Co_pad, part, s, out_h);
+    const int cus = nm_num_cus();
+    if (!cus) return NM_ERR_HIP;
+    const Plan q = plan(conv_call(in, g, cin_real, w_packed16 != nullptr, out_h, wgs_cap, cus), nm_conv_switches());
+    switch (q.why) {
+    case TAKEN: break;
+    case SPARSE_NOT_POOL: nm_set_error("conv: a brick-sparse input tensor can only feed the k2 s2 split-fp16 pool kernel"); return q.status;
+    case IN2_NOT_POOL: nm_set_error("conv: an un-materialised residual sum can only feed the k2 s2 split-fp16 pool kernel"); return q.status;
+    case LDS_TILE: nm_set_error("conv: LDS tile %zu B too large", q.lds); return q.status;
+    case BF16_UP2C: nm_set_error("conv_up2c: 16-bit storage (input %d / output %d) needs conv mode 4", in.h, out_h); return q.status;
+    case BF16_NO_KERNEL:
+        nm_set_error("%s: no instantiation for bfloat16 input=%d / output=%d in this conv mode / layer shape (16-bit storage needs conv mode 4)", kernel_name(q.kernel), in.h, out_h);
+        return q.status;
     }
-    Tiling t = choose_tiling(g, in.C);
-    if (t.lds_bytes > 160 * 1024) { nm_set_error("conv: LDS tile %zu B too large", t.lds_bytes); return NM_ERR_UNSUPPORTED; }
     ConvParams p;
     p.in = in.p; p.in_scale = in.scale; p.in_shift = in.shift; p.in_slope = in.slope;
     p.N = in.N; p.ID = in.D; p.IH = in.H; p.IW = in.W; p.Cin = in.C;
-    p.w = w_packed; p.bias = bias; p.out = out; p.part = part;
+    p.w = q.w_f16 ? static_cast<const float*>(w_packed16) : w_packed; p.bias = bias; p.out = out; p.part = part;
     p.OD = g.OD; p.OH = g.OH; p.OW = g.OW; p.Cout = g.Cout; p.Co_pad = g.Co_pad;
     p.ks = g.ks; p.stride = g.stride; p.pad = g.pad;
-    p.bz_l2 = t.bz_l2; p.by_l2 = t.by_l2; p.bx_l2 = t.bx_l2; p.nbz = t.nbz; p.nby = t.nby; p.nbx = t.nbx;
+    p.bz_l2 = q.bz_l2; p.by_l2 = q.by_l2; p.bx_l2 = q.bx_l2; p.nbz = q.nbz; p.nby = q.nby; p.nbx = q.nbx;
+    p.KC = q.KC; p.HZ = q.HZ; p.HY = q.HY; p.HX = q.HX; p.HV = q.HV; p.HVp = q.HVp; p.CVp = q.CVp; p.ZP = q.ZP;
     p.cin_real = cin_real > 0 ? cin_real : in.C;
     p.up2 = g.up2 ? 1 : 0;
-    p.st = nm_walk::SuperTile{};
+    p.w16 = q.w16 ? w_packed16 : nullptr; p.ksplit = q.ksplit;
+    p.st = q.st;
     p.in_alt = in.alt; p.in_map = in.brickmap;
     p.in2 = in.p2; p.in2_scale = in.scale2; p.in2_shift = in.shift2; p.in2_slope = in.slope2;
     p.in_h = in.h; p.out_h = out_h;
-    if (in.p2 && !(nm_conv_pool16_eligible(in.C, g.OD, g.OH, g.OW, w_packed16 != nullptr) && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2 && !in.brickmap)) {
-        nm_set_error("conv: an un-materialised residual sum can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG;
-    }
-    if (in.brickmap && !(nm_conv_pool16_eligible(in.C, g.OD, g.OH, g.OW, w_packed16 != nullptr) && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2 &&
-                         in.alt && in.D % 4 == 0 && in.H % 8 == 0 && in.W % 8 == 0)) {
-        nm_set_error("conv: a brick-sparse input tensor can only feed the k2 s2 split-fp16 pool kernel"); return NM_ERR_ARG;
-    }
-    p.w16 = (nm_ls().conv_mode == 1 && w_packed16 && in.C % 8 == 0 && !g.up2 && t.MT == 1 && (t.KC % 16 == 0 || t.KC == in.C)) ? w_packed16 : nullptr;
-    if (p.w16) t.lds_bytes = max(t.lds_bytes, (size_t)(((t.KC + 15) & ~15) / 4) * (t.HVp + t.CVp) * 16);
-    p.ksplit = 1;
-    if (p.w16) {       // tiny volumes: how many of the 4 row tiles (32 rows each) of the brick hold voxels at all
-        const int top = ((min(g.OD, 1 << t.bz_l2) - 1) << (t.bx_l2 + t.by_l2)) + ((min(g.OH, 1 << t.by_l2) - 1) << t.bx_l2) + min(g.OW, 1 << t.bx_l2) - 1;
-        const int rw = top / 32 + 1;
-        p.ksplit = rw == 1 ? 4 : (rw == 2 ? 2 : 1);
-        if (p.ksplit > 1) t.lds_bytes = max(t.lds_bytes, (size_t)4 * t.NT * 16 * 64 * sizeof(float));
-    }
 #ifdef NM_DIAG
     p.stamps = g_stamps;
 #endif
-    p.KC = t.KC; p.HZ = t.HZ; p.HY = t.HY; p.HX = t.HX; p.HV = t.HV; p.HVp = t.HVp; p.CVp = t.CVp; p.ZP = t.HY * t.HX;
-    dim3 grid((unsigned)(in.N * t.nbz * t.nby * t.nbx), (unsigned)(g.Co_pad / (t.NT * 32)));
-    if (pool16_case(t, in.C, w_packed16 != nullptr) && g.ks == 2 && g.stride == 2 && g.pad == 0 && !g.up2) {
-        p.w = static_cast<const float*>(w_packed16);
-        return t.NT == 2 ? launch_pool_f16s<2>(p, grid, s) : launch_pool_f16s<1>(p, grid, s);
-    }
-    // the persistent producer / consumer kernels take k3 s1 p1 layers of whole 4 x 8 x 8 bricks, at least four of them along z.
-    // Routing, in this order: Cout % 64 == 0 -> conv_f16p2 (one-product modes: conv_f16q2); Cout == 32 in the one-product modes ->
-    // conv_f16r; Cout == 32 with three products, fp32 storage and OD % 8 == 0 -> conv_f16p8 (8 x 8 x 8 bricks); what is left of
-    // Cout == 32 (OD % 8 == 4, bfloat16 storage, conv_f16r switched off) and conv mode 2's Cout % 32 == 0 -> conv_f16p
-    const bool k3_bricks = w_packed16 && in.C % 16 == 0 && g.ks == 3 && g.stride == 1 && g.pad == 1 && !g.up2 &&
-                           g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16;
-    // (conv_f16q2 keeps a whole step's weights in LDS: a one-product call with more than 1024 output channels - no layer has more
-    // than 256 - goes on to conv_f16s, which has no bfloat16 form for k3)
-    if (nm_ls().conv_mode == 1 && k3_bricks && g.Cout % 64 == 0 && !(nm_ls().single && g.Cout > 1024)) {
-        const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 64);
-        p.w = static_cast<const float*>(w_packed16);
-        return launch_f16p2(p, work, s, wgs_cap);
-    }
-    if (nm_ls().conv_mode == 1 && nm_ls().single && nm_ls().f16r && k3_bricks &&(in.C == 32 || in.C == 64) && g.Cout == 32 &&
-        (p.in_h != 0) == (p.out_h != 0)) {
-        // one-product modes, 32 output channels: the layer's weights stay in LDS (conv_f16r_kernel)
-        const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8);
-        p.w = static_cast<const float*>(w_packed16);
-        if (in.C == 32) return p.in_h ? launch_f16r_impl<3, 2>(p, work, s, wgs_cap) : launch_f16r_impl<0, 2>(p, work, s, wgs_cap);
-        return p.in_h ? launch_f16r_impl<3, 4>(p, work, s, wgs_cap) : launch_f16r_impl<0, 4>(p, work, s, wgs_cap);
-    }
-    // three products, fp32 in and out, exactly 32 output channels, whole 8 x 8 x 8 bricks: conv_f16p8 (twice the MFMAs per staged step;
-    // bit-identical to conv_f16p, which keeps OD % 8 == 4, the one-product / bfloat16 forms and conv mode 2's several cout groups)
-    if (nm_ls().conv_mode == 1 && !nm_ls().single && k3_bricks && g.Cout == 32 && g.OD % 8 == 0 && !p.in_h && !p.out_h) {
-        const int work = in.N * (g.OD / 8) * (g.OH / 8) * (g.OW / 8);
-        p.w = static_cast<const float*>(w_packed16);
-        return launch_f16p8(p, work, s, wgs_cap);
-    }
-    // (with more cout groups per brick conv_f16p re-stages the input per group and measures a little slower than conv_f16s: only
-    // conv mode 2, the parity tests of that path, sends every eligible layer here)
-    if (nm_ls().conv_mode == 1 && k3_bricks && g.Cout % 32 == 0 && (nm_ls().f16p_all || g.Cout == 32)) {
-        const int work = in.N * (g.OD / 4) * (g.OH / 8) * (g.OW / 8) * (g.Cout / 32);
-        p.w = static_cast<const float*>(w_packed16);
-        return launch_f16p(p, work, s, wgs_cap);
-    }
-    if (nm_ls().conv_mode == 1 && w_packed16 && in.C % 16 == 0 && t.MT == 2 && t.bx_l2 == 3 && t.by_l2 == 3 && t.bz_l2 == 2 &&
-        g.stride == 1 && (g.ks == 1 || g.ks == 3) && t.HZ == g.ks + 3 && t.HY * t.HX * 2 <= 256) {
-        // halo planes padded to a pitch of 4 (mod 16) 16-B slots: conflict-free A reads (see conv_f16s_kernel)
-        Tiling t16 = t;
-        const int area = t.HY * t.HX;
-        p.ZP = area + ((4 - (area & 15)) & 15);
-        const int hv = t.HZ * p.ZP;
-        p.HVp = hv + ((2 - (hv & 7)) & 7);
-        const bool blds = (t.NT == 1 && g.ks == 3);
-        const size_t bbytes = blds ? (size_t)2 * 9 * 4 * 32 * 16 : 0;          // two 9-tap weight groups (Cout = 32 layers)
-        t16.lds_bytes = max(blds ? (size_t)4 * p.HVp * 16 + bbytes : (size_t)4 * (p.HVp + t.CVp) * 16, (size_t)4 * 64 * 2 * sizeof(float));
-        if (t16.lds_bytes <= 80 * 1024) {
-            p.w = static_cast<const float*>(w_packed16);
-            if (g.ks == 3 && g.up2) return t.NT == 2 ? launch_f16s<2, 2, 3, true>(p, t16, grid, s) : launch_f16s<2, 1, 3, true>(p, t16, grid, s);
-            if (g.ks == 3) return t.NT == 2 ? launch_f16s<2, 2, 3, false>(p, t16, grid, s) : launch_f16s<2, 1, 3, false>(p, t16, grid, s);
-            if (!g.up2) return t.NT == 2 ? launch_f16s<2, 2, 1, false>(p, t16, grid, s) : launch_f16s<2, 1, 1, false>(p, t16, grid, s);
-        }
-        p.HVp = t.HVp;
-    }
-    if (p.in_h || p.out_h) return io16_unsupported("conv (fp32 MFMA kernel)", p);
-    if (t.MT == 2 && t.NT == 2) return launch_t<2, 2>(p, t, grid, s);
-    if (t.MT == 2 && t.NT == 1) return launch_t<2, 1>(p, t, grid, s);
-    if (t.MT == 1 && t.NT == 2) return launch_t<1, 2>(p, t, grid, s);
-    return launch_t<1, 1>(p, t, grid, s);
+    if (q.kernel != CONV_UP2C) return launch_planned(q, p, s);
+    // the fused-upsample layers on the coarse grid with composite weights (nm_up2c.hip): main + shell launches, timed together
+    NmProfScope prof(s, conv_flops(p, q.taps) * q.flops_factor, q.variant);
+    return nm_launch_conv_up2c(in, g.up2c, bias, out, g.Cout, g.Co_pad, part, s, q.up);
 }
 
 int nm_occ_blocks_per_frame(int G) { return (G / 8) * (G / 8) * (G / 4); }

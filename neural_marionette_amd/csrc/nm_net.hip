@@ -199,7 +199,7 @@ struct Loader {
         w.wup = nullptr;
         // only for the layer shapes conv_up2c takes (the composition is a 27-tap fp64 kernel over 8 x 27 x Cin x Cout items and
         // runs after every optimizer step)
-        if (w.ks != 3 || !nm_up2c_eligible(coarse, coarse, coarse, w.Cin, w.Cout, 3, 1, 1)) return;
+        if (!nm_conv_plan::up2c_eligible(nm_conv_switches(), coarse, coarse, coarse, w.Cin, w.Cout, w.ks, 1, 1)) return;
         const float* src = get(p + ".weight", (int64_t)w.Cout * w.Cin * 27);
         if (!src) return;
         w.wup = nm_ctx_weight_alloc(c, nm_up2c_weight_floats(w.Cin, w.Co_pad));
@@ -357,8 +357,8 @@ TensorRef conv_gn(Net& n, const TensorRef& in, const ConvW& w, const NormW* gn, 
     // layer runs as a plain conv on conv_f16r (resident weights) instead of the composite-weight kernel's one-product instantiation
     // (conv_up2c<.., 3>: 2 x 2.4 ms per step at 0.44 of the time on the matrix pipe, profiles/r05_pmc_mfma_train_bf16.json).
     TensorRef src = in;
-    const bool mat = up2 && rec && n.keep && !out_buf && nm_ls().single && nm_ls().up2_mat && nm_ls().f16r && w.wp16 && w.ks == 3 && stride == 1 && pad == 1 &&
-                     w.Cout == 32 && (in.C == 32 || in.C == 64) && g.OD % 4 == 0 && g.OH % 8 == 0 && g.OW % 8 == 0 && g.OD >= 16;
+    const bool mat = up2 && rec && n.keep && !out_buf && nm_ls().up2_mat &&
+                     nm_conv_plan::k3_on_f16r(nm_conv_switches(), in.C, w.Cout, w.ks, stride, pad, g.OD, g.OH, g.OW, w.wp16 != nullptr);
     if (mat) {
         float* upb = n.alloc_e((size_t)in.N * ov * in.C, oh);
         if (n.live()) n.run(nm_launch_upsample2(in, upb, n.s, oh));
@@ -367,7 +367,7 @@ TensorRef conv_gn(Net& n, const TensorRef& in, const ConvW& w, const NormW* gn, 
     }
     float* out = out_buf ? out_buf : n.alloc_e((size_t)in.N * ov * w.Cout, oh);
     float *part = nullptr, *scale = nullptr, *shift = nullptr;
-    const int nblk = nm_conv_blocks_per_frame(g, in.C);
+    const int nblk = nm_conv_blocks_per_frame(src, g);
     double* chsum = nullptr;
     if (gn) {
         part = n.alloc((size_t)in.N * nblk * w.Cout * 2);
@@ -575,7 +575,7 @@ TensorRef first_layer(Net& n, const float* occ, int N, int G, const FeatNetW& w,
     // conv - this tensor's only consumer - reads the constant field there (TensorRef::alt / brickmap).  Training keeps the dense
     // tensor (the backward pass reads it).
     const bool sparse = !rec && w.field_part && nm_conv_get_mode() == 1 && nm_ls().sparse_first &&
-                        nm_conv_pool16_eligible(Cout, G / 2, G / 2, G / 2, w.p1.c.wp16 != nullptr);
+                        nm_conv_plan::pool_on_pool_kernels(nm_conv_switches(), Cout, G / 2, G / 2, G / 2, w.p1.c.wp16 != nullptr);
     unsigned char* bmap = sparse ? reinterpret_cast<unsigned char*>(n.alloc(((size_t)N * nblk + 3) / 4)) : nullptr;
     unsigned char* bflags = sparse ? reinterpret_cast<unsigned char*>(n.alloc(((size_t)N * nblk + 3) / 4)) : nullptr;
     float* scale = n.alloc((size_t)N * Cout); float* shift = n.alloc((size_t)N * Cout);
@@ -598,7 +598,7 @@ void feature_net(Net& n, const float* occ, int N, int G, const FeatNetW& w, int 
     TensorRef x = first_layer(n, occ, N, G, w, r);
     x = pool(n, x, w.p1, r ? &r->p1 : nullptr);
     // (inference: r2's residual sum is evaluated by the pool conv that consumes it)
-    const bool lazy = !r && nm_ls().lazy_res && nm_conv_pool16_eligible(w.r2.c2.Cout, x.D / 2, x.H / 2, x.W / 2, w.p3.c.wp16 != nullptr) &&
+    const bool lazy = !r && nm_ls().lazy_res && nm_conv_plan::pool_on_pool_kernels(nm_conv_switches(), w.r2.c2.Cout, x.D / 2, x.H / 2, x.W / 2, w.p3.c.wp16 != nullptr) &&
                       x.D % 2 == 0 && x.H % 2 == 0 && x.W % 2 == 0;
     x = res(n, x, w.r2, nullptr, r ? &r->r2 : nullptr, lazy);
     x = pool(n, x, w.p3, r ? &r->p3 : nullptr);

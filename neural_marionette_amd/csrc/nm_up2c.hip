@@ -46,13 +46,9 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int BZ = 2, BY = 8, BX = 8;                 // coarse cells of a brick (per parity class: 128 GEMM rows)
-constexpr int HZ = BZ + 2, HY = BY + 2, HX = BX + 2;  // coarse halo tile
-constexpr int ZP = 104;                               // z-plane pitch in 16-byte slots: >= HY*HX and = 8 (mod 16)
-constexpr int HVP = HZ * ZP + 1;                      // slots per (chunk, hi|lo, lane half) plane; odd: staging writes spread over the banks
-constexpr int CG = 32;                                // input channels per LDS buffer (two buffers: one read by the MFMAs, one being staged)
-constexpr int NPLANES = CG / 16 * 4;
-constexpr size_t LDS_BYTES = (size_t)2 * NPLANES * HVP * 16 + 2 * CG * sizeof(float);      // + the next tile's GroupNorm scale / shift
+// the brick (BZ, BY, BX), its halo tile and LDS planes (HZ, HY, HX, ZP, HVP, CG, NPLANES, LDS_BYTES), the face kernels' line pitch (FP,
+// face_fpv) and conv_up2y_kernel's row tiles (YT): nm_conv_plan.h, where the launch plan reads them too
+using namespace nm_conv_plan::up2c;
 
 // (16-byte aligned: 128 bytes of kernel arguments, so the shell kernels' trailing ints start on a 16-byte boundary and arrive in one
 //  aligned scalar load)
@@ -697,7 +693,6 @@ __global__ __launch_bounds__(512, 1) void conv_up2c_x16_kernel(Up2cParams p) {
 // 128 -> 64 layer: 288 columns on 256 CUs).  NM355_UP2Y_MARCH: 0 never, 2 always marches.
 // The GroupNorm partials of class (pz, px), parity py go to slot 8 brick + 4 pz + 2 px + py: the class's two waves fill its two
 // column blocks - every slot is written once, in a fixed order.
-constexpr int YT = HY;
 struct StepPosY : StepPos { int iy; };      // iy: the brick's place in its column (0: all ten row tiles; else tiles 0 and 1 are carried)
 
 template <bool MARCH>
@@ -970,8 +965,7 @@ __global__ __launch_bounds__(512, 1) void conv_up2y_kernel(Up2cParams p) {
 // channels): staged once into LDS (activated, split), then 9 taps x Cin/16 k-steps per wave from LDS with the wave's own weights
 // streamed three k-steps ahead.  The result is added to the main kernel's output; the wave writes the GroupNorm partials of its
 // voxels' final values.
-constexpr int FP = 36;                                // slots per staged line (34 used)
-constexpr int FPV = 3 * FP + 1;                       // slots per plane
+constexpr int FPV = face_fpv(1);                      // slots per plane: three staged lines of FP slots (34 used)
 
 template <bool SINGLE, int IO = 0>
 __global__ __launch_bounds__(256, 4) void conv_up2c_face_kernel(Up2cParams p, int TY, int TX) {
@@ -1198,7 +1192,7 @@ __global__ __launch_bounds__(256, 4) void conv_up2c_edge_kernel(Up2cParams p, in
 // `off` (the line lies on an edge for this class), the ownership of a row, a group that ends at the last across-index (lines
 // f >= AC are skipped, never padded; their MFMAs run on staged clamped lines and are dropped).  Under p.ypad the y faces have no
 // groups at all; their (empty) partial slots are zeroed by the workgroups of the frame, 256 floats per workgroup and round.
-template <int R> constexpr int face_r_fpv() { return (R + 2) * FP + 1; }      // slots per plane (odd)
+template <int R> constexpr int face_r_fpv() { return face_fpv(R); }      // slots per plane (odd)
 
 template <int R, int P>
 __global__ __launch_bounds__(256, 2) void conv_up2c_face_r_kernel(Up2cParams p, int TY, int TX) {
@@ -1378,7 +1372,7 @@ __global__ __launch_bounds__(256, 2) void conv_up2c_face_r_kernel(Up2cParams p, 
 // sequence is conv_up2c_edge_kernel's.
 __global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, int TZ, int TY, int TX, int slot0) {
     constexpr int NHT = 2;                                             // output halves
-    __shared__ __attribute__((aligned(16))) float aff[4][2][128];                                  // [wave][scale | shift][channel] (Cin <= 128: nm_up2c_eligible)
+    __shared__ __attribute__((aligned(16))) float aff[4][2][128];                                  // [wave][scale | shift][channel] (Cin <= 128: nm_conv_plan::up2c_eligible)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, l31 = lane & 31;
     const int nXY = 8 * TZ, nXZ = 8 * TY, nYZ = 8 * TX, per_frame = nXY + nXZ + nYZ;
@@ -1551,13 +1545,6 @@ __global__ __launch_bounds__(256, 1) void conv_up2c_edge_p_kernel(Up2cParams p, 
 
 }  // namespace
 
-bool nm_up2c_eligible(int ID, int IH, int IW, int Cin, int Cout, int ks, int stride, int pad) {
-    return ks == 3 && stride == 1 && pad == 1 && ID % BZ == 0 && IH % BY == 0 && IW % BX == 0 && Cin % CG == 0 && Cout % 32 == 0 &&
-           ((Cin == 64 && Cout == 32) || (nm_ls().up2y && !nm_conv_single() && Cin <= 128 && Cout <= 64));      // (the wider layer: in the product form only - the one-product modes and NM355_UP2Y=0 keep it on conv_f16s)
-}
-
-bool nm_up2y_active() { return nm_ls().up2y != 0 && nm_ls().conv_mode == 1 && nm_conv_single() == 0; }
-
 size_t nm_up2c_weight_floats(int Cin, int Co_pad) {
     return (size_t)(TOTAL_TAPS + YSETS * 27) * (Cin >> 4) * 4 * Co_pad * 8 / 2;       // halves -> 4-byte units
 }
@@ -1567,14 +1554,6 @@ int nm_launch_up2c_compose(const float* w, int Cout, int Cin, int Co_pad, void* 
     hipLaunchKernelGGL(up2c_compose_kernel, dim3(2048), dim3(256), 0, s, w, Cout, Cin, Co_pad, reinterpret_cast<_Float16*>(packed));
     hipLaunchKernelGGL(up2y_compose_kernel, dim3(512), dim3(256), 0, s, w, Cout, Cin, Co_pad, reinterpret_cast<_Float16*>(packed));
     return nm_check_hip(hipGetLastError(), "up2c_compose launch");
-}
-
-static void shell_tiles(int ID, int IH, int IW, int& TZ, int& TY, int& TX) { TZ = (ID + 31) / 32; TY = (IH + 31) / 32; TX = (IW + 31) / 32; }
-static int face_groups(int ID, int IH, int IW) { int TZ, TY, TX; shell_tiles(ID, IH, IW, TZ, TY, TX); return 2 * ID * TY + 2 * ID * TX + 2 * IH * TX; }
-static int edge_items(int ID, int IH, int IW) { int TZ, TY, TX; shell_tiles(ID, IH, IW, TZ, TY, TX); return 8 * (TZ + TY + TX); }
-
-int nm_up2c_blocks_per_frame(int ID, int IH, int IW) {
-    return 8 * (ID / BZ) * (IH / BY) * (IW / BX) + 4 * face_groups(ID, IH, IW) + edge_items(ID, IH, IW);
 }
 
 // The one-product instantiations of the main / face / edge kernels by storage combination io (bit 0 bfloat16 input, bit 1 bfloat16
@@ -1588,41 +1567,25 @@ static void launch_io(void (*split)(P...), void (*const (&one)[4])(P...), bool s
 }
 
 int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bias, float* out, int Cout, int Co_pad, float* part,
-                        hipStream_t s, int out_h) {
-    if (!nm_up2c_eligible(in.D, in.H, in.W, in.C, Cout, 3, 1, 1) || !packed) { nm_set_error("conv_up2c: shape not eligible"); return NM_ERR_ARG; }
-    if ((in.scale == nullptr) != (in.shift == nullptr)) { nm_set_error("conv_up2c: scale/shift must come together"); return NM_ERR_ARG; }
+                        hipStream_t s, const nm_conv_plan::Up2cPlan& u) {
+    using namespace nm_conv_plan;
+    if (!packed) { nm_set_error("conv_up2c: no composite weight sets"); return NM_ERR_ARG; }
     static NmDeviceOnce attr_set;
     if (int rc = nm_raise_lds_limit(attr_set, 160 * 1024, "hipFuncSetAttribute(conv_up2c)", MAIN_ONE[0], MAIN_ONE[1], MAIN_ONE[2], MAIN_ONE[3],
                                     &conv_up2c_x16_kernel, &conv_up2y_kernel<false>, &conv_up2y_kernel<true>,
                                     &conv_up2c_face_r_kernel<2, 9>, &conv_up2c_face_r_kernel<4, 6>)) return rc;
-    const bool single = nm_conv_single() != 0;
-    const bool io16 = in.h || out_h;
-    if (io16 && !single) {
-        nm_set_error("conv_up2c: 16-bit storage (input %d / output %d) needs conv mode 4", in.h, out_h); return NM_ERR_UNSUPPORTED;
-    }
-    const int io = (in.h ? 1 : 0) | (out_h ? 2 : 0);
-    const int cus = nm_num_cus();
-    if (!cus) return NM_ERR_HIP;
+    const bool single = u.main == UP2C_ONE;
+    const int io = u.io;
     Up2cParams p;
     p.in = in.p; p.in_scale = in.scale; p.in_shift = in.shift; p.in_slope = in.slope;
     p.N = in.N; p.ID = in.D; p.IH = in.H; p.IW = in.W; p.Cin = in.C;
     p.wc = static_cast<const half8*>(packed); p.wy = p.wc + (size_t)TOTAL_TAPS * (in.C >> 4) * 4 * Co_pad; p.bias = bias; p.out = out; p.part = part;
     p.Cout = Cout; p.Co_pad = Co_pad;
-    p.nbz = in.D / BZ; p.nby = in.H / BY; p.nbx = in.W / BX;
-    p.nblk = nm_up2c_blocks_per_frame(in.D, in.H, in.W);
-    const int bricks = p.nbz * p.nby * p.nbx, total = p.N * bricks;
-    // conv_up2y_kernel: whole columns of bricks along y per workgroup where that leaves no CU without one (NM355_UP2Y_MARCH=2: always),
-    // zero padding along y in its epilogue (NM355_UP2Y_YPAD)
-    const bool y_main = io == 0 && !single && nm_ls().up2y;
-    const int columns = p.N * p.nbz * p.nbx;
-    // row tiles of the busiest workgroup: 10 per brick, or 10 + 8 (nby - 1) per column
-    const long long tiles_bricks = (long long)((total + cus - 1) / cus) * YT, tiles_columns = (long long)((columns + cus - 1) / cus) * (YT + (YT - 2) * (p.nby - 1));
-    p.march = y_main && p.nby > 1 && (nm_ls().up2y_march >= 2 || (nm_ls().up2y_march == 1 && columns >= cus && tiles_columns < tiles_bricks));
-    p.ypad = y_main && nm_ls().up2y_ypad != 0;
-    // (the one-product modes keep ONE kernel in fp32 and in bfloat16 storage: the instantiations are bit-compared with one another,
-    //  tests/test_storage16_gpu.py)
-    void (*const main_split)(Up2cParams) = !y_main ? conv_up2c_x16_kernel : p.march ? conv_up2y_kernel<true> : conv_up2y_kernel<false>;
-    launch_io(main_split, MAIN_ONE, single, io, dim3((unsigned)min(p.march ? columns : total, cus)), 512, LDS_BYTES, s, p);
+    p.nbz = u.nbz; p.nby = u.nby; p.nbx = u.nbx;
+    p.nblk = up2c::part_rows(in.D, in.H, in.W);
+    p.march = u.march; p.ypad = u.ypad;
+    void (*const main_split)(Up2cParams) = u.main == UP2C_X16 ? conv_up2c_x16_kernel : u.main == UP2Y_MARCH ? conv_up2y_kernel<true> : conv_up2y_kernel<false>;
+    launch_io(main_split, MAIN_ONE, single, io, dim3((unsigned)u.main_grid), 512, LDS_BYTES, s, p);
     int rc = nm_check_hip(hipGetLastError(), "conv_up2c launch");
     if (rc) return rc;
     // NM355_ENC_SCHED bit 2 (the lane is set by decode_frames only, nm_net.hip): the edge launch goes to the lane, behind the main
@@ -1636,30 +1599,16 @@ int nm_launch_conv_up2c(const TensorRef& in, const void* packed, const float* bi
         if ((rc = nm_check_hip(hipEventRecord(ls.shell_fork, s), "conv_up2c: shell fork event"))) return rc;
         if ((rc = nm_check_hip(hipStreamWaitEvent(se, ls.shell_fork, 0), "conv_up2c: shell lane wait"))) return rc;
     }
-    int TZ, TY, TX; shell_tiles(in.D, in.H, in.W, TZ, TY, TX);
-    const int fg = face_groups(in.D, in.H, in.W), ei = edge_items(in.D, in.H, in.W);
-    const size_t face_lds = (size_t)(in.C / 16 * 4) * FPV * 16;
-    // NM355_UP2C_SHELL (split-fp16, fp32 storage only; the one-product and 16-bit-storage instantiations keep the kernels below):
-    // units 0 the kernels below (A/B), 1 the face form (default), 2 the face and the edge form, 3 the edge form alone; tens: lines
-    // per face workgroup (2 or 4; else 4 at Cin <= 64 and 2 above: DESIGN 5).  The face form fixes a thread's channel octet across
-    // its staging items, so it takes the channel counts whose octets divide 256; any other keeps the kernel below.
-    const int shell = (io == 0 && !single) ? nm_ls().up2c_shell : 0;
-    const bool face_r = (shell % 10 == 1 || shell % 10 == 2) && 256 % (in.C / 8) == 0, edge_p = shell % 10 == 2 || shell % 10 == 3;
-    if (face_r) {
-        const int R = shell / 10 == 2 ? 2 : shell / 10 == 4 ? 4 : in.C <= 64 ? 4 : 2;
-        const int GD = (in.D + R - 1) / R, GH = (in.H + R - 1) / R;
-        const int groups = 2 * GD * TY + (p.ypad ? 0 : 2 * GD * TX) + 2 * GH * TX;
-        if (R == 2) hipLaunchKernelGGL((conv_up2c_face_r_kernel<2, 9>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<2>() * 16, s, p, TY, TX);
-        else hipLaunchKernelGGL((conv_up2c_face_r_kernel<4, 6>), dim3((unsigned)(p.N * groups)), dim3(256), (size_t)(in.C / 16 * 4) * face_r_fpv<4>() * 16, s, p, TY, TX);
+    const int TZ = u.sh.TZ, TY = u.sh.TY, TX = u.sh.TX;
+    if (u.face == FACE_R) {
+        if (u.R == 2) hipLaunchKernelGGL((conv_up2c_face_r_kernel<2, 9>), dim3((unsigned)u.face_grid), dim3(256), u.face_lds, s, p, TY, TX);
+        else hipLaunchKernelGGL((conv_up2c_face_r_kernel<4, 6>), dim3((unsigned)u.face_grid), dim3(256), u.face_lds, s, p, TY, TX);
     }
-    else launch_io(conv_up2c_face_kernel<false>, FACE_ONE, single, io, dim3((unsigned)(p.N * fg)), 256, face_lds, s, p, TY, TX);
+    else launch_io(conv_up2c_face_kernel<false>, FACE_ONE, single, io, dim3((unsigned)u.face_grid), 256, u.face_lds, s, p, TY, TX);
     rc = nm_check_hip(hipGetLastError(), "conv_up2c_face launch");
-    const long long items = (long long)p.N * ei;
-    // (one output half: the ring's registers leave one wave per SIMD, and 1.5 items per SIMD then run in two rounds - measured
-    //  slower than conv_up2c_edge_kernel on the 64 -> 32 layer, which keeps it)
     if (!rc) {
-        if (edge_p && Cout == 64) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, se, p, TZ, TY, TX, 8 * bricks + 4 * fg);
-        else launch_io(conv_up2c_edge_kernel<false>, EDGE_ONE, single, io, dim3((unsigned)((items + 3) / 4)), 256, 0, se, p, TZ, TY, TX, 8 * bricks + 4 * fg);
+        if (u.edge == EDGE_P) hipLaunchKernelGGL(conv_up2c_edge_p_kernel, dim3((unsigned)u.edge_grid), dim3(256), 0, se, p, TZ, TY, TX, u.slot0);
+        else launch_io(conv_up2c_edge_kernel<false>, EDGE_ONE, single, io, dim3((unsigned)u.edge_grid), 256, 0, se, p, TZ, TY, TX, u.slot0);
         rc = nm_check_hip(hipGetLastError(), "conv_up2c_edge launch");
         if (!rc && se != s && ls.prof_on) ++ls.side_launches;
     }

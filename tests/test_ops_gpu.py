@@ -166,6 +166,43 @@ def test_conv3d_one_product_mode_beyond_1024_output_channels(ctx):
     assert not out.any(), "a refused call wrote its output"
 
 
+# conv mode, bfloat16 input, bfloat16 output, Cin, Cout, ks, stride, pad, input size, fused upsample, kernel family the refusal names
+REFUSED_CONVS = [
+    (1, 1, 1, 32, 32, 3, 1, 1, 16, 0, "conv_f16p:"),
+    (4, 1, 0, 32, 64, 3, 1, 1, 16, 0, "conv_f16p2:"),
+    (4, 1, 1, 32, 32, 3, 1, 1, 8, 0, "conv_f16s:"),
+    (0, 1, 1, 16, 32, 1, 1, 0, 8, 0, "conv (fp32 MFMA kernel):"),
+    (4, 0, 1, 32, 32, 2, 2, 0, 16, 0, "conv_pool_f16q:"),
+    (1, 0, 1, 64, 32, 3, 1, 1, 8, 1, "conv_up2c:"),
+]
+
+
+@pytest.mark.parametrize("case", REFUSED_CONVS, ids=lambda c: "m%d_io%d%d_ci%d_co%d_k%d_d%d_up%d" % (c[:6] + c[8:10]))
+def test_refused_convs_launch_nothing(ctx, case):
+    """Every bfloat16 storage combination without a kernel instantiation is refused by the launch plan (nm_conv_plan.h) before any conv
+    kernel is launched: NM_ERR_UNSUPPORTED, a message that names the kernel family the call was routed to, and the output untouched."""
+    from neural_marionette_amd import _lib
+    mode, in16, out16, Cin, Cout, ks, stride, pad, size, up2, family = case
+    N, osize = 1, ((2 if up2 else 1) * size + 2 * pad - ks) // stride + 1
+    x = torch.zeros(N, size, size, size, Cin, dtype=torch.bfloat16 if in16 else torch.float32, device="cuda")
+    out = torch.full((N, osize, osize, osize, Cout), 7.0, dtype=torch.bfloat16 if out16 else torch.float32, device="cuda")
+    w = torch.zeros(Cout, Cin, ks, ks, ks, device="cuda"); b = torch.zeros(Cout, device="cuda")
+    _lib.check(ctx.lib.nm_set_conv_mode(ctx.handle, mode), "set_conv_mode")
+    _lib.check(ctx.lib.nm_op_set_storage16(ctx.handle, in16, out16), "op_set_storage16")
+    try:
+        rc = ctx.lib.nm_op_conv3d(ctx.handle, _lib.ptr(x), N, size, size, size, Cin, None, None, 1.0, _lib.ptr(w), _lib.ptr(b),
+                                  Cout, ks, stride, pad, _lib.ptr(out), 0, None, None, None, None, up2)
+        msg = ctx.lib.nm_last_error()
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(ctx.lib.nm_op_set_storage16(ctx.handle, 0, 0), "op_set_storage16")
+        _lib.check(ctx.lib.nm_set_conv_mode(ctx.handle, 1), "set_conv_mode")
+    msg = msg.decode() if isinstance(msg, bytes) else str(msg)
+    assert rc == _lib.NM_ERR_UNSUPPORTED, (rc, msg)
+    assert family in msg, msg
+    assert bool((out == 7.0).all()), "a refused call wrote its output"
+
+
 @pytest.mark.parametrize("mode", [0, 1, 3], ids=["fp32mfma", "split16", "f16"])
 @pytest.mark.parametrize("Cin,Cout,size,prologue,N", [(128, 64, 8, False, 2), (64, 32, 12, True, 2), (16, 32, 5, True, 2),
                                                        (32, 32, 16, True, 5), (48, 32, 8, False, 40), (64, 64, 16, True, 3)])
